@@ -10,9 +10,13 @@ Uq1-Uq5 unproject + dilate.  Shapes are independent, so ranks shard SHAPES with 
 (weak scaling: one shape per rank per step); `--parallel views` instead splits the 8 views of one shape across
 ranks and assembles them with a single RCCL all_gather (strong scaling).
 Random-init UNet weights of the reference architecture (the checkpoint cannot be fetched offline), synthetic shape.
-Rank 0 prints ONE JSON line (contract in the task statement) incl. `roofline` (dominant kernel: the 3x3
-implicit-GEMM conv, timed with HIP events on its launch stream inside the timed region) and `cpu_baseline`
-(the oracle's CPU restatement of the reference's 'nearest' path on a bounded sample, rank 0 / N=1 only).
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times the K steps and prints
+the line (`roofline`, `extras` and `cpu_baseline` are null).  `--full` adds the side measurements: `roofline` (dominant kernel: the
+3x3 implicit-GEMM conv, timed with HIP events on its launch stream inside the timed region, plus the box calibration and the clock /
+power sampled under load), `extras` (other workloads and configurations, timed after the timed region) and `cpu_baseline` (the
+oracle's CPU restatement of the reference's 'nearest' path on a bounded sample, rank 0 / N=1 only).
+
+  --dump-outputs DIR    after the timed steps, rank 0 writes what its last step returned as DIR/<name>.npy (float32 / float64)
 """
 import argparse
 import json
@@ -303,6 +307,50 @@ def calibrate(dev, seconds=3.0):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+_FULL_RESULT = ('vertices', 'uvs', 'faces', 'mesh_tex_idx', 'atlas', 'mask')     # colorize_one_mesh's 6-tuple
+
+
+def _named_outputs(res, prefix=''):
+    """What one step returned, flattened to {name: tensor}: an atlas, colorize_one_mesh's 6-tuple, or a list of either (one per shape)."""
+    if torch.is_tensor(res):
+        return {prefix + 'atlas': res}
+    if isinstance(res, tuple) and len(res) == len(_FULL_RESULT):
+        return {prefix + n: t for n, t in zip(_FULL_RESULT, res) if torch.is_tensor(t)}
+    if isinstance(res, (list, tuple)):
+        out = {}
+        for i, r in enumerate(res):
+            out.update(_named_outputs(r, f'{prefix}shape{i}_'))
+        return out
+    raise TypeError(f"bench step returned {type(res).__name__}")
+
+
+def dump_outputs(res, out_dir):
+    """Writes the step's arrays as out_dir/<name>.npy, converted exactly: floating, bool and 8 / 16-bit integer data as float32 (float64
+    stays float64), wider integers as float64.  At most DUMP_BUDGET_BYTES in all, file headers included: arrays beyond their share of the
+    budget are replaced by a fixed sample (seed 0, sorted flat indices, the same for every run of the same arguments).
+    Returns {name: {shape, dtype, sampled}}."""
+    arrs = {}
+    for name, t in _named_outputs(res).items():
+        a = t.detach().cpu().numpy()
+        wide = a.dtype == np.float64 or (np.issubdtype(a.dtype, np.integer) and a.dtype.itemsize > 2)
+        arrs[name] = a.astype(np.float64 if wide else np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    left, info = DUMP_BUDGET_BYTES - 1024 * len(arrs), {}                # (1 KiB per file covers its .npy header)
+    for i, name in enumerate(sorted(arrs, key=lambda n: arrs[n].nbytes)):
+        a = arrs[name]
+        share = left // (len(arrs) - i)
+        sampled = a.nbytes > share
+        if sampled:
+            k = share // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        left -= a.nbytes
+        info[name] = dict(shape=list(arrs[name].shape), dtype=str(a.dtype), sampled=bool(sampled))
+    return info
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -311,20 +359,26 @@ def main():
     ap.add_argument('--workload', default='ddnm', choices=['ddnm', 'nearest'])
     ap.add_argument('--parallel', default='shapes', choices=['shapes', 'views'])
     ap.add_argument('--ddnm-steps', type=int, default=100)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--profile-period', type=int, default=1, help='HIP events around the dominant kernel in every k-th UNet forward of the timed '
-                    'region (1 = every forward, 0 = none: roofline.achieved is then null)')
+    ap.add_argument('--full', action='store_true', help='also the side measurements: roofline (HIP events in the timed region, box '
+                    'calibration, clock / power under load), extras and cpu_baseline.  Off: set up, warm up, time the steps, print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help="after the timed steps, write what rank 0's last step returned "
+                    'as DIR/<name>.npy (float32 / float64, at most 64 MB in all; same arguments = same inputs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no cpu_baseline')
+    ap.add_argument('--profile-period', type=int, default=1, help='with --full: HIP events around the dominant kernel in every k-th UNet forward '
+                    'of the timed region (1 = every forward, 0 = none: roofline.achieved is then null)')
     ap.add_argument('--no-graphs', action='store_true', help='nearest workload with several shapes per step: eager launches on streams '
                                                              'instead of one HIP graph per shape')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend (nccl = RCCL; gloo only for the one-GPU rehearsal of the N > 1 path)")
     ap.add_argument('--one-device', action='store_true', help='rehearsal of the N > 1 code path on a one-GPU box: every rank uses cuda:0 (with --backend gloo)')
-    ap.add_argument('--no-extras', action='store_true', help='skip the nearest-workload / one-shape-latency side measurements')
-    ap.add_argument('--extras-timeout', type=float, default=300.0, help='N > 1: seconds the view-parallel side figure may take before the headline line is printed without it')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the nearest-workload / one-shape-latency side measurements')
+    ap.add_argument('--extras-timeout', type=float, default=300.0, help='with --full, N > 1: seconds the view-parallel side figure may take before the headline line is printed without it')
     ap.add_argument('--shapes-per-step', type=int, default=4,
                     help='independent shapes textured per step on each GPU, their 8-view sets batched through the UNet together '
                          '(BASELINE configs[4] style); 1 = one shape at a time (configs[2], lowest latency).  What each setting measures on '
                          'one MI355X is in DESIGN.md section 8 (the default is the fastest)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     rank = int(os.environ.get('RANK', 0))
     world = int(os.environ.get('WORLD_SIZE', 1))
@@ -413,17 +467,20 @@ def main():
     for _ in range(args.warmup):
         step()
     sync()
-    if inpainter is not None:
+    if inpainter is not None and args.full:
         inpainter.model.profile(args.profile_period)
-    sampler = LoadSampler(dev) if rank == 0 else None
+    sampler = LoadSampler(dev) if rank == 0 and args.full else None
     if sampler is not None:
         sampler.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     sync()
     dt = time.perf_counter() - t0
     under_load = sampler.stop() if sampler is not None else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, args.dump_outputs)
+    del last
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -445,7 +502,7 @@ def main():
                 return
             printed[0] = True
         calib = None
-        if rank == 0 and inpainter is not None and not args.no_extras and not from_watchdog:
+        if rank == 0 and inpainter is not None and args.full and not args.no_extras and not from_watchdog:
             calib = calibrate(dev)
             if roofline is not None and calib.get('gemm_f16_random_tflops'):
                 roofline['calibrated_peak'] = calib['gemm_f16_random_tflops']
@@ -474,13 +531,15 @@ def main():
                                    parallelism=f"{args.parallel}-parallel x{world}", views_per_unet_batch=views_here,
                                    shapes_per_step=world * SPS if args.parallel == 'shapes' else 1),
                        roofline=roofline, extras=extras_ or None)
-            if world == 1 and not args.no_cpu_baseline:
+            if world == 1 and args.full and not args.no_cpu_baseline:
                 out['cpu_baseline'] = cpu_baseline()
             else:
                 out['cpu_baseline'] = None
             print(json.dumps(out), flush=True)
 
-    if inpainter is not None:
+    if not args.full:
+        pass                                        # a plain run: the headline figure only (roofline / extras / cpu_baseline null)
+    elif inpainter is not None:
         ms, flops, launches = inpainter.model.profile_read()
         ams, aflops, alaunches = inpainter.model.profile_read(attention=True)
         inpainter.model.profile(False)

@@ -1,4 +1,4 @@
-"""bench.py contract on the GPU: one JSON line with the driver's fields plus `roofline` and `cpu_baseline`."""
+"""bench.py contract on the GPU: one JSON line with the driver's fields; with --full also `roofline`, `extras` and `cpu_baseline`."""
 import json
 import os
 import subprocess
@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.parametrize("extra", [[], ["--shapes-per-step", "1"], ["--workload", "nearest"]])
 def test_bench_prints_one_json_line_with_the_contract_fields(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--ddnm-steps", "2", "--no-cpu-baseline"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--ddnm-steps", "2", "--no-cpu-baseline", "--full"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -45,7 +45,7 @@ def test_bench_two_ranks_rehearsal_carries_the_view_parallel_figure():
     s = socket.socket(); s.bind(('127.0.0.1', 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--ddnm-steps", "2", "--shapes-per-step", "1",
-           "--backend", "gloo", "--one-device"]
+           "--backend", "gloo", "--one-device", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -66,7 +66,7 @@ def test_bench_two_ranks_headline_survives_a_side_figure_that_does_not_come_back
     s = socket.socket(); s.bind(('127.0.0.1', 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--ddnm-steps", "2", "--shapes-per-step", "1",
-           "--backend", "gloo", "--one-device", "--extras-timeout", "0.01"]
+           "--backend", "gloo", "--one-device", "--extras-timeout", "0.01", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -74,3 +74,42 @@ def test_bench_two_ranks_headline_survives_a_side_figure_that_does_not_come_back
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["roofline"]["achieved"] > 0
     assert "error" in d["extras"]["view_parallel"]
+
+
+def _run_plain(args, tmp):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", str(tmp)] + args
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline only (no side measurements), --steps sets the timed steps, and --dump-outputs
+    writes the atlases of the last step (four shapes per step by default) as float32 .npy files within the 64 MB budget."""
+    import numpy as np
+    d = _run_plain(["--steps", "2", "--warmup", "1", "--ddnm-steps", "2"], tmp_path / "dump")
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "shapes/hour" and d["higher_is_better"] is True
+    assert abs(d["value"] - 3600e3 * d["config"]["shapes_per_step"] / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert d["roofline"] is None and d["extras"] is None and d["cpu_baseline"] is None
+    files = sorted(os.listdir(tmp_path / "dump"))
+    assert files == [f"shape{i}_atlas.npy" for i in range(4)], files
+    assert sum(os.path.getsize(tmp_path / "dump" / f) for f in files) <= 64e6
+    for f in files:
+        a = np.load(tmp_path / "dump" / f)
+        assert a.dtype == np.float32 and a.shape == (1024, 1024, 3) and np.isfinite(a).all() and a.std() > 0
+
+
+def test_bench_dumped_outputs_repeat_run_to_run(tmp_path):
+    """Same arguments, same inputs: two plain runs of the (deterministic) nearest workload dump identical arrays."""
+    import numpy as np
+    args = ["--workload", "nearest", "--steps", "2", "--warmup", "1"]
+    _run_plain(args, tmp_path / "a")
+    _run_plain(args, tmp_path / "b")
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files and files == sorted(os.listdir(tmp_path / "b"))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f

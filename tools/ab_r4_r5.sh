@@ -9,8 +9,8 @@ cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out; O=gpurun_out/r05_ab_r4_r5.txt; : > $
 R=${1:-3}
 for i in $(seq 1 $R); do
   for arm in r4 r5; do
-    if [ $arm = r4 ]; then d=build/r4tree; else d=.; fi
-    line=$(cd $d && python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | tail -1)
+    if [ $arm = r4 ]; then d=build/r4tree; full=; else d=.; full=--full; fi     # (the round-4 bench.py always printed the roofline)
+    line=$(cd $d && python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras $full 2>/dev/null | tail -1)
     echo "$arm run $i: $(python - "$line" <<'PY'
 import json, sys
 j = json.loads(sys.argv[1]); r = j['roofline']

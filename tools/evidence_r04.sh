@@ -3,7 +3,8 @@
 set -euo pipefail
 : "${GRAFT_REPO_ROOT:?}"
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/ev
-python bench.py > gpurun_out/ev/bench_full.json 2> gpurun_out/ev/bench_full.err
+EV=$_                                  # (the directory made on the line above)
+python bench.py --full > "$EV"/bench_full.json 2> "$EV"/bench_full.err
 python tools/time_unet.py --batches 1 2 4 8 32 --iters 20 --sampler-steps 20 --out gpurun_out/ev/unet_latency.json > gpurun_out/ev/unet_latency.log 2>&1
 python tools/time_stages.py > gpurun_out/ev/stage_times.log 2>&1; cp gpurun_out/stage_times.json gpurun_out/ev/
 cd /tmp && export TMPDIR=/tmp

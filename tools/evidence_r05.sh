@@ -1,10 +1,10 @@
 #!/bin/bash
-# Round-5 evidence set (GPU box): bench line (defaults), rocprofv3 kernel stats of the same command, PMC passes (dominant kernel + per
+# Round-5 evidence set (GPU box): bench line (defaults, --full), rocprofv3 kernel stats of the same command, PMC passes (dominant kernel + per
 # kernel), UNet latency table, stage times, nearest-workload kernel stats.  Everything lands in gpurun_out/ev5/ (small files only).
 set -uo pipefail
 : "${GRAFT_REPO_ROOT:?}"
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/ev5; E=gpurun_out/ev5
-python bench.py > $E/bench_full.json 2> $E/bench_full.err
+python bench.py --full > $E/bench_full.json 2> $E/bench_full.err
 python tools/time_unet.py --batches 1 2 4 8 32 --iters 20 --sampler-steps 20 --out $E/unet_latency.json > $E/unet_latency.log 2>&1
 python tools/time_stages.py > $E/stage_times.log 2>&1; cp gpurun_out/stage_times.json $E/ 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
