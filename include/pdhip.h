@@ -73,6 +73,20 @@ int pdhip_raster_barycentrics(const float* pos /*[V,Vn,4]*/, int V, int Vn, cons
 int pdhip_interpolate(const float* attr /*[Na,C]*/, int C, const int32_t* tri /*[F,3]*/, const int64_t* face_idxs,
                       const float* bary, long long pixels, float* out /*[pixels,C]*/, void* stream);
 
+/* ---- UV unwrapping (the xatlas.parametrize call of xatlas_uvmap_w_face_id, models/get3d/extract_texture_map.py:42-44; the layout is
+ *      this library's own): charts of faces sharing a dominant signed normal axis (n.axis >= cos 70 for every face of a chart),
+ *      orthographic projection per chart, one world-to-texel scale for all charts, shelf packing with `gutter` texels around every
+ *      chart, no texel centre covered twice (the rasteriser's coverage rules; overlapping charts are split and re-packed).
+ *      vertices [Vn,3] f32, faces [F,3] i64 -> uvs [T,2] in [0,1] (capacity 3F entries: one per (chart, vertex) pair), tex_idx [F,3] i64,
+ *      face_chart [F] i32 (chart id = the smallest face index of the chart), counts (device, 4 x i32): T, charts, split rounds,
+ *      error flags.  ws: pdhip_uv_atlas_ws_bytes(Vn, F) bytes.  Synchronises `stream` once per packing round (one word read);
+ *      a face index outside [0, Vn) or charts that cannot fit the atlas return PDHIP_E_ARG with the cause. */
+size_t pdhip_uv_atlas_ws_bytes(int Vn, int F);
+int pdhip_uv_atlas(const float* vertices /*[Vn,3]*/, int Vn, const int64_t* faces /*[F,3]*/, int F, int resolution, int gutter,
+                   float* uvs /*[3F,2] capacity*/, int64_t* tex_idx /*[F,3]*/, int32_t* face_chart /*[F]*/,
+                   int32_t* counts /*device: [0] = T uv entries used, [1] = charts, [2] = split rounds, [3] = error flags*/,
+                   void* ws, void* stream);
+
 /* ---- SURVEY 8(e) configs[4], round 4: S independent shapes of EQUAL sizes (Vn vertices, F faces, N points, atlas A) through the same V
  *      cameras in ONE launch per stage.  Per-shape inputs are stacked ([S, ...]); every per-view array has S*V leading entries, view
  *      g = s * V + v; results equal the per-shape entry points bit for bit (tests/test_gpu_round4.py).  The per-view-independent stages

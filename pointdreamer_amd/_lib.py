@@ -35,6 +35,8 @@ _SIGS = {
     'pdhip_debug_set_raster_path': (C.c_int, [i32]),
     'pdhip_raster_barycentrics': (C.c_int, [vp, i32, i32, vp, i32, vp, vp, vp]),
     'pdhip_interpolate': (C.c_int, [vp, i32, vp, vp, vp, C.c_longlong, vp, vp]),
+    'pdhip_uv_atlas_ws_bytes': (sz, [i32, i32]),
+    'pdhip_uv_atlas': (C.c_int, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     'pdhip_rescale_vertices': (C.c_int, [vp, i32, i32, vp, vp, vp, f64, vp]),
     'pdhip_optimize_color_ws_bytes': (sz, [i32, i32, i32]),
     'pdhip_optimize_color': (C.c_int, [vp, i32, vp, vp, i32, i32, vp, i32, vp, f64, i32, vp, vp, vp]),

@@ -4,10 +4,11 @@ same YAML keys (configs/*.yaml of the reference) and the same output tree as /ro
   <output_path>/<ply stem>_<config stem>/config.yaml, input_pc.ply,
       models/model_normalized.{obj,mtl,png}, others/{k}_{sparse,mask0,mask2,inpainted}.png, others/atlas_wo_background.png
 
-Geometry and UV unwrapping are UPSTREAM of this build (POCO / SPR / xatlas are out of scope):
-the driver uses the reference's own drop-in hooks -- `<pc>_untextured_mesh.obj` next to the PLY (demo.py:391-399)
-and the cached `geo/xatlas_<res>.pth` dict (demo.py:428-448); if no mesh is supplied it falls back to the build's
-stand-in UV sphere fitted to the cloud (clearly logged), so that the texturing path can be exercised end to end.
+Geometry is UPSTREAM of this build (POCO / SPR are out of scope): the driver uses the reference's own
+drop-in hooks -- `<pc>_untextured_mesh.obj` next to the PLY (demo.py:391-399) and the cached `geo/xatlas_<res>.pth` dict
+(demo.py:428-448).  A mesh without `vt` records is unwrapped on the device (extract_texture_map.xatlas_uvmap_w_face_id, this
+build's own chart layout) and the dict cached; if no mesh is supplied it falls back to the build's stand-in UV sphere fitted to
+the cloud (clearly logged), so that the texturing path can be exercised end to end.
 
   python -m pointdreamer_amd.demo --config configs/nearest.yaml --pc_file dataset/demo_data/clock.ply
 """
@@ -110,7 +111,7 @@ _STANDIN = {}
 def standin_geometry(xyz, atlas_res, device, logger):
     """No mesh next to the PLY and no POCO here: UV sphere (radius 0.5 = the normalised cloud's half extent) + analytic atlas.
     The same for every cloud, so a directory run builds it once per (atlas_res, device)."""
-    logger.warning('no <pc>_untextured_mesh.obj supplied: using the stand-in UV sphere geometry (POCO/SPR/xatlas are upstream)')
+    logger.warning('no <pc>_untextured_mesh.obj supplied: using the stand-in UV sphere geometry (POCO/SPR are upstream)')
     key = (int(atlas_res), str(device))
     if key not in _STANDIN:
         _STANDIN[key] = _standin_geometry(atlas_res, device)
@@ -183,8 +184,15 @@ def _load_shape(cfg, pc_file, name, device, logger):
             torch.save({k: t.cpu() for k, t in xatlas_dict.items()}, xatlas_file)
             logger.info(f'UV atlas rasterised from the mesh\'s own vt/f records -> {xatlas_file}')
         else:
-            raise FileNotFoundError(f"{xatlas_file} not found and {geo_path} has no vt / f v/vt records: the chart parametrisation "
-                                    "(xatlas.parametrize, CPU third-party) is upstream of this build; provide either")
+            # no UVs (what POCO / SPR emit): unwrap on the device, then rasterise + interpolate, and cache the dict like the reference
+            # does after xatlas_uvmap_w_face_id (demo.py:428-449)
+            from .extract_texture_map import xatlas_uvmap_w_face_id
+            logger.info('UV unwrapping...')
+            start = time.time()
+            uvs, tex_idx, gb_pos, amask, fid = xatlas_uvmap_w_face_id(None, vertices, faces, cfg.xatlas_texture_res)
+            xatlas_dict = dict(uvs=uvs, mesh_tex_idx=tex_idx, gb_pos=gb_pos, mask=amask, per_atlas_pixel_face_id=fid)
+            torch.save({k: t.cpu() for k, t in xatlas_dict.items()}, xatlas_file)
+            logger.info(f'UV unwrapping time: {time.time() - start} s -> {xatlas_file}')
         logger.info('Existing geometry + xatlas data loaded')
     else:
         vertices, faces, xatlas_dict = standin_geometry(xyz, cfg.xatlas_texture_res, device, logger)

@@ -135,3 +135,32 @@ def make_shape(n_points=30000, A=1024, stacks=50, slices=100, seed=0, n_charts=1
     xyz, rgb = sphere_points(n_points, seed=seed)
     return dict(vertices=vertices, faces=faces, f_normals=face_normals(vertices, faces),
                 gb_pos=gb_pos, mask=mask, per_atlas_pixel_face_id=fid, points=xyz, colors=rgb)
+
+
+def icosphere(n, radius=0.5, noise=0.0, seed=0):
+    """Icosahedron with every face cut into n^2 triangles (20 n^2 faces, shared vertices welded), projected onto the sphere, each
+    vertex then moved radially by a factor 1 + noise * N(0, 1): a stand-in for a marching-cubes surface of a given face count."""
+    t = (1 + 5 ** 0.5) / 2
+    V = np.array([[-1, t, 0], [1, t, 0], [-1, -t, 0], [1, -t, 0], [0, -1, t], [0, 1, t], [0, -1, -t], [0, 1, -t],
+                  [t, 0, -1], [t, 0, 1], [-t, 0, -1], [-t, 0, 1]], np.float64)
+    F = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    ii, jj = np.meshgrid(np.arange(n + 1), np.arange(n + 1), indexing='ij')
+    keep = ii + jj <= n
+    ii, jj = ii[keep], jj[keep]
+    lid = -np.ones((n + 2, n + 2), np.int64)
+    lid[ii, jj] = np.arange(len(ii))
+    i, j = np.meshgrid(np.arange(n), np.arange(n), indexing='ij')
+    up = i + j < n
+    down = i + j + 2 <= n
+    tri = np.concatenate([np.stack([lid[i, j], lid[i + 1, j], lid[i, j + 1]], -1)[up],
+                          np.stack([lid[i + 1, j], lid[i + 1, j + 1], lid[i, j + 1]], -1)[down]])
+    vs = [V[a] + (V[b] - V[a]) * (ii[:, None] / n) + (V[c] - V[a]) * (jj[:, None] / n) for a, b, c in F]
+    fs = [tri + k * len(ii) for k in range(len(F))]
+    v, f = np.concatenate(vs), np.concatenate(fs)
+    v = v / np.linalg.norm(v, axis=1, keepdims=True)
+    _, first, inv = np.unique(np.round(v, 9), axis=0, return_index=True, return_inverse=True)
+    v, f = v[first], inv.reshape(-1)[f]
+    rng = np.random.default_rng(seed)
+    v = v * radius * (1.0 + noise * rng.standard_normal((len(v), 1)))
+    return v.astype(F32), f.astype(np.int64)
