@@ -87,6 +87,34 @@ int pdhip_uv_atlas(const float* vertices /*[Vn,3]*/, int Vn, const int64_t* face
                    int32_t* counts /*device: [0] = T uv entries used, [1] = charts, [2] = split rounds, [3] = error flags*/,
                    void* ws, void* stream);
 
+/* ---- Surface reconstruction from the cloud (baselines/spr.py:recon_one_shape_SPR: normals for a point set + screened Poisson through
+ *      pymeshlab on the CPU there; here a dense-grid Poisson solve and marching cubes on the device, the layout and the mesh are this
+ *      library's own).  points [N,3] f32, N >= 16.
+ *      pdhip_estimate_normals: k nearest neighbours (3 <= k <= 32, the point itself included) through a sorted cell list, normal =
+ *      eigenvector of the smallest eigenvalue of the neighbourhood covariance, oriented (1) by the votes sign(n . (eye - p)) of the
+ *      n_eyes (<= 64) Fibonacci eyes on the sphere of radius eye_radius * (largest extent) round the cloud's centre that SEE the point
+ *      (pdhip_hidden_point_removal), (2) by up to 32 Jacobi rounds of the majority of sign(n_i . n_j) over the oriented neighbours,
+ *      (3) by the nearest oriented neighbour.  counts (device, 4 x i32): points oriented by rule 1, 2, 3, and left as computed (no
+ *      oriented neighbour); they add up to N.  ws: pdhip_estimate_normals_ws_bytes(N, k, n_eyes).
+ *      pdhip_surface_recon: the indicator function chi (HIGHER INSIDE the solid; normals point outwards) on a grid of 2^depth cells per
+ *      axis (depth 6, 7, 8; cell size h = largest extent / (0.75 * 2^depth), the cloud's bounding cube centred), solved by conjugate
+ *      gradients to a relative residual of 1e-4, iso value = mean of chi at the points; marching cubes with one vertex per crossing grid
+ *      edge: a closed, consistently oriented triangle mesh, counter-clockwise seen from outside, every component returned.
+ *      vertices [vertex_capacity,3] f32, faces [face_capacity,3] i64 (never more than 3 (2^depth + 1)^3 vertices and 5 * 8^depth faces;
+ *      a closed surface of area S has about 2 S / h^2 faces and half as many vertices); colors [N,3] / vertex_colors
+ *      [vertex_capacity,3] (both or neither): colour of the nearest cloud point.  counts (device, 4 x i32): vertices, faces, solver
+ *      iterations, 0; they are written even when the capacities are too small (PDHIP_E_ARG, nothing written past the buffers).
+ *      info (device, 8 x f32): h, grid origin x y z, iso value, relative residual reached, splat radius, nodes per axis.
+ *      Both synchronise `stream` (bounding box; solver status every 32 iterations; sizes).  Measured: profiles/surface_recon_bench.txt.  All points equal, points on a plane or a
+ *      line, a solve that does not converge, an empty or inverted surface: PDHIP_E_ARG with the cause.  Two calls give equal bytes. */
+size_t pdhip_estimate_normals_ws_bytes(int N, int k, int n_eyes);
+int pdhip_estimate_normals(const float* points /*[N,3]*/, int N, int k, int n_eyes, double eye_radius, float* normals /*[N,3]*/,
+                           int32_t* counts /*device [4]*/, void* ws, void* stream);
+size_t pdhip_surface_recon_ws_bytes(int N, int depth);
+int pdhip_surface_recon(const float* points /*[N,3]*/, const float* normals /*[N,3]*/, const float* colors /*[N,3] or NULL*/, int N, int depth,
+                        float* vertices, int vertex_capacity, int64_t* faces, int face_capacity, float* vertex_colors /*or NULL*/,
+                        int32_t* counts /*device [4]*/, float* info /*device [8]*/, void* ws, void* stream);
+
 /* ---- SURVEY 8(e) configs[4], round 4: S independent shapes of EQUAL sizes (Vn vertices, F faces, N points, atlas A) through the same V
  *      cameras in ONE launch per stage.  Per-shape inputs are stacked ([S, ...]); every per-view array has S*V leading entries, view
  *      g = s * V + v; results equal the per-shape entry points bit for bit (tests/test_gpu_round4.py).  The per-view-independent stages
@@ -368,6 +396,8 @@ int pdhip_io_read_ply_xyzrgb(const char* path, float* xyz /*[n,3] host*/, uint8_
  * double: `%f` of a float32 value is printed from its exact double). */
 int pdhip_io_write_obj_mtl(const char* obj_path, const char* mtl_path, const char* texture_stem, const double* points, long long P,
                            const double* tcoords, long long T, const int64_t* faces, const int64_t* facetex, long long F);
+/* untextured OBJ (`v` with 9 significant digits: float32 round trip; `f a b c`), written to a per-process temporary and renamed */
+int pdhip_io_write_obj_plain(const char* obj_path, const float* points /*[P,3] host*/, long long P, const int64_t* faces /*[F,3] host*/, long long F);
 /* 8-bit RGB / RGBA PNG (utils/utils_2d.py:351-399 save path); hwc: host [H,W,channels] */
 int pdhip_io_write_png(const char* path, const uint8_t* hwc, int H, int W, int channels, int zlib_level);
 /* device: out[h,w,c] = uint8(clip(img[c,h,w] * 255, 0, 255)) -- the conversion the reference does on the host before saving */

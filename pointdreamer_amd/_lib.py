@@ -37,6 +37,10 @@ _SIGS = {
     'pdhip_interpolate': (C.c_int, [vp, i32, vp, vp, vp, C.c_longlong, vp, vp]),
     'pdhip_uv_atlas_ws_bytes': (sz, [i32, i32]),
     'pdhip_uv_atlas': (C.c_int, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    'pdhip_estimate_normals_ws_bytes': (sz, [i32, i32, i32]),
+    'pdhip_estimate_normals': (C.c_int, [vp, i32, i32, i32, f64, vp, vp, vp, vp]),
+    'pdhip_surface_recon_ws_bytes': (sz, [i32, i32]),
+    'pdhip_surface_recon': (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     'pdhip_rescale_vertices': (C.c_int, [vp, i32, i32, vp, vp, vp, f64, vp]),
     'pdhip_optimize_color_ws_bytes': (sz, [i32, i32, i32]),
     'pdhip_optimize_color': (C.c_int, [vp, i32, vp, vp, i32, i32, vp, i32, vp, f64, i32, vp, vp, vp]),
@@ -67,6 +71,7 @@ _SIGS = {
     'pdhip_io_ply_count': (C.c_longlong, [C.c_char_p]),
     'pdhip_io_read_ply_xyzrgb': (C.c_int, [C.c_char_p, vp, vp, C.c_longlong]),
     'pdhip_io_write_obj_mtl': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, vp, C.c_longlong, vp, C.c_longlong, vp, vp, C.c_longlong]),
+    'pdhip_io_write_obj_plain': (C.c_int, [C.c_char_p, vp, C.c_longlong, vp, C.c_longlong]),
     'pdhip_io_write_png': (C.c_int, [C.c_char_p, vp, i32, i32, i32, i32]),
     'pdhip_chw_f32_to_hwc_u8': (C.c_int, [vp, i32, i32, i32, vp, vp]),
     'pdhip_mark_unpainted_faces': (C.c_int, [vp, vp, i32, i32, vp, vp]),

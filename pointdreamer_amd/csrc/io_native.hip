@@ -14,6 +14,7 @@
 #include <atomic>
 #include <sstream>
 #include <string.h>
+#include <unistd.h>
 using namespace pdhip;
 
 namespace {
@@ -150,6 +151,34 @@ extern "C" int pdhip_io_write_obj_mtl(const char* obj_path, const char* mtl_path
     const size_t w = fwrite(out.data(), 1, out.size(), f);
     fclose(f);
     PD_REQUIRE(w == out.size(), "pdhip_io_write_obj_mtl: short write to %s", obj_path);
+    return PDHIP_OK;
+}
+
+// Untextured OBJ (`v x y z`, `f a b c`, 1-based): coordinates with 9 significant digits, so that a reader gets the float32 values back.
+// Written to `<path>.<pid>.tmp` and renamed: a reader never sees half a file, two writers never share a temporary.
+extern "C" int pdhip_io_write_obj_plain(const char* obj_path, const float* points, long long P, const int64_t* faces, long long F) {
+    PD_REQUIRE(obj_path && points && faces && P > 0 && F > 0, "pdhip_io_write_obj_plain: null or empty argument");
+    std::string out;
+    out.reserve((size_t)(P * 48 + F * 36 + 64));
+    char buf[256];
+    for (long long i = 0; i < P; ++i) {
+        const int k = snprintf(buf, sizeof buf, "v %.9g %.9g %.9g\n", (double)points[3 * i], (double)points[3 * i + 1], (double)points[3 * i + 2]);
+        out.append(buf, k);
+    }
+    for (long long i = 0; i < F; ++i) {
+        const int k = snprintf(buf, sizeof buf, "f %lld %lld %lld\n", (long long)faces[3 * i] + 1, (long long)faces[3 * i + 1] + 1,
+                               (long long)faces[3 * i + 2] + 1);
+        out.append(buf, k);
+    }
+    const std::string tmp = std::string(obj_path) + "." + std::to_string((long long)getpid()) + ".tmp";
+    FILE* f = fopen(tmp.c_str(), "w");
+    PD_REQUIRE(f != nullptr, "pdhip_io_write_obj_plain: cannot open %s", tmp.c_str());
+    const size_t w = fwrite(out.data(), 1, out.size(), f);
+    fclose(f);
+    if (w != out.size() || rename(tmp.c_str(), obj_path) != 0) {
+        remove(tmp.c_str());
+        PD_REQUIRE(false, "pdhip_io_write_obj_plain: could not write %s", obj_path);
+    }
     return PDHIP_OK;
 }
 

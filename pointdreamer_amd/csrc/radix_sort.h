@@ -1,0 +1,124 @@
+// Radix sort (LSD, 8-bit digits, stable) of 64-bit keys with int32 values, and a one-workgroup scan: shared by the geometry units that
+// sort on the device (uv_atlas.hip: edge keys, packing order, UV entries; surface_recon.hip: cell keys).  Written here because rocPRIM's
+// sort carries scratch on gfx950.  Every kernel has internal linkage: each including unit gets its own copy.
+#pragma once
+#include "common.h"
+
+namespace pdhip {
+namespace {
+
+constexpr int RS_T = 256, RS_ITEMS = 8, RS_TILE = RS_T * RS_ITEMS;
+
+__global__ __launch_bounds__(RS_T) void k_rs_hist(const uint64_t* __restrict__ keys, int n, int shift, int* __restrict__ hist, int nblk) {
+    __shared__ int h[256];
+    const int t = threadIdx.x;
+    h[t] = 0;
+    __syncthreads();
+    const int base = blockIdx.x * RS_TILE;
+    for (int k = 0; k < RS_ITEMS; ++k) {
+        const int i = base + k * RS_T + t;
+        if (i < n) atomicAdd(&h[(int)((keys[i] >> shift) & 255ull)], 1);
+    }
+    __syncthreads();
+    hist[t * nblk + blockIdx.x] = h[t];
+}
+
+// digit offsets (exclusive scan of hist, digit-major) -> stable scatter: element order = (item round, wave, lane)
+__global__ __launch_bounds__(RS_T) void k_rs_scatter(const uint64_t* __restrict__ kin, const int* __restrict__ vin, int n, int shift,
+                                                     const int* __restrict__ offs, int nblk, uint64_t* __restrict__ kout,
+                                                     int* __restrict__ vout) {
+    __shared__ int run[256];
+    __shared__ int wc[RS_T / 64][256];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    run[t] = offs[t * nblk + blockIdx.x];
+    const int base = blockIdx.x * RS_TILE;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (int k = 0; k < RS_ITEMS; ++k) {
+        const int i = base + k * RS_T + t;
+        const bool valid = i < n;
+        const uint64_t key = valid ? kin[i] : 0ull;
+        const int val = valid ? vin[i] : 0;
+        const int d = (int)((key >> shift) & 255ull);
+#pragma unroll
+        for (int w = 0; w < RS_T / 64; ++w) wc[w][t] = 0;
+        __syncthreads();
+        unsigned long long peers = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = (d >> b) & 1;
+            const unsigned long long bal = __ballot(bit);
+            peers &= bit ? bal : ~bal;
+        }
+        const int rank = __popcll(peers & lt);
+        if (valid && rank == 0) wc[wave][d] = __popcll(peers);
+        __syncthreads();
+        int r = run[t];
+#pragma unroll
+        for (int w = 0; w < RS_T / 64; ++w) {
+            const int c = wc[w][t];
+            wc[w][t] = r;
+            r += c;
+        }
+        run[t] = r;
+        __syncthreads();
+        if (valid) {
+            const int pos = wc[wave][d] + rank;
+            kout[pos] = key;
+            vout[pos] = val;
+        }
+        __syncthreads();
+    }
+}
+
+// one workgroup: out[i] = sum of in[0..i] (inclusive) or in[0..i) (exclusive)
+constexpr int SC_T = 1024;
+__global__ __launch_bounds__(SC_T) void k_scan(const int* __restrict__ in, int* __restrict__ out, int n, int exclusive) {
+    __shared__ int part[SC_T];
+    const int t = threadIdx.x;
+    const int chunk = (n + SC_T - 1) / SC_T;
+    const int b = min(n, t * chunk), e = min(n, b + chunk);
+    int s = 0;
+    for (int i = b; i < e; ++i) s += in[i];
+    part[t] = s;
+    __syncthreads();
+    for (int off = 1; off < SC_T; off <<= 1) {                    // Hillis-Steele inclusive scan of the chunk sums
+        const int add = t >= off ? part[t - off] : 0;
+        __syncthreads();
+        part[t] += add;
+        __syncthreads();
+    }
+    int run = part[t] - s;
+    for (int i = b; i < e; ++i) {
+        const int x = in[i];
+        out[i] = exclusive ? run : run + x;
+        run += x;
+    }
+}
+
+struct SortBufs {
+    uint64_t* k[2];
+    int* v[2];
+    int* hist;
+};
+
+static int bits_for(unsigned long long maxkey) {
+    int b = 0;
+    while (b < 64 && (maxkey >> b) != 0ull) ++b;
+    return b;
+}
+
+// sorts keys / values k[0] / v[0] (n elements) by bits [0, bits); returns the index (0 / 1) of the buffer pair holding the result
+static int radix_sort(SortBufs& sb, int n, int bits, hipStream_t s) {
+    const int nblk = cdiv(n, RS_TILE);
+    int cur = 0;
+    for (int shift = 0; shift < bits; shift += 8) {
+        k_rs_hist<<<nblk, RS_T, 0, s>>>(sb.k[cur], n, shift, sb.hist, nblk);
+        k_scan<<<1, SC_T, 0, s>>>(sb.hist, sb.hist + 256 * nblk, 256 * nblk, 1);
+        k_rs_scatter<<<nblk, RS_T, 0, s>>>(sb.k[cur], sb.v[cur], n, shift, sb.hist + 256 * nblk, nblk, sb.k[cur ^ 1], sb.v[cur ^ 1]);
+        cur ^= 1;
+    }
+    return cur;
+}
+
+}  // namespace
+}  // namespace pdhip

@@ -4,10 +4,11 @@ same YAML keys (configs/*.yaml of the reference) and the same output tree as /ro
   <output_path>/<ply stem>_<config stem>/config.yaml, input_pc.ply,
       models/model_normalized.{obj,mtl,png}, others/{k}_{sparse,mask0,mask2,inpainted}.png, others/atlas_wo_background.png
 
-Geometry is UPSTREAM of this build (POCO / SPR are out of scope): the driver uses the reference's own
-drop-in hooks -- `<pc>_untextured_mesh.obj` next to the PLY (demo.py:391-399) and the cached `geo/xatlas_<res>.pth` dict
-(demo.py:428-448).  A mesh without `vt` records is unwrapped on the device (extract_texture_map.xatlas_uvmap_w_face_id, this
-build's own chart layout) and the dict cached; if no mesh is supplied it falls back to the build's stand-in UV sphere fitted to
+Geometry: the reference's drop-in hooks -- `<pc>_untextured_mesh.obj` next to the PLY (demo.py:391-399), the cached
+`geo/<name>_untextured/models/model_normalized.obj` (demo.py:401-406) and the cached `geo/xatlas_<res>.pth` dict (demo.py:428-448)
+-- and, with `geo_from: 'SPR'`, a mesh reconstructed from the cloud on the device (spr.recon_one_shape_SPR; POCO stays out of
+scope).  A mesh without `vt` records is unwrapped on the device (extract_texture_map.xatlas_uvmap_w_face_id, this
+build's own chart layout) and the dict cached; if no mesh is supplied and `geo_from` is not 'SPR' it falls back to the build's stand-in UV sphere fitted to
 the cloud (clearly logged), so that the texturing path can be exercised end to end.
 
   python -m pointdreamer_amd.demo --config configs/nearest.yaml --pc_file dataset/demo_data/clock.ply
@@ -31,6 +32,8 @@ SUPPORTED_KEYS = ('texture_gen_method', 'camera_distribution', 'cam_res', 'view_
                   'point_validation_by_o3d', 'hidden_point_removal_radius', 'refine_point_validation_by_remove_abnormal_depth',
                   'crop_img', 'crop_padding', 'mask_ratio_thresh', 'edge_dilate_kernels', 'optimize_from',
                   'xatlas_texture_res', 'complete_unseen_by', 'output_path')
+# keys of this build's own stages in front of the texturing path (geo_from: 'SPR'): validated like the others, not pipeline arguments
+GEOMETRY_KEYS = ('spr_depth', 'spr_knn')
 
 
 class Cfg(dict):
@@ -70,7 +73,7 @@ def load_config(cfg_file, overrides=None):
     are validated, upstream keys are kept but unused, an unknown key is an error (a typo must not silently fall back)."""
     cfg = Cfg(yaml.safe_load(open(cfg_file)))
     cfg.update(overrides or {})
-    unknown = [k for k in cfg if k not in SUPPORTED_KEYS and k not in UPSTREAM_KEYS]
+    unknown = [k for k in cfg if k not in SUPPORTED_KEYS and k not in UPSTREAM_KEYS and k not in GEOMETRY_KEYS]
     if unknown:
         raise KeyError(f"{cfg_file}: unknown config keys {unknown}")
     if 'texture_gen_method' not in cfg:
@@ -81,6 +84,11 @@ def load_config(cfg_file, overrides=None):
     # arrays of the path are sized by view_num, so a mismatch is an error here instead of an index error later
     if cfg.camera_distribution in ('blender', 'exact_blender') and cfg.view_num != 20:
         raise ValueError(f"camera_distribution={cfg.camera_distribution!r} places 20 cameras: set view_num: 20 (got {cfg.view_num})")
+    from . import spr
+    if 'spr_depth' in cfg and cfg.spr_depth not in spr.DEPTHS:
+        raise ValueError(f"spr_depth={cfg.spr_depth!r}: the dense grid of the SPR geometry supports {spr.DEPTHS} (2^depth cells per axis)")
+    if 'spr_knn' in cfg and not (isinstance(cfg.spr_knn, int) and 3 <= cfg.spr_knn <= 32):
+        raise ValueError(f"spr_knn={cfg.spr_knn!r}: the normals of the SPR geometry take 3 .. 32 neighbours")
     if cfg.optimize_from == 'None':                      # YAML `None` is the string 'None' (demo.py:213 treats both alike)
         cfg['optimize_from'] = None
     return cfg
@@ -166,12 +174,26 @@ def _load_shape(cfg, pc_file, name, device, logger):
     io_utils.save_colored_pc_ply(xyz.cpu().numpy(), rgb.cpu().numpy(), os.path.join(out, 'input_pc.ply'))
     geo_path = pc_file.replace('.ply', '_untextured_mesh.obj')
     xatlas_file = os.path.join(out, 'geo', f'xatlas_{cfg.xatlas_texture_res}.pth')
-    if os.path.exists(geo_path):
-        v, f, vt, ft = io_utils.load_obj_mesh(geo_path, with_uv=True)
+    cached_geo = os.path.join(out, 'geo', f'{name}_untextured', 'models', 'model_normalized.obj')
+    if not os.path.exists(geo_path) and not os.path.exists(cached_geo) and cfg.get('geo_from') == 'SPR':
+        # baselines/spr.py:recon_one_shape_SPR on the normalised cloud (demo.py:411-416), on the device; the mesh goes to the
+        # reference's cache path and is read back from it, so that this run and a resumed one texture the same float32 values
+        from . import spr
+        logger.info('Generating geometry by SPR...')
+        start = time.time()
+        depth = cfg.get('spr_depth', spr.DEFAULT_DEPTH)
+        rv, rf, _, rc = spr.recon_one_shape_SPR(xyz, rgb, depth=depth, knn=cfg.get('spr_knn', spr.DEFAULT_KNN), save_path=cached_geo,
+                                                return_counts=True)
+        logger.info(f'Get Geometry time: {time.time() - start} s by SPR (depth {depth}: {rc["vertices"]} vertices, {rc["faces"]} '
+                    f'faces, {rc["iterations"]} solver iterations; normals oriented by {rc["orientation"]})')
+    if os.path.exists(geo_path) or os.path.exists(cached_geo):
+        supplied = os.path.exists(geo_path)
+        v, f, vt, ft = io_utils.load_obj_mesh(geo_path if supplied else cached_geo, with_uv=True)
         vertices = torch.from_numpy(v).to(device)
         faces = torch.from_numpy(f).to(device)
-        vertices -= (vmax + vmin) / 2.
-        vertices /= (vmax - vmin).max()
+        if supplied:                                     # (the cached mesh was made from the normalised cloud: demo.py:401-406)
+            vertices -= (vmax + vmin) / 2.
+            vertices /= (vmax - vmin).max()
         if os.path.exists(xatlas_file):
             xatlas_dict = {k: (t.to(device) if torch.is_tensor(t) else t) for k, t in torch.load(xatlas_file).items()}
         elif vt is not None:

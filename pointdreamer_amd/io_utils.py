@@ -232,6 +232,17 @@ def load_obj_mesh(path, with_uv=False):
     return v, f, None, None
 
 
+def save_obj_mesh(vertices, faces, path):
+    """Untextured OBJ (`v x y z` / `f a b c`, 1-based) through the native writer: the wire format of the geo/<name>_untextured cache
+    (what POCO / SPR leave, demo.py:401-406).  Coordinates carry 9 significant digits: load_obj_mesh returns the same float32 values."""
+    L = _lib.lib()
+    v = np.ascontiguousarray(np.asarray(vertices)[:, :3], np.float32)
+    f = np.ascontiguousarray(faces, np.int64)
+    os.makedirs(os.path.dirname(os.fspath(path)) or '.', exist_ok=True)
+    _lib.check(L.pdhip_io_write_obj_plain(os.fspath(path).encode(), v.ctypes.data_as(C.c_void_p), len(v), f.ctypes.data_as(C.c_void_p), len(f)),
+               'pdhip_io_write_obj_plain')
+
+
 def savemeshtes2(pointnp_px3, tcoords_px2, facenp_fx3, facetex_fx3, fname):
     """utils_3d.py:27-64, byte-identical text output (native formatter)."""
     L = _lib.lib()

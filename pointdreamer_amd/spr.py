@@ -1,0 +1,130 @@
+"""Geometry from the cloud alone (`geo_from: 'SPR'`): the reference's baselines/spr.py:recon_one_shape_SPR asks pymeshlab (CPU) for
+normals for a point set, screened Poisson reconstruction and quadric decimation.  Here the first two run on the device
+(csrc/surface_recon.hip): oriented normals from k nearest neighbours + visibility votes, a Poisson solve on a dense grid of
+2^depth cells per axis, marching cubes with welded vertices.  The mesh is this project's own (not pymeshlab's): a closed,
+consistently oriented triangle mesh, every component of the iso-surface included.  Decimation is not built."""
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import ptr, stream, check, PdhipError
+
+DEPTHS = (6, 7, 8)
+DEFAULT_DEPTH = 6                    # 7-36 k faces, the size the stages downstream were tuned at (DESIGN, surface reconstruction)
+DEFAULT_KNN = 16
+EYE_RADIUS = 1.6                     # the cameras' distance (demo.py:337), in units of the cloud's largest extent
+
+
+def _points(points, what):
+    if not torch.is_tensor(points) or not points.is_cuda:
+        raise PdhipError(f"{what} needs tensors on the GPU (cuda:N == HIP device); there is no CPU path")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise PdhipError(f"{what}: expected [N,3], got {tuple(points.shape)}")
+    return points.detach().float().contiguous()
+
+
+def estimate_normals(points, k=DEFAULT_KNN, n_eyes=32, return_counts=False, eye_radius=EYE_RADIUS):
+    """points [N,3] (GPU) -> unit normals [N,3] f32 pointing out of the solid.  return_counts: also a dict with the number of points
+    oriented by the eyes that see them (`eyes`), by the majority of their oriented neighbours (`neighbours`), by their nearest oriented
+    neighbour (`nearest`) and left as computed (`unoriented`); they add up to N (synchronises)."""
+    p = _points(points, 'estimate_normals')
+    L = _lib.lib()
+    N = p.shape[0]
+    nbytes = L.pdhip_estimate_normals_ws_bytes(N, int(k), int(n_eyes))
+    ws = torch.empty((max(1, nbytes),), dtype=torch.uint8, device=p.device)
+    normals = torch.empty((N, 3), dtype=torch.float32, device=p.device)
+    counts = torch.zeros((4,), dtype=torch.int32, device=p.device)
+    check(L.pdhip_estimate_normals(ptr(p), N, int(k), int(n_eyes), float(eye_radius), ptr(normals), ptr(counts), ptr(ws), stream()),
+          'pdhip_estimate_normals')
+    if return_counts:
+        c = counts.cpu().tolist()
+        return normals, dict(eyes=c[0], neighbours=c[1], nearest=c[2], unoriented=c[3])
+    return normals
+
+
+def capacities(depth):
+    """Default (vertex, face) capacities of poisson_reconstruct: a surface of 6 (2^depth)^2 cells' area -- four times a sphere that
+    fills the grid's inner 3/4.  A mesh that needs more is reconstructed again with the sizes the first call reported."""
+    g2 = (1 << int(depth)) ** 2
+    return 8 * g2, 16 * g2
+
+
+def poisson_reconstruct(points, normals, depth=DEFAULT_DEPTH, return_counts=False, colors=None, capacity=None):
+    """points, normals [N,3] (GPU; normals point outwards) -> (vertices f32 [Vn,3], faces int64 [F,3]).  colors [N,3]: a third result,
+    the colour of the nearest cloud point per vertex.  return_counts: a last result, dict(vertices, faces, iterations, h, origin,
+    iso, residual, splat_radius).  capacity: (vertices, faces) to allocate instead of capacities(depth); too small is a PdhipError
+    that names the sizes needed."""
+    if int(depth) not in DEPTHS:
+        raise ValueError(f"depth={depth}: the dense grid supports depth 6, 7 or 8 (2^depth cells per axis); the reference's default 12 "
+                         "is an octree depth")
+    p = _points(points, 'poisson_reconstruct')
+    n = _points(normals, 'poisson_reconstruct')
+    if n.shape != p.shape:
+        raise PdhipError(f"poisson_reconstruct: points {tuple(p.shape)} and normals {tuple(n.shape)} differ")
+    c = None
+    if colors is not None:
+        c = _points(colors, 'poisson_reconstruct')
+        if c.shape != p.shape:
+            raise PdhipError(f"poisson_reconstruct: points {tuple(p.shape)} and colors {tuple(c.shape)} differ")
+    N, dev = p.shape[0], p.device
+    L = _lib.lib()
+    ws = torch.empty((max(1, L.pdhip_surface_recon_ws_bytes(N, int(depth))),), dtype=torch.uint8, device=dev)
+    counts = torch.zeros((4,), dtype=torch.int32, device=dev)
+    info = torch.zeros((8,), dtype=torch.float32, device=dev)
+    vcap, fcap = capacity if capacity is not None else capacities(depth)
+    for attempt in (0, 1):
+        verts = torch.empty((int(vcap), 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((int(fcap), 3), dtype=torch.int64, device=dev)
+        vcol = torch.empty((int(vcap), 3), dtype=torch.float32, device=dev) if c is not None else None
+        rc = L.pdhip_surface_recon(ptr(p), ptr(n), ptr(c, allow_none=True), N, int(depth), ptr(verts), int(vcap), ptr(faces), int(fcap),
+                                   ptr(vcol, allow_none=True), ptr(counts), ptr(info), ptr(ws), stream())
+        nv, nf, iters, _ = counts.cpu().tolist()
+        if rc != 0 and attempt == 0 and capacity is None and (nv > vcap or nf > fcap):
+            vcap, fcap = max(nv, vcap), max(nf, fcap)       # the call reported the sizes: once more, exactly
+            continue
+        check(rc, 'pdhip_surface_recon')
+        break
+    out = [verts[:nv].contiguous(), faces[:nf].contiguous()]
+    if c is not None:
+        out.append(vcol[:nv].contiguous())
+    if return_counts:
+        i = info.cpu().tolist()
+        out.append(dict(vertices=nv, faces=nf, iterations=iters, h=i[0], origin=tuple(i[1:4]), iso=i[4], residual=i[5], splat_radius=i[6],
+                        nodes=int(i[7])))
+    return tuple(out)
+
+
+def _to_device(a, name):
+    if torch.is_tensor(a):
+        if not a.is_cuda:
+            raise PdhipError(f"recon_one_shape_SPR: {name} is a CPU tensor; pass a GPU tensor or a numpy array (there is no CPU path)")
+        return a
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32))).to(torch.device('cuda', torch.cuda.current_device()))
+
+
+def recon_one_shape_SPR(coords, colors, gt_normals=None, save_path=None, depth=DEFAULT_DEPTH, simplify_face_num=None, *, knn=DEFAULT_KNN,
+                        return_counts=False):
+    """baselines/spr.py:16-75 with its argument order and 3-tuple (vertices [Vn,3], faces [F,3], vertex_colors [Vn,3]), as GPU
+    tensors.  coords / colors / gt_normals: GPU tensors or numpy arrays (numpy goes to the current device).  gt_normals None: the
+    normals are estimated.  save_path: the mesh is written as an OBJ.  depth: 6, 7 or 8 (a dense grid of 2^depth cells per axis, not
+    the reference's octree depth 12).  simplify_face_num: quadric decimation is not built -- anything but None is refused."""
+    if simplify_face_num is not None:
+        raise NotImplementedError("recon_one_shape_SPR: mesh decimation (simplify_face_num) is not built; pass None and choose the face "
+                                  "count through depth (6, 7, 8)")
+    if int(depth) not in DEPTHS:
+        raise ValueError(f"depth={depth}: the dense grid supports depth 6, 7 or 8 (2^depth cells per axis); the reference's default 12 "
+                         "is an octree depth")
+    xyz = _to_device(coords, 'coords')
+    rgb = _to_device(colors, 'colors')
+    counts = None
+    if gt_normals is None:
+        normals, counts = estimate_normals(xyz, k=knn, return_counts=True)
+    else:
+        normals = _to_device(gt_normals, 'gt_normals')
+    verts, faces, vcol, rc = poisson_reconstruct(xyz, normals, depth=depth, colors=rgb, return_counts=True)
+    if save_path is not None:
+        from . import io_utils
+        io_utils.save_obj_mesh(verts.cpu().numpy(), faces.cpu().numpy(), save_path)
+    if return_counts:
+        return verts, faces, vcol, dict(orientation=counts, **rc)
+    return verts, faces, vcol

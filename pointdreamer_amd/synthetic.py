@@ -164,3 +164,112 @@ def icosphere(n, radius=0.5, noise=0.0, seed=0):
     rng = np.random.default_rng(seed)
     v = v * radius * (1.0 + noise * rng.standard_normal((len(v), 1)))
     return v.astype(F32), f.astype(np.int64)
+
+
+# ---- analytic test solids for the surface reconstruction (spr.py): signed distance (negative inside), outward unit normal, a smooth
+# colour field, an area-uniform seeded point sampler.  All fit the box [-0.5, 0.5]^3.
+def solid_color(x):
+    """Smooth colour field in [0.05, 0.95]^3 at positions x [n,3]."""
+    x = np.asarray(x, np.float64)
+    cols = []
+    for c in range(3):
+        ph = 2.0 * c
+        cols.append(0.5 + 0.45 * np.sin(3 * np.pi * x[:, 0] + ph) * np.cos(2 * np.pi * x[:, 1] + 0.5 * ph) * np.cos(2 * np.pi * x[:, 2] - ph))
+    return np.stack(cols, 1)
+
+
+def _seg_dist(p, a, b):
+    pa, ba = p - a, b - a
+    h = np.clip((pa @ ba) / (ba @ ba), 0.0, 1.0)
+    return np.linalg.norm(pa - h[:, None] * ba, axis=1)
+
+
+class Solid:
+    """name, sdf(x) (exact distances, except 'ellipsoid': distance to the foot point of a Newton projection, exact to O(d^2 * curvature)),
+    components, euler (per component), volume (closed form where there is one, else None: see volume())."""
+    NAMES = ('sphere', 'ellipsoid', 'torus', 'rounded_box', 'two_spheres', 'cup')
+
+    def __init__(self, name):
+        if name not in self.NAMES:
+            raise ValueError(f"unknown solid {name!r}: one of {self.NAMES}")
+        self.name = name
+        self.components, self.euler = (2, 2) if name == 'two_spheres' else (1, 0 if name == 'torus' else 2)
+        self.ell = np.array([0.5, 0.35, 0.25])
+        self.volume_exact = {'sphere': 4 / 3 * np.pi * 0.5 ** 3, 'ellipsoid': 4 / 3 * np.pi * float(np.prod(self.ell)),
+                             'torus': 2 * np.pi ** 2 * 0.35 * 0.15 ** 2, 'two_spheres': 2 * 4 / 3 * np.pi * 0.2 ** 3}.get(name)
+
+    def sdf(self, x):
+        x = np.asarray(x, np.float64)
+        n = self.name
+        if n == 'sphere':
+            return np.linalg.norm(x, axis=1) - 0.5
+        if n == 'torus':                                       # major 0.35, minor 0.15, axis y
+            q = np.stack([np.hypot(x[:, 0], x[:, 2]) - 0.35, x[:, 1]], 1)
+            return np.linalg.norm(q, axis=1) - 0.15
+        if n == 'rounded_box':                                 # half extents (0.5, 0.35, 0.3), corner radius 0.1
+            q = np.abs(x) - (np.array([0.5, 0.35, 0.3]) - 0.1)
+            return np.linalg.norm(np.maximum(q, 0.0), axis=1) + np.minimum(q.max(1), 0.0) - 0.1
+        if n == 'two_spheres':                                 # radius 0.2, centres (+-0.3, 0, 0): 0.2 apart
+            c = np.array([0.3, 0.0, 0.0])
+            return np.minimum(np.linalg.norm(x - c, axis=1), np.linalg.norm(x + c, axis=1)) - 0.2
+        if n == 'cup':                                         # a U profile of wall radius 0.07 revolved about y: open at the top
+            p = np.stack([np.hypot(x[:, 0], x[:, 2]), x[:, 1]], 1)
+            a, b, c = np.array([0.0, -0.4]), np.array([0.4, -0.4]), np.array([0.4, 0.43])
+            return np.minimum(_seg_dist(p, a, b), _seg_dist(p, b, c)) - 0.07
+        # ellipsoid: foot point by Newton steps on the Lagrange multiplier of the closest-point problem
+        e2 = self.ell ** 2
+        t = np.zeros(len(x))
+        for _ in range(30):
+            d = e2[None] / (t[:, None] + e2[None])
+            g = ((d * x) ** 2 / e2[None]).sum(1) - 1.0
+            dg = (-2.0 * (d * x) ** 2 / e2[None] / (t[:, None] + e2[None])).sum(1)
+            t = np.maximum(t - g / np.where(dg == 0, -1.0, dg), -e2.min() * 0.999)
+        foot = e2[None] / (t[:, None] + e2[None]) * x
+        inside = ((x / self.ell) ** 2).sum(1) < 1.0
+        return np.linalg.norm(x - foot, axis=1) * np.where(inside, -1.0, 1.0)
+
+    def normal(self, x, eps=1e-5):
+        """Outward unit normal = the normalised gradient of sdf (central differences)."""
+        x = np.asarray(x, np.float64)
+        g = np.stack([self.sdf(x + eps * np.eye(3)[a]) - self.sdf(x - eps * np.eye(3)[a]) for a in range(3)], 1)
+        return g / np.maximum(np.linalg.norm(g, axis=1, keepdims=True), 1e-300)
+
+    def color(self, x):
+        return solid_color(x)
+
+    def volume(self, n=160):
+        """Closed form, or the midpoint rule on an n^3 grid over [-0.55, 0.55]^3 with a linear ramp across the surface."""
+        if self.volume_exact is not None:
+            return self.volume_exact
+        h = 1.1 / n
+        c = (np.arange(n) + 0.5) * h - 0.55
+        tot = 0.0
+        for z in c:
+            X, Y = np.meshgrid(c, c, indexing='ij')
+            d = self.sdf(np.stack([X.ravel(), Y.ravel(), np.full(X.size, z)], 1))
+            tot += np.clip(0.5 - d / h, 0.0, 1.0).sum()
+        return tot * h ** 3
+
+    def sample(self, n, seed=0, noise=0.0, shell=0.01):
+        """n points area-uniform on the surface (uniform draws in a thin shell round it, projected along the normal), optional Gaussian
+        noise of standard deviation `noise` along the normal -> (xyz f32 [n,3], rgb f32 [n,3], outward normals f32 [n,3])."""
+        rng = np.random.default_rng(seed)
+        got = []
+        have = 0
+        while have < n:
+            x = rng.uniform(-0.6, 0.6, (400000, 3))
+            x = x[np.abs(self.sdf(x)) < shell]
+            for _ in range(3):
+                x = x - self.sdf(x)[:, None] * self.normal(x)
+            got.append(x)
+            have += len(x)
+        x = np.concatenate(got)[:n]
+        nrm = self.normal(x)
+        rgb = self.color(x)
+        if noise > 0:
+            x = x + noise * rng.standard_normal((n, 1)) * nrm
+        return x.astype(F32), np.clip(rgb, 0, 1).astype(F32), nrm.astype(F32)
+
+
+def solid(name):
+    return Solid(name)
