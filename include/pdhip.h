@@ -354,6 +354,18 @@ int pdhip_gn_silu_conv3x3_nhwc_f16(const void* x, const float* gamma, const floa
 int pdhip_debug_conv3x3_apply(const void* x, const float* table /*[N][Cin/8][16]*/, const void* w_packed, const float* bias, const void* residual,
                               void* y, int N, int H, int W, int Cin, int Cout, int Cout_pad, const void* zero_page, void* stream);   /* tuning hook */
 int pdhip_debug_set_fold_skip(int on);   /* 1 (default): in the small-M layers a channel-changing ResBlock's skip 1x1 conv (unet.py:206-209, 255) is appended to conv2's K loop (k_conv_sk<10>: out = W2 im2col(h) + Wskip x + (b2 + bskip), one launch and one rounding); 0: its own launch + a residual read; returns the previous value */
+int pdhip_debug_set_up_phase(int mode);   /* in_layers conv of an up-ResBlock, conv3x3(nearest_x2(h)) (unet.py:190-192, 236-242), as four 2x2 phase convs over the half-resolution h with the coinciding taps summed in the weights (4/9 of the MACs): 0 never / 1 (default) where it measured faster / 2 every eligible layer; returns the previous value */
+/* phase weights of that form: w_packed [Cout_pad][9*Cin] f16 -> w_phase [4][Cout_pad][4*Cin] f16 (phase = 2 py + px of the output pixel, k = (2 ty + tx) Cin + c over the
+ * 2x2 source window); each entry the f32 sum in (ky, kx) order of the taps that land on one source pixel, rounded once to f16 */
+int pdhip_pack_conv_up2_phase_f16(const void* w_packed, int Cin, int Cout_pad, void* w_phase, void* stream);
+/* y [N,2H,2W,Cout] = conv3x3(nearest_x2(x [N,H,W,Cin]), pad 1) + bias through the four phase convs.  Cin % 64 == 0, Cout % 8 == 0, Cout_pad % 128 == 0,
+ * gn_part (may be NULL; written only when H*W % 256 == 0): GroupNorm octet partials [N][4*H*W/256][Cout/8][2] */
+int pdhip_conv3x3_up2_phase_nhwc_f16(const void* x, const void* w_phase, const float* bias, void* y, int N, int H, int W, int Cin, int Cout,
+                                     int Cout_pad, const void* zero_page, float* gn_part, void* stream);
+/* the same layer on the 9-tap halo-resident kernel, which reads source pixel (y >> 1, x >> 1) (the route the phase conv replaces; only layers that
+ * kernel takes unsplit) */
+int pdhip_conv3x3_up2_halo_nhwc_f16(const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W, int Cin, int Cout,
+                                    int Cout_pad, const void* zero_page, void* stream);
 int pdhip_debug_set_fold_resample(int on);   /* 1 (default): the resampled x branch of up / down ResBlocks is folded into its consumers; 0: k_resample passes */
 int pdhip_debug_set_fold_finalize(int max_batch);   /* largest UNet batch at which GroupNorm-apply reduces the conv epilogues' statistics partials itself (no k_gn_finalize_oct launch); default 8, 0 = never */
 int pdhip_debug_set_fold_finalize_chunks(int chunks);   /* above that batch the in-kernel statistics are kept for tensors whose producers left at most this many chunks per image (default 16; 0 = batch rule only); returns the previous value */

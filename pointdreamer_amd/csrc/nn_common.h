@@ -36,6 +36,12 @@ int conv_igemm(const half_t* X, const half_t* Wt, const float* bias, const half_
                const float* apply_table = nullptr,          // input = silu(A x + B) per gn_table (layers the halo kernel takes only)
                int res_up = 0,                              // residual = half-resolution tensor read with nearest x2 (unsplit halo layers only)
                int in_up = 0);                              // X = half-resolution tensor, input = its nearest x2 (halo layers only)
+// ---- conv3x3(nearest_x2(X)) as four 2x2 phase convs over the half-resolution X [N,H,W,Cin] (nn_gemm.hip, k_conv_igemm<4>): Y [N,2H,2W,Cout].
+// Wph [4][Cout_pad][4 Cin] from conv_up2_phase_pack(w9 = the packed [Cout_pad][9 Cin] weights); gn_part: octet partials, *gn_fused chunks per image
+bool conv_up2_phase_eligible(int N, int H, int W, int Cin, int Cout, int Cout_pad);
+int conv_up2_phase_pack(const half_t* w9, int Cin, int Cout_pad, half_t* dst, hipStream_t s);
+int conv_up2_phase(const half_t* X, const half_t* Wph, const float* bias, half_t* Y, int N, int H, int W, int Cin, int Cout, int Cout_pad,
+                   const half_t* zero_page, hipStream_t s, float* gn_part, int* gn_fused);
 // ---- small-M convolution with in-launch split-K combine (nn_conv_sk.hip).  ws: [0, 4096) ticket words (zero at allocation,
 // self-resetting), slabs behind them.  conv_sk_plan decides whether / how a layer runs there (bm == 0: not this kernel's layer).
 struct SkPlan { int bm, bn, splits, tile_id; };

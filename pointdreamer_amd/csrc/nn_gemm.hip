@@ -45,6 +45,11 @@ __device__ __forceinline__ int swz(int row) {
 
 // Tile geometry: WM x WN waves, each wave owns TM x 4 accumulator tiles of 16x16 (wave tile TM*16 rows x 64 columns).
 //   <2,2,4> 128x128 / 4 waves      <4,2,4> 256x128 / 8 waves      <2,4,8> 256x256 / 8 waves (wave tile 128x64)
+// TAPS == 4: the 3x3 conv of a nearest-x2 up-sampled image as four 2x2 "phase" convs over the HALF-resolution image X [N,H,W,Cin]
+// (conv_up2_phase below).  Output pixel (2y + py, 2x + px) only sees source pixels (y + ty - 1 + py, x + tx - 1 + px), ty, tx in {0, 1},
+// with the 3x3 taps that land on one source pixel summed in the weights: Wt [4 phases][Cout_pad][4 Cin], phase = 2 py + px, k = (2 ty + tx) Cin + c.
+// The phase rides in the tile id (m-tile, phase, n-tile: the four phases of a pixel tile share its activations through L2), the epilogue
+// scatters row m to its pixel of Y [N,2H,2W,Cout] and the GroupNorm partials get 4 chunks (one per phase) per pixel tile.
 template <int TAPS, int BKT, int NSTAGE, int WM, int WN, int TM>
 __global__ __launch_bounds__(WM * WN * 64) void k_conv_igemm(const half_t* __restrict__ X, const half_t* __restrict__ Wt,
                                                     const float* __restrict__ bias, const half_t* __restrict__ residual,
@@ -80,9 +85,12 @@ __global__ __launch_bounds__(WM * WN * 64) void k_conv_igemm(const half_t* __res
         const int b = blockIdx.x, q = total_tiles >> 3, r = total_tiles & 7, xcd = b & 7, i = b >> 3;
         tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
     }
-    const int m0 = (tile / n_tiles) * BMT, n0 = (tile % n_tiles) * BNT;
+    const int mt = tile / n_tiles, n0 = (tile - mt * n_tiles) * BNT;
+    const int phase = (TAPS == 4) ? (mt & 3) : 0;                  // (uniform)
+    const int m0 = ((TAPS == 4) ? (mt >> 2) : mt) * BMT;
     const long long M = (long long)N * H * W;
     const int K = TAPS * Cin;
+    if (TAPS == 4) Wt += (size_t)phase * ((size_t)n_tiles * BNT) * K;
     const int kc = Cin / BKT;                // K-steps per tap
     const int KI = TAPS * kc;
 
@@ -117,7 +125,8 @@ __global__ __launch_bounds__(WM * WN * 64) void k_conv_igemm(const half_t* __res
         bp[i] = Wt + (size_t)(n0 + r) * K + (lpos ^ swz<BKT>(r)) * 8;
     }
     auto set_tap = [&](int tap) {
-        const int dy = (TAPS == 1) ? 0 : tap / 3 - 1, dx = (TAPS == 1) ? 0 : tap - (tap / 3) * 3 - 1;
+        const int dy = (TAPS == 1) ? 0 : (TAPS == 4) ? (tap >> 1) - 1 + (phase >> 1) : tap / 3 - 1;
+        const int dx = (TAPS == 1) ? 0 : (TAPS == 4) ? (tap & 1) - 1 + (phase & 1) : tap - (tap / 3) * 3 - 1;
 #pragma unroll
         for (int i = 0; i < LPO; ++i) {
             const int yy = py[i] + dy, xx = pxx[i] + dx;
@@ -428,7 +437,11 @@ __global__ __launch_bounds__(WM * WN * 64) void k_conv_igemm(const half_t* __res
         const long long m = (long long)m0 + row;
         if (m < M && n0 + col8 < Cout) {
             half8 v = *reinterpret_cast<const half8*>(&Cs[row * CS_LD + col8]);
-            const size_t o = (size_t)m * Cout + n0 + col8;
+            size_t o = (size_t)m * Cout + n0 + col8;
+            if (TAPS == 4) {                               // half-resolution pixel (img, y, x) -> pixel (2y + py, 2x + px) of the x2 image
+                const int hw = H * W, img = (int)(m / hw), rem = (int)(m - (long long)img * hw), y = rem / W, x = rem - y * W;
+                o = ((((size_t)img * 2 * H + 2 * y + (phase >> 1)) * 2 * W) + 2 * x + (phase & 1)) * Cout + n0 + col8;
+            }
             if (residual != nullptr) {
                 const half8 rv = *reinterpret_cast<const half8*>(residual + o);
 #pragma unroll
@@ -456,8 +469,8 @@ __global__ __launch_bounds__(WM * WN * 64) void k_conv_igemm(const half_t* __res
         if (tid < CT && n0 + tid * 8 < Cout) {
             float s1 = 0.f, q1 = 0.f;
             for (int r = 0; r < RPP; ++r) { s1 += red[(r * CT + tid) * 2]; q1 += red[(r * CT + tid) * 2 + 1]; }
-            const int hw = H * W, chunks = hw / BMT;
-            const int img = m0 / hw, chunk = (m0 - img * hw) / BMT;
+            const int hw = H * W, chunks = (TAPS == 4 ? 4 : 1) * (hw / BMT);
+            const int img = m0 / hw, chunk = (TAPS == 4) ? ((m0 - img * hw) / BMT) * 4 + phase : (m0 - img * hw) / BMT;
             float* dst = gn_part + (((size_t)img * chunks + chunk) * (Cout >> 3) + (n0 >> 3) + tid) * 2;
             dst[0] = s1; dst[1] = q1;
         }
@@ -706,6 +719,57 @@ int conv_igemm(const half_t* X, const half_t* Wt, const float* bias, const half_
     if (splits > 1) {
         return splitk_reduce(partial, splits, M, Cout, bias, residual, Y, fuse_sk ? gn_part : nullptr, H * W, s);
     }
+    PD_LAUNCH_CHECK();
+    return PDHIP_OK;
+}
+
+// ---- 3x3 conv of a nearest-x2 up-sampled image as four 2x2 phase convs over the half-resolution image: 4/9 of the MACs.
+// w9 [Cout_pad][9 Cin] (the engine's packed f16 weights) -> dst [4][Cout_pad][4 Cin]: each entry is the f32 sum, in (ky, kx) order, of the
+// 1, 2 or 4 taps that land on the source pixel, rounded once to f16.  Rows: py 0 -> {ky 0}, {1, 2}; py 1 -> {0, 1}, {2}; columns alike.
+__global__ void k_pack_up2_phase(const half_t* __restrict__ w9, int Cout_pad, int Cin, half_t* __restrict__ dst) {
+    const long long total = 16LL * Cout_pad * Cin;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % Cin), tap = (int)((i / Cin) & 3);
+        const int o = (int)((i / (4LL * Cin)) % Cout_pad), ph = (int)(i / (4LL * Cin * Cout_pad));
+        const int py = ph >> 1, px = ph & 1, ty = tap >> 1, tx = tap & 1;
+        const int ky0 = py == 0 ? ty : 2 * ty, ky1 = py == 0 ? 2 * ty : ty + 1;      // inclusive tap ranges
+        const int kx0 = px == 0 ? tx : 2 * tx, kx1 = px == 0 ? 2 * tx : tx + 1;
+        float sum = 0.f;
+        for (int ky = ky0; ky <= ky1; ++ky)
+            for (int kx = kx0; kx <= kx1; ++kx) sum += (float)w9[(size_t)o * 9 * Cin + (size_t)(ky * 3 + kx) * Cin + c];
+        dst[i] = (half_t)sum;
+    }
+}
+int conv_up2_phase_pack(const half_t* w9, int Cin, int Cout_pad, half_t* dst, hipStream_t s) {
+    const long long total = 16LL * Cout_pad * Cin;
+    k_pack_up2_phase<<<(int)std::min<long long>((total + 255) / 256, 4096), 256, 0, s>>>(w9, Cout_pad, Cin, dst);
+    PD_LAUNCH_CHECK();
+    return PDHIP_OK;
+}
+// layers the phase kernel takes (H, W: the HALF-resolution input): K-step 64; the GroupNorm partials also need 256-row pixel tiles inside one image
+bool conv_up2_phase_eligible(int N, int H, int W, int Cin, int Cout, int Cout_pad) {
+    return N >= 1 && H >= 1 && W >= 1 && Cin % 64 == 0 && Cout % 8 == 0 && Cout_pad % 128 == 0 && Cout_pad >= Cout &&
+           ((long long)N * H * W + 255) / 256 * 4 * (Cout_pad / 128) < (1LL << 30);
+}
+int conv_up2_phase(const half_t* X, const half_t* Wph, const float* bias, half_t* Y, int N, int H, int W, int Cin, int Cout, int Cout_pad,
+                   const half_t* zero_page, hipStream_t s, float* gn_part, int* gn_fused) {
+    PD_REQUIRE(conv_up2_phase_eligible(N, H, W, Cin, Cout, Cout_pad),
+               "conv_up2_phase: need Cin %% 64 == 0, Cout %% 8 == 0, padded Cout %% 128 == 0 (Cin=%d Cout=%d pad=%d)", Cin, Cout, Cout_pad);
+    if (((long long)H * W) % 256 != 0) gn_part = nullptr;      // a pixel tile would straddle two images: no fused statistics
+    // tile geometry (tuning hook: 8 / 16 force one): 256x256 where the padded Cout allows it, else 256x128 / 4 waves; both run the
+    // register-pipelined schedule
+    int geo = (g_force_wmw == 8 || g_force_wmw == 16) ? g_force_wmw : 8;
+    if (Cout_pad % 256 != 0) geo = 16;
+    const int bnt = geo == 8 ? 256 : 128;
+    const long long M = (long long)N * H * W;
+    const int m_tiles = (int)((M + 255) / 256), n_tiles = Cout_pad / bnt, total = m_tiles * 4 * n_tiles;
+    if (gn_fused) *gn_fused = gn_part != nullptr ? 4 * (int)(((long long)H * W) / 256) : 0;
+    const size_t smem = std::max<size_t>((size_t)2 * (256 + bnt) * 64 * 2, (size_t)256 * (bnt + 8) * 2);
+    dim3 grid(total, 1);
+    int rc;
+    if (geo == 8) rc = launch_conv<4, 64, 12, 2, 4, 8>(grid, smem, s, X, Wph, bias, nullptr, Y, N, H, W, Cin, Cout, n_tiles, total, zero_page, 1, nullptr, gn_part, nullptr, Cin);
+    else rc = launch_conv<4, 64, 12, 2, 2, 8>(grid, smem, s, X, Wph, bias, nullptr, Y, N, H, W, Cin, Cout, n_tiles, total, zero_page, 1, nullptr, gn_part, nullptr, Cin);
+    if (rc) return rc;
     PD_LAUNCH_CHECK();
     return PDHIP_OK;
 }

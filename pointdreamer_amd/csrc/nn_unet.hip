@@ -18,7 +18,7 @@ using namespace pdnn;
 namespace {
 
 struct ConvW { half_t* w = nullptr; float* b = nullptr; int cin = 0, cout = 0, cout_pad = 0, taps = 0; bool have_w = false, have_b = false;
-               half_t* wf = nullptr; };   // wf: fragment-major copy for the row-resident kernel (nn_conv_rr.hip), the 3x3 convs of the <= 64^2 levels; packed at load time
+               half_t* wf = nullptr; half_t* wph = nullptr; };   // wf: fragment-major copy for the row-resident kernel (nn_conv_rr.hip), the 3x3 convs of the <= 64^2 levels; packed at load time   // wph: phase weights [4][cout_pad][4 cin] of an up-ResBlock's in_layers conv (conv_up2_phase), packed at load time
 struct NormW { float* g = nullptr; float* b = nullptr; int c = 0; bool have_g = false, have_b = false; };
 struct ResB { std::string name; int cin, cout, mode; NormW n1, n2; ConvW c1, c2, skip; long long emb_off; bool has_skip; bool have_ew = false, have_eb = false;
               half_t* c2s_w = nullptr; float* c2s_b = nullptr; bool c2s_ready = false; half_t* c2s_wf = nullptr; int hw = 0; };   // hw: resolution the block's convs run at   // conv2 with the skip 1x1 appended to its K loop (conv_sk_skip), built by pdhip_unet_load_tensor once its four sources are loaded
@@ -58,6 +58,10 @@ namespace pdnn { thread_local int g_fold_finalize = 8; thread_local int g_fold_f
 // at least g_fuse_skip_min_tiles pixel tiles (default 1: measured a gain at every batch) runs GroupNorm-apply and the skip 1x1 as ONE
 // pass over its input (k_gn_skip), 2 = always
 namespace pdnn { thread_local int g_fuse_skip = 1; thread_local int g_fuse_skip_min_tiles = 1; }
+// tuning / test hook (pdhip_debug_set_up_phase): the in_layers conv of an up-ResBlock, conv3x3(nearest_x2(h)), as four 2x2 phase convs over the
+// half-resolution h with the coinciding taps summed in the weights (4/9 of the MACs; k_conv_igemm<4>).  0 = never, 1 (default) = where it
+// measured faster than the 9-tap route (up_phase_routes below), 2 = every eligible layer.  Independent of g_fold_resample.
+namespace pdnn { thread_local int g_up_phase = 1; }
 namespace {
 struct Prof { std::vector<hipEvent_t> ev; std::vector<uint8_t> cls; size_t used = 0; double flops[2] = {0, 0}; bool on = false;
               int period = 1; long long forwards = 0; bool armed = false; };   // cls 0: halo 3x3 conv, 1: attention
@@ -301,6 +305,28 @@ int run_rr_gn_conv(Ctx& c, const Act& x, const NormW& n, const float* film, long
     return PDHIP_OK;
 }
 
+// the up-ResBlock in_layers conv on the phase kernel?  (H, W: the half-resolution input)
+bool up_phase_routes(const Ctx& c, const ResB& rb, int H, int W) {
+    if (c.dry || g_up_phase == 0 || rb.mode != 2 || rb.c1.wph == nullptr || (H * W) % 256 != 0 ||
+        !conv_up2_phase_eligible(c.N, H, W, rb.c1.cin, rb.c1.cout, rb.c1.cout_pad)) return false;
+    if (g_up_phase == 2) return true;
+    // automatic, by measurement (profiles/up_phase_layers.txt, batch 1 ... 32 x the five up blocks): from 128 tiles (4 phases x 256-pixel tiles x
+    // channel tiles) on the phase conv beat the 9-tap route in every case (1.19x at 128 tiles ... 1.94x), at 64 tiles and below it lost (0.23 ... 0.92x:
+    // 256 x 256 tiles on a quarter of the CUs)
+    const long long tiles = (long long)c.N * H * W / 256 * 4 * (rb.c1.cout_pad / (rb.c1.cout_pad % 256 == 0 ? 256 : 128));
+    return tiles >= 128;
+}
+int run_conv_up_phase(Ctx& c, const Act& x, const ConvW& w, Act* out) {      // (not booked by the --full profile hook: 4 Cin MACs per output, not 9 Cin)
+    *out = Act{nullptr, w.cout, 2 * x.H, 2 * x.W};
+    out->p = arena_take(c.u, (size_t)c.N * 4 * x.H * x.W * w.cout);
+    float* part = reinterpret_cast<float*>(arena_take(c.u, (size_t)c.N * ((4 * x.H * x.W + 15) / 16) * (w.cout / 8) * 2 * 2));
+    PD_REQUIRE(w.have_w && w.have_b, "unet: conv weights not loaded");
+    int fused = 0;
+    PD_TRY(conv_up2_phase(x.p, w.wph, w.b, out->p, c.N, x.H, x.W, w.cin, w.cout, w.cout_pad, c.u->zero_page, c.s, part, &fused));
+    if (fused) { out->gn_part = part; out->gn_chunks = fused; out->Ca = w.cout; }
+    return PDHIP_OK;
+}
+
 int run_res(Ctx& c, const Act& x, ResB& rb, Act* out) {
     Act h0, h1, h2, xr = x, sk;
     const float* film = c.dry ? nullptr : c.film_base + rb.emb_off;
@@ -342,6 +368,9 @@ int run_res(Ctx& c, const Act& x, ResB& rb, Act* out) {
         PD_TRY(run_gn_conv(c, x, rb.n1, nullptr, 0, rb.c1, nullptr, &h1));
     } else if (rb.mode == 0 && rr_gn_ok(c, x, rb.c1, x.H, x.W)) {
         PD_TRY(run_rr_gn_conv(c, x, rb.n1, nullptr, 0, rb.c1, nullptr, 0, &h1));
+    } else if (x.p2 == nullptr && !rb.has_skip && up_phase_routes(c, rb, x.H, x.W)) {
+        PD_TRY(run_gn(c, x, rb.n1, nullptr, 0, 1, 0, &h0));                  // GroupNorm at half resolution, the x2 lives in the weights
+        PD_TRY(run_conv_up_phase(c, h0, rb.c1, &h1));
     } else if (fold_in_up) {
         PD_TRY(run_gn(c, x, rb.n1, nullptr, 0, 1, 0, &h0));
         PD_TRY(run_conv(c, h0, rb.c1, nullptr, &h1, true, nullptr, 0, 1));
@@ -578,6 +607,9 @@ extern "C" int pdhip_unet_create(int image_size, int model_channels, int num_res
             chk(dalloc(u, &rb.c2s_b, (size_t)rb.cout));
         }
         // fragment-major copies for the row-resident kernel (small-batch route of the <= 64^2 levels; +~1 GB at the 256^2 config: 288 GB HBM)
+        // phase weights of an up block's in_layers conv, 16 Cin Cout_pad f16 (50 MB over the four up blocks whose half-resolution image holds whole 256-pixel tiles)
+        if (rb.mode == 2 && ((rb.hw / 2) * (rb.hw / 2)) % 256 == 0 && conv_up2_phase_eligible(1, rb.hw / 2, rb.hw / 2, rb.cin, rb.cout, rb.c1.cout_pad))
+            chk(dalloc(u, &rb.c1.wph, (size_t)16 * rb.c1.cout_pad * rb.cin));
         if (rb.hw <= 64 && rb.cin % 128 == 0 && rb.cout % 128 == 0) {
             chk(dalloc(u, &rb.c1.wf, conv_rr_weight_halfs(rb.cin, 9, 0, rb.cout)));
             chk(dalloc(u, &rb.c2.wf, conv_rr_weight_halfs(rb.cout, 9, 0, rb.cout)));
@@ -702,6 +734,7 @@ extern "C" int pdhip_unet_load_tensor(pdhip_unet* u, const char* name_c, const v
         k_pack_conv<<<grid_for(numel), 256, 0, s>>>(data, is_f16, c.cout, c.cin, c.taps, c.w);
         PD_LAUNCH_CHECK();
         if (c.wf != nullptr) PD_TRY(conv_rr_pack(c.w, c.cin, c.taps, 0, c.cout, c.wf, s));      // (same stream: ordered behind the repack above)
+        if (c.wph != nullptr) PD_TRY(conv_up2_phase_pack(c.w, c.cin, c.cout_pad, c.wph, s));   // (from the f16-rounded taps: an f32 and an f16 checkpoint give the same bytes)
         c.have_w = true;
         return PDHIP_OK;
     };
@@ -948,6 +981,30 @@ extern "C" int pdhip_debug_set_conv_sk_order(int order) { int old = pdnn::g_sk_o
 /* tuning / test hook: 1 (default) = GroupNorm + SiLU applied inside the consuming halo conv, 0 = stand-alone passes */
 /* tuning / test hook: 1 (default) = up / down ResBlocks never materialise their resampled x branch; 0 = k_resample passes */
 extern "C" int pdhip_debug_set_rr_gn(int max_width) { int old = pdnn::g_rr_gn; pdnn::g_rr_gn = max_width; return old; }
+extern "C" int pdhip_debug_set_up_phase(int mode) { int old = pdnn::g_up_phase; pdnn::g_up_phase = mode; return old; }
+/* stand-alone: the packed 3x3 weights [Cout_pad][9 Cin] f16 -> phase weights [4][Cout_pad][4 Cin] f16 */
+extern "C" int pdhip_pack_conv_up2_phase_f16(const void* w_packed, int Cin, int Cout_pad, void* w_phase, void* stream) {
+    PD_REQUIRE(w_packed && w_phase && Cin > 0 && Cout_pad > 0, "pdhip_pack_conv_up2_phase_f16: bad arguments");
+    return conv_up2_phase_pack((const half_t*)w_packed, Cin, Cout_pad, (half_t*)w_phase, as_stream(stream));
+}
+/* stand-alone: y [N,2H,2W,Cout] = conv3x3(nearest_x2(x [N,H,W,Cin])) + bias through the four phase convs; gn_part (may be NULL): GroupNorm octet
+ * partials [N][4 H W / 256][Cout/8][2] */
+extern "C" int pdhip_conv3x3_up2_phase_nhwc_f16(const void* x, const void* w_phase, const float* bias, void* y, int N, int H, int W, int Cin, int Cout,
+                                                int Cout_pad, const void* zero_page, float* gn_part, void* stream) {
+    PD_REQUIRE(x && w_phase && y && zero_page, "pdhip_conv3x3_up2_phase_nhwc_f16: null argument");
+    return conv_up2_phase((const half_t*)x, (const half_t*)w_phase, bias, (half_t*)y, N, H, W, Cin, Cout, Cout_pad, (const half_t*)zero_page,
+                          as_stream(stream), gn_part, nullptr);
+}
+/* stand-alone: the same layer on the 9-tap halo-resident kernel reading the half-resolution x with index arithmetic (the route the phase conv
+ * replaces; layers that kernel takes unsplit only: 2W in {32 .. 256}) */
+extern "C" int pdhip_conv3x3_up2_halo_nhwc_f16(const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W, int Cin, int Cout,
+                                               int Cout_pad, const void* zero_page, void* stream) {
+    PD_REQUIRE(x && w_packed && y && zero_page, "pdhip_conv3x3_up2_halo_nhwc_f16: null argument");
+    PD_REQUIRE(conv_uses_halo(N, 2 * H, 2 * W, Cin, Cout, Cout_pad, 9, 0) && (2 * W != 256 || (2 * H) % 4 == 0),
+               "pdhip_conv3x3_up2_halo_nhwc_f16: not a layer the halo-resident kernel takes unsplit");
+    return conv_igemm((const half_t*)x, (const half_t*)w_packed, bias, nullptr, (half_t*)y, N, 2 * H, 2 * W, Cin, Cout, Cout_pad, 9,
+                      (const half_t*)zero_page, as_stream(stream), nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, 1);
+}
 extern "C" int pdhip_debug_set_fold_skip(int on) { int old = pdnn::g_fold_skip; pdnn::g_fold_skip = on; return old; }
 extern "C" int pdhip_debug_set_fold_resample(int on) { int old = pdnn::g_fold_resample; pdnn::g_fold_resample = on; return old; }
 extern "C" int pdhip_debug_set_fold_finalize_chunks(int chunks) { int old = pdnn::g_fold_finalize_chunks; pdnn::g_fold_finalize_chunks = chunks; return old; }

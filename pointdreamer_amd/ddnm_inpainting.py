@@ -54,6 +54,10 @@ _reg('pdhip_debug_set_fold_resample', C.c_int, [i32])
 _reg('pdhip_debug_set_fold_finalize', C.c_int, [i32])
 _reg('pdhip_debug_set_fold_finalize_chunks', C.c_int, [i32])
 _reg('pdhip_debug_set_fold_skip', C.c_int, [i32])
+_reg('pdhip_debug_set_up_phase', C.c_int, [i32])
+_reg('pdhip_pack_conv_up2_phase_f16', C.c_int, [vp, i32, i32, vp, vp])
+_reg('pdhip_conv3x3_up2_phase_nhwc_f16', C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp])
+_reg('pdhip_conv3x3_up2_halo_nhwc_f16', C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp])
 _reg('pdhip_debug_set_conv_sk', C.c_int, [i32, i32, i32])
 _reg('pdhip_debug_set_conv_sk_stages', C.c_int, [i32])
 _reg('pdhip_debug_set_conv_sk_kgroups', C.c_int, [i32])

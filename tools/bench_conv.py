@@ -16,6 +16,8 @@ ap.add_argument('--zeros', action='store_true', help='zero activations and weigh
 ap.add_argument('--stamps', action='store_true', help='lab_stamp build: print per-phase cycle averages of the last launch')
 ap.add_argument('--res', action='store_true', help='pass a residual tensor (the out_layers conv of a ResBlock)')
 ap.add_argument('--apply', action='store_true', help='time the APPLY (GroupNorm + SiLU in LDS) variant of the halo kernel on 3x3 shapes')
+ap.add_argument('--up2', type=int, nargs='*', default=None, metavar='N', help='time the in_layers conv of the five up-ResBlocks, conv3x3(nearest_x2(x)), at these batches: '
+                'the 9-tap route (halo kernel reading the half-resolution x; x2 tensor + conv2d where that kernel does not take the layer) against the four 2x2 phase convs (256x256 and 256x128 tiles)')
 ap.add_argument('--lib', default=None, help='alternative libpdhip.so (lab builds)')
 a = ap.parse_args()
 if a.lib:
@@ -25,6 +27,57 @@ if a.custom:
     SHAPES = [tuple(a.custom[i:i + 6]) for i in range(0, len(a.custom), 6)]
 dev = 'cuda:0'
 zp = torch.zeros(128, dtype=torch.float16, device=dev)
+
+def timed(call, iters):
+    for _ in range(3):
+        rc = call(None)
+        if rc != 0:
+            timed.err = L.pdhip_last_error().decode()
+            return None
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    e0.record()
+    for _ in range(iters):
+        call(st)
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3                 # us
+
+
+if a.up2 is not None:
+    print("| up conv1 | N | 9-tap route | us | TFLOP/s (9 taps) | phase 256x256 us | TFLOP/s (4 taps) | phase 256x128 us | TFLOP/s (4 taps) | old / best new |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    for N in (a.up2 or [32]):
+        for hs, Cin, Cout in [(128, 256, 256), (64, 512, 512), (32, 512, 512), (16, 1024, 1024), (8, 1024, 1024)]:
+            x = torch.randn((N, hs, hs, Cin), device=dev).half()
+            w9 = (torch.randn((Cout, 9 * Cin), device=dev) * 0.05).half()
+            wph = torch.empty((4, Cout, 4 * Cin), dtype=torch.float16, device=dev)
+            assert L.pdhip_pack_conv_up2_phase_f16(P(w9), Cin, Cout, P(wph), None) == 0
+            b = torch.zeros(Cout, device=dev)
+            y = torch.empty((N, 2 * hs, 2 * hs, Cout), dtype=torch.float16, device=dev)
+            part = torch.empty((N, max(4 * hs * hs // 256, 1), Cout // 8, 2), device=dev)
+            route = 'halo in_up'
+            t_old = timed(lambda st: L.pdhip_conv3x3_up2_halo_nhwc_f16(P(x), P(w9), P(b), P(y), N, hs, hs, Cin, Cout, Cout, P(zp), st), a.iters)
+            if t_old is None:                                # the engine's other form: a x2 resample pass (not timed here) + the 9-tap conv on the x2 tensor
+                route = 'conv2d on the x2 tensor (+ x2 pass, not timed)'
+                ws = torch.zeros(16 * 384 * 128 * 128, device=dev)
+                L.pdhip_debug_set_conv_splitk(P(ws), ws.numel(), 0)
+                xu = x.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2).contiguous()
+                t_old = timed(lambda st: L.pdhip_conv2d_nhwc_f16(P(xu), P(w9), P(b), None, P(y), N, 2 * hs, 2 * hs, Cin, Cout, Cout, 9, P(zp), st), a.iters)
+                L.pdhip_debug_set_conv_splitk(None, 0, 0)
+                del xu, ws
+            tn = {}
+            for geo in (8, 16):
+                L.pdhip_debug_set_conv_tile(geo)
+                tn[geo] = timed(lambda st: L.pdhip_conv3x3_up2_phase_nhwc_f16(P(x), P(wph), P(b), P(y), N, hs, hs, Cin, Cout, Cout, P(zp), P(part), st), a.iters)
+            L.pdhip_debug_set_conv_tile(0)
+            if t_old is None or None in tn.values():
+                print(f"| {hs}^2 -> {2 * hs}^2, {Cin} -> {Cout} | {N} | failed: {timed.err} |", flush=True)
+                continue
+            f9 = 2.0 * N * 4 * hs * hs * Cout * 9 * Cin
+            f4 = f9 * 4 / 9
+            print(f"| {hs}^2 -> {2 * hs}^2, {Cin} -> {Cout} | {N} | {route} | {t_old:.1f} | {f9 / t_old / 1e6:.0f} | {tn[8]:.1f} | {f4 / tn[8] / 1e6:.0f} | {tn[16]:.1f} | {f4 / tn[16] / 1e6:.0f} | {t_old / min(tn.values()):.2f} |", flush=True)
+    sys.exit(0)
 for si, (N, H, W, Cin, Cout, taps) in enumerate(SHAPES):
     if a.shapes is not None and si not in a.shapes:
         continue
