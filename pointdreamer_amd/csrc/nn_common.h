@@ -17,7 +17,7 @@ typedef __attribute__((ext_vector_type(4))) float float4_t;
 // 3x3 convolution with an LDS-resident activation halo (nn_conv_halo.hip): 512-pixel x 128-channel tiles, W in {64,128,256}
 bool conv3x3_halo_eligible(int N, int H, int W, int Cin, int Cout_pad);
 int conv3x3_halo_splits(int N, int H, int W, int Cin, int Cout, int Cout_pad, size_t splitk_ws_floats);   // 1 direct, >1 split, 0 = do not use
-bool conv_uses_halo(int N, int H, int W, int Cin, int Cout, int Cout_pad, int taps, size_t splitk_ws_floats);   // conv_igemm's routing (nn_gemm.hip)
+int conv3x3_halo_launch_splits(int N, int H, int W, int Cin, int Cout, int Cout_pad, size_t halo_ws_floats);   // what conv3x3_halo launches with (>= 1; honours g_force_splits)
 // apply_table != NULL: the input is silu(A x + B) of X per gn_table (zero padding applies to the TRANSFORMED image)
 int conv3x3_halo(const half_t* X, const half_t* Wt, const float* bias, const half_t* residual, half_t* Y, int N, int H, int W,
                  int Cin, int Cout, int Cout_pad, const half_t* zero_page, hipStream_t s, float* gn_part, int* gn_fused,
@@ -56,8 +56,6 @@ int fuse_skip_weights(const half_t* w3, int K9, const half_t* w1, int Cs, int Co
 int conv_sk(const SkPlan& pl, const half_t* X, const half_t* Wt, const float* bias, const half_t* residual, half_t* Y, int N, int H, int W,
             int Cin, int Cout, int Cout_pad, int taps, const half_t* zero_page, hipStream_t s, float* ws, size_t ws_floats, float* gn_part,
             int* gn_fused, const half_t* X2, int Cin1, int res_up = 0);      // res_up: residual = half-resolution tensor read with nearest x2
-// conv_igemm's routing decision for a single-source layer without input transform: does it go to k_conv_sk? (nn_gemm.hip)
-bool conv_routes_small(int N, int H, int W, int Cin, int Cout, int Cout_pad, int taps, size_t splitk_ws_floats);
 extern thread_local int g_sk_mode, g_sk_tile, g_sk_splits, g_sk_stages, g_sk_kg, g_sk_order;                         // tuning / test hooks (pdhip_debug_set_conv_sk)
 #define PD_SK_TICKET_FLOATS 4096
 // combine per-(chunk, channel-octet) partial sums written by the conv epilogue ([N][chunks][C/8][2]) of one tensor, or of
@@ -90,6 +88,46 @@ int conv_ht_slabs(int N, int H, int W, int Cin, int Cout_pad, size_t ws_floats);
 int conv_ht(const half_t* X, const half_t* Wt, const float* bias, const half_t* residual, half_t* Y, int N, int H, int W, int Cin, int Cout,
             int Cout_pad, const half_t* zero_page, hipStream_t s, float* gn_part, int* gn_chunks, int res_up, float* ws, size_t ws_floats);
 extern thread_local int g_ht_mode;
+
+// ---- the route of ONE conv (nn_gemm.hip): which of the six kernels runs it, with what split, what it leaves behind and what it absorbs.
+// conv_plan() is the only place a kernel is chosen; conv_launch() is the only place one is started.  Pure host code: no device needed.
+enum ConvKernel { CONV_HALO, CONV_RR, CONV_HT, CONV_SK, CONV_IGEMM, CONV_UP_PHASE };
+const char* conv_kernel_name(ConvKernel k);
+struct ConvNeeds {                 // two_source is a fact of the input; the rest are wishes -- the plan's takes_* say which the kernel absorbs
+    bool two_source = false;       //   input = never-materialised channel concat (1x1 only)
+    bool in_up = false;            //   input = half-resolution tensor read as its nearest x2
+    bool apply = false;            //   GroupNorm (+ FiLM) + SiLU from an (A, B) table while staging (halo kernel)
+    bool in_gn = false;            //   the same from the producers' octet partials while staging (row-resident kernel)
+    bool want_gn = false;          //   leave GroupNorm octet partials of the output
+    int skip_cs = 0;               //   channels of the ResBlock's skip 1x1 to append to the K loop (0 = none)
+    bool have_wf = false, have_wf_skip = false;   // fragment-major weights exist (plain / with the skip appended)
+};
+struct ConvPlan {
+    int N = 0, H = 0, W = 0, Cin = 0, Cout = 0, Cout_pad = 0, taps = 0;   // H, W: the resolution the conv runs at (its output's)
+    ConvKernel kernel = CONV_IGEMM;
+    SkPlan sk{0, 0, 0, 0}; RrPlan rr{0, 0, 0, 0, 0, 0, 0};
+    int splits = 1;                // HALO / IGEMM: split-K factor
+    int slabs = 1;                 // HT: K-slabs
+    int bk = 0, geo = 0;           // IGEMM: K-step and tile geometry
+    bool want_gn = false;          // the caller keeps room for the output's octet partials
+    int gn_chunks = 0;             // octet-partial chunks per image the launch leaves (0 = none)
+    bool takes_res_up = false;     // can read its residual from the half-resolution tensor
+    bool takes_in_up = false, takes_apply = false, takes_in_gn = false, takes_skip = false;   // the wishes of ConvNeeds it absorbs
+    int skip_cs = 0;               // takes_skip: channels of the appended skip 1x1
+};
+ConvPlan conv_plan(int N, int H, int W, int Cin, int Cout, int Cout_pad, int taps, const ConvNeeds& needs, size_t ws_floats);
+// the up-ResBlock phase conv is chosen by the engine (nn_unet.hip), not by precedence; (H, W) = the output, twice the input it reads
+ConvPlan conv_up2_phase_plan(int N, int H, int W, int Cin, int Cout, int Cout_pad, bool want_gn);
+struct ConvArgs {
+    const half_t* X; const half_t* X2; int Cin1;      // X2 / Cin1: second tensor of a two-source input
+    const half_t* Wt;                                  // the weights in the chosen kernel's layout
+    const float* bias; const half_t* residual; int res_up;
+    const float* apply_table;                          // takes_apply
+    const RrIn* rr_in;                                 // takes_in_gn: the source with its GroupNorm description
+    const half_t* XS; const half_t* XS2; int Cs1;      // takes_skip: the skip source [XS (Cs1 channels) | XS2]
+    half_t* Y; const half_t* zero_page; float* ws; size_t ws_floats; float* gn_part;
+};
+int conv_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t s, int* gn_chunks);   // *gn_chunks: what the launcher left (== p.gn_chunks when a.gn_part != NULL)
 
 // ---- the GroupNorm (+ FiLM) (+ SiLU) element map (nn_norm.hip's k_gn_apply and nn_conv_rr.hip's staging: ONE definition, bit-identical results)
 // x * sigmoid(x); v_rcp_f32 (1 ulp) instead of the IEEE divide sequence: the result is rounded to f16 (or feeds the f32 head,

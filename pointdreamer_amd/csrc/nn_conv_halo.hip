@@ -522,6 +522,15 @@ int conv3x3_halo_splits(int N, int H, int W, int Cin, int Cout, int Cout_pad, si
     return splits;
 }
 
+// the split factor conv3x3_halo launches with (ws_floats: what the launcher may use, 0 = no workspace)
+int conv3x3_halo_launch_splits(int N, int H, int W, int Cin, int Cout, int Cout_pad, size_t ws_floats) {
+    int splits = conv3x3_halo_splits(N, H, W, Cin, Cout, Cout_pad, ws_floats);
+    if (splits < 1) splits = 1;
+    if (g_force_splits >= 1 && ws_floats > 0)                   // tuning / test hook
+        splits = (int)std::min<size_t>(std::min(g_force_splits, Cin / 32), ws_floats / ((size_t)N * H * W * Cout));
+    return splits < 1 ? 1 : splits;
+}
+
 // gn_part (optional): fused GroupNorm octet partials; chunks per image returned through gn_fused (H*W/512 from the direct
 // epilogue, H*W/16 from the split reduce)
 int conv3x3_halo(const half_t* X, const half_t* Wt, const float* bias, const half_t* residual, half_t* Y, int N, int H, int W,
@@ -529,11 +538,7 @@ int conv3x3_halo(const half_t* X, const half_t* Wt, const float* bias, const hal
                  float* splitk_ws, size_t splitk_ws_floats, const float* apply_table, int res_up, int in_up) {
     PD_REQUIRE(in_up == 0 || (apply_table == nullptr && H % 2 == 0), "conv3x3_halo: an up-sampled input excludes the in-conv GroupNorm");
     PD_REQUIRE(conv3x3_halo_eligible(N, H, W, Cin, Cout_pad), "conv3x3_halo: unsupported geometry (N=%d H=%d W=%d Cin=%d)", N, H, W, Cin);
-    int splits = conv3x3_halo_splits(N, H, W, Cin, Cout, Cout_pad, splitk_ws ? splitk_ws_floats : 0);
-    if (splits < 1) splits = 1;
-    if (g_force_splits >= 1 && splitk_ws != nullptr)            // tuning / test hook
-        splits = (int)std::min<size_t>(std::min(g_force_splits, Cin / 32), splitk_ws_floats / ((size_t)N * H * W * Cout));
-    if (splits < 1) splits = 1;
+    const int splits = conv3x3_halo_launch_splits(N, H, W, Cin, Cout, Cout_pad, splitk_ws ? splitk_ws_floats : 0);
     PD_REQUIRE(!res_up || (splits == 1 && residual != nullptr && H % 2 == 0), "conv3x3_halo: an up-sampled residual needs the direct (unsplit) epilogue");
     float* partial = splits > 1 ? splitk_ws : nullptr;
     const bool fuse_sk = splits > 1 && gn_part != nullptr && (H * W) % 16 == 0;

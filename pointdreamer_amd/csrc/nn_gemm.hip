@@ -572,37 +572,124 @@ static int launch_conv(dim3 grid, size_t smem, hipStream_t s, const half_t* X, c
     return PDHIP_OK;
 }
 
-// does conv_igemm route this layer to the halo-resident kernel? (tuning hook: tile geometry 32 forces it, any other forced
-// geometry / K-step / stage count disables it)
-bool conv_uses_halo(int N, int H, int W, int Cin, int Cout, int Cout_pad, int taps, size_t splitk_ws_floats) {
-    if (taps != 9 || !conv3x3_halo_eligible(N, H, W, Cin, Cout_pad)) return false;
-    if (g_force_wmw == 32) return true;
-    // automatic use only when the tiles alone fill the chip: with the chunk split (small-M layers) the halo kernel measures
-    // no better than the 128x128 split-K path (tools/bench_splitk.py: 54 vs 51 us at 32x32 / 512 -> 512)
-    return g_force_wmw == 0 && g_force_bk == 0 && g_force_stages == 0 && g_force_splits == 0 &&
-           conv3x3_halo_splits(N, H, W, Cin, Cout, Cout_pad, 0) == 1;
+const char* conv_kernel_name(ConvKernel k) {
+    static const char* const names[] = {"halo", "rr", "ht", "sk", "igemm", "phase"};
+    return names[k];
 }
 
-// THE routing decision of conv_igemm() -- the one copy of it (run_res predicts the route of conv2 to decide whether the
-// up-sampled x branch needs materialising; a second copy of the predicate could drift from the one that launches): 0 = halo-resident
-// kernel, 1 = k_conv_sk (plan in *plan), 2 = the implicit-GEMM kernel, 3 = k_conv_ht (256 x 64 halo tiles: the 64^2 / 128^2 levels at batch 1-2).
-int conv_route(int N, int H, int W, int Cin, int Cout, int Cout_pad, int taps, size_t splitk_ws_floats, bool two_source, bool in_up,
-               bool apply, SkPlan* plan) {
-    if (!two_source && conv_uses_halo(N, H, W, Cin, Cout, Cout_pad, taps, splitk_ws_floats)) return 0;
-    if (taps == 9 && !two_source && !in_up && !apply && g_force_wmw == 0 && g_force_bk == 0 && g_force_stages == 0 && g_force_splits == 0 &&
-        conv_ht_routes(N, H, W, Cin, Cout, Cout_pad, splitk_ws_floats)) return 3;
-    if (!in_up && !apply && g_force_wmw == 0 && g_force_bk == 0 && g_force_stages == 0 && g_force_splits == 0) {
-        const SkPlan pl = conv_sk_plan(N, H, W, Cin, Cout, Cout_pad, taps, two_source, splitk_ws_floats);
-        if (pl.bm > 0) {
-            if (plan) *plan = pl;
-            return 1;
+// THE routing decision: every conv of the engine and of the stand-alone entry points gets its kernel here and nowhere else.  Precedence,
+// first match wins (W = 256 layers whose height is no multiple of 4 run the halo kernel on full rows, which absorbs nothing):
+//   1. halo + apply       the caller wishes the in-conv GroupNorm (needs.apply) and the layer is a halo layer (2. or 6.)
+//   2. rr / sk + skip     the caller wishes the skip 1x1 appended (needs.skip_cs), no halo layer: k_conv_rr, else k_conv_sk
+//   3. rr + in_gn         the caller wishes the in-staging GroupNorm (needs.in_gn) and k_conv_rr has a variant that carries it
+//   4. halo, unsplit      3x3, single source, halo geometry, the tiles alone fill the chip (or tile hook 32 and >= 256 tiles)
+//   5. rr                 fragment-major weights exist, 3x3, single source, no in_up: whatever conv_rr_plan takes (g_rr_* hooks)
+//   6. halo, split        only under the tile hook (g_force_wmw == 32); takes in_up, not res_up
+//   7. ht                 3x3, single source, no forced geometry: conv_ht_routes (g_ht_mode)
+//   8. sk                 no forced geometry: conv_sk_plan (g_sk_* hooks)
+//   9. igemm              everything else; any forced geometry / K-step / stage count / split (g_force_*) other than tile 32 lands here
+// A wish the chosen kernel does not absorb (takes_* false) is the caller's to serve with a pass of its own.
+ConvPlan conv_plan(int N, int H, int W, int Cin, int Cout, int Cout_pad, int taps, const ConvNeeds& nd, size_t ws_floats) {
+    ConvPlan p;
+    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.Cout_pad = Cout_pad; p.taps = taps;
+    const long long hw = (long long)H * W, M = (long long)N * hw;
+    const bool forced = g_force_wmw != 0 || g_force_bk != 0 || g_force_stages != 0 || g_force_splits != 0;
+    // automatic halo use only when the tiles alone fill the chip: with the chunk split (small-M layers) the halo kernel measures
+    // no better than the 128x128 split-K path (tools/bench_splitk.py: 54 vs 51 us at 32x32 / 512 -> 512)
+    const bool halo = !nd.two_source && taps == 9 && conv3x3_halo_eligible(N, H, W, Cin, Cout_pad) &&
+                      (g_force_wmw == 32 || (!forced && conv3x3_halo_splits(N, H, W, Cin, Cout, Cout_pad, 0) == 1));
+    const bool unsplit = halo && conv3x3_halo_splits(N, H, W, Cin, Cout, Cout_pad, ws_floats) == 1;
+    const bool strips = W != 256 || H % 4 == 0;
+    const bool single3 = taps == 9 && !nd.two_source;
+    // (the first PD_SK_TICKET_FLOATS words of the workspace are k_conv_sk's self-resetting ticket counters: the f32 partials of the halo
+    // and implicit-GEMM kernels must not land on them, or the next split k_conv_sk launch never sees its last ticket)
+    const size_t part_floats = ws_floats > PD_SK_TICKET_FLOATS ? ws_floats - PD_SK_TICKET_FLOATS : 0;
+    auto done = [&](ConvKernel k) {
+        p.kernel = k;
+        int chunks = 0;
+        switch (k) {
+        case CONV_HALO:
+            p.splits = conv3x3_halo_launch_splits(N, H, W, Cin, Cout, Cout_pad, part_floats);
+            chunks = p.splits > 1 ? (hw % 16 == 0 ? (int)(hw / 16) : 0) : (int)(hw / 512);
+            p.takes_res_up = unsplit && p.splits == 1 && strips;
+            break;
+        case CONV_RR: chunks = p.rr.bands; p.takes_res_up = true; break;
+        case CONV_HT: p.slabs = conv_ht_slabs(N, H, W, Cin, Cout_pad, ws_floats); chunks = (int)(hw / 256); p.takes_res_up = true; break;
+        case CONV_SK: chunks = (hw % p.sk.bm == 0 || p.sk.bm == 2 * hw) ? std::max((int)(hw / p.sk.bm), 1) : 0; p.takes_res_up = true; break;
+        default: {
+            p.bk = (g_force_bk == 32 || Cin % 64 != 0) ? 32 : 64;
+            // tile geometry: 256x256 (wave tile 128x64: 25 % fewer LDS reads per MFMA, half the L2 traffic) once it still yields
+            // at least one workgroup per CU; 128x128 otherwise
+            int geo = g_force_wmw;
+            if (geo != 2 && geo != 4 && geo != 8 && geo != 16)
+                geo = (Cout_pad % 256 == 0 && ((M + 255) / 256) * (Cout_pad / 256) >= 256) ? 8 : 2;
+            if (geo == 8 && Cout_pad % 256 != 0) geo = 2;
+            p.geo = geo;
+            const int bmt = geo == 2 ? 128 : 256, bnt = geo == 8 ? 256 : 128;    // geo 16: 256x128, 4 waves with 128x64 wave tiles
+            const int total = (int)((M + bmt - 1) / bmt) * (Cout_pad / bnt);
+            // small-M 3x3 layers (32x32 .. 8x8 levels) leave most of the 256 CUs idle: split the K loop across workgroups, aiming at
+            // ~512 work items but never more than 8 splits -- the f32 partial round trip costs more than it buys beyond that, and
+            // never for 1x1 convs, whose K loop is too short to amortise it (tools/bench_splitk.py holds the measured table)
+            const int KI = taps * (Cin / p.bk);
+            int splits = 1;
+            if (part_floats > 0 && taps == 9 && total <= 256) {
+                // up to 8 splits in general; tiny-M layers (the 8x8 / 16x16 levels at batch 1-2: 8-16 tiles, a weight stream of 19-38 MB
+                // per conv) go on splitting while the f32 partials stay small (<= 8 MB: L2-resident), up to 32 -- measured at batch 1
+                // (tools/time_unet.py): 22-24 us -> see DESIGN section 8
+                int cap = 8;
+                while (cap < 32 && total * cap < 256 && (size_t)(2 * cap) * M * Cout * sizeof(float) <= (size_t)8 << 20) cap *= 2;
+                splits = std::min(std::min((512 + total / 2) / total, KI / 2), cap);
+                while (splits > 1 && (size_t)splits * M * Cout > part_floats) --splits;
+            }
+            if (g_force_splits >= 1 && part_floats > 0)
+                splits = (int)std::min<size_t>(std::min(g_force_splits, std::max(KI / 2, 1)), part_floats / ((size_t)M * Cout));
+            if (splits < 1 || nd.two_source) splits = 1;
+            p.splits = splits;
+            // fused GroupNorm partial statistics: only when a tile never straddles two images (split: from the reduce kernel)
+            chunks = splits == 1 ? (hw % bmt == 0 ? (int)(hw / bmt) : 0) : (hw % SK_ROWS == 0 ? (int)(hw / SK_ROWS) : 0);
         }
+        }
+        p.gn_chunks = nd.want_gn ? chunks : 0;
+        return p;
+    };
+    p.want_gn = nd.want_gn;
+    p.takes_apply = nd.apply && halo && strips;
+    if (p.takes_apply) return done(CONV_HALO);
+    if (nd.skip_cs > 0 && !halo && taps == 9) {
+        p.skip_cs = nd.skip_cs;
+        if (nd.have_wf_skip) {
+            p.rr = conv_rr_plan(N, H, W, Cin, Cout, 9, nd.skip_cs, ws_floats);
+            if (p.rr.variant != 0) { p.takes_skip = true; return done(CONV_RR); }
+        }
+        p.sk = conv_sk_plan(N, H, W, Cin, Cout, Cout_pad, 9, false, ws_floats, nd.skip_cs);
+        if (p.sk.bm > 0) { p.takes_skip = true; return done(CONV_SK); }
+        p.skip_cs = 0;
     }
-    return 2;
+    if (nd.in_gn && nd.have_wf && single3) {
+        p.rr = conv_rr_plan(N, H, W, Cin, Cout, 9, 0, ws_floats, true);
+        if (p.rr.variant != 0) { p.takes_in_gn = true; return done(CONV_RR); }
+    }
+    p.takes_in_up = nd.in_up && halo && strips;
+    if (unsplit) return done(CONV_HALO);
+    if (nd.have_wf && single3 && !p.takes_in_up && !unsplit) {
+        p.rr = conv_rr_plan(N, H, W, Cin, Cout, 9, 0, ws_floats);
+        if (p.rr.variant != 0) return done(CONV_RR);
+    }
+    if (halo) return done(CONV_HALO);
+    if (single3 && !forced && conv_ht_routes(N, H, W, Cin, Cout, Cout_pad, ws_floats)) return done(CONV_HT);
+    if (!forced) {
+        p.sk = conv_sk_plan(N, H, W, Cin, Cout, Cout_pad, taps, nd.two_source, ws_floats);
+        if (p.sk.bm > 0) return done(CONV_SK);
+    }
+    return done(CONV_IGEMM);
 }
-bool conv_routes_small(int N, int H, int W, int Cin, int Cout, int Cout_pad, int taps, size_t splitk_ws_floats) {   // k_conv_sk or k_conv_ht
-    const int r = conv_route(N, H, W, Cin, Cout, Cout_pad, taps, splitk_ws_floats, false, false, false, nullptr);
-    return r == 1 || r == 3;
+
+ConvPlan conv_up2_phase_plan(int N, int H, int W, int Cin, int Cout, int Cout_pad, bool want_gn) {
+    ConvPlan p;
+    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.Cout_pad = Cout_pad; p.taps = 9;
+    p.kernel = CONV_UP_PHASE; p.want_gn = want_gn;
+    p.gn_chunks = want_gn && ((long long)H * W / 4) % 256 == 0 ? (int)((long long)H * W / 256) : 0;   // 4 phases x 256-pixel tiles of the half-resolution image
+    return p;
 }
 
 int splitk_reduce(const float* partial, int splits, long long M, int Cout, const float* bias, const half_t* residual, half_t* Y,
@@ -613,6 +700,89 @@ int splitk_reduce(const float* partial, int splits, long long M, int Cout, const
     return PDHIP_OK;
 }
 
+// the one place a conv kernel is started: p says which, a carries the operands in that kernel's layouts
+int conv_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t s, int* gn_chunks) {
+    const int N = p.N, H = p.H, W = p.W, Cin = p.Cin, Cout = p.Cout, Cout_pad = p.Cout_pad, taps = p.taps;
+    const long long hw = (long long)H * W, M = (long long)N * hw;
+    float* part_ws = a.ws != nullptr && a.ws_floats > PD_SK_TICKET_FLOATS ? a.ws + PD_SK_TICKET_FLOATS : nullptr;   // behind k_conv_sk's tickets
+    const size_t part_floats = part_ws != nullptr ? a.ws_floats - PD_SK_TICKET_FLOATS : 0;
+    int chunks = 0, rc = PDHIP_OK;
+    switch (p.kernel) {
+    case CONV_HALO:
+        rc = conv3x3_halo(a.X, a.Wt, a.bias, a.residual, a.Y, N, H, W, Cin, Cout, Cout_pad, a.zero_page, s, a.gn_part, &chunks, part_ws, part_floats,
+                          a.apply_table, a.res_up, p.takes_in_up ? 1 : 0);
+        break;
+    case CONV_RR: {
+        const RrIn plain{a.X, nullptr, Cin, Cin, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 1e-5f};
+        const RrIn skip{a.XS, a.XS2, p.skip_cs, a.XS2 ? a.Cs1 : p.skip_cs, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 1e-5f};
+        rc = conv_rr(p.rr, p.takes_in_gn ? *a.rr_in : plain, p.takes_skip ? &skip : nullptr, 9, a.Wt, a.bias, a.residual, a.res_up, a.Y, N, H, W, Cout,
+                     a.ws, a.ws_floats, a.gn_part, &chunks, s);
+        break;
+    }
+    case CONV_HT:
+        rc = conv_ht(a.X, a.Wt, a.bias, a.residual, a.Y, N, H, W, Cin, Cout, Cout_pad, a.zero_page, s, a.gn_part, &chunks, a.res_up, a.ws, a.ws_floats);
+        break;
+    case CONV_SK: {      // small-M layers (output tiles do not fill the chip): small tiles, deep staging, split-K combined inside the launch
+        float* gnp = (a.gn_part != nullptr && (hw % p.sk.bm == 0 || p.sk.bm == 2 * hw)) ? a.gn_part : nullptr;
+        rc = p.takes_skip ? conv_sk_skip(p.sk, a.X, a.Wt, a.bias, a.Y, N, H, W, Cin, Cout, Cout_pad, a.XS, a.XS2, a.XS2 ? a.Cs1 : p.skip_cs, p.skip_cs,
+                                         a.zero_page, s, a.ws, a.ws_floats, gnp, &chunks)
+                          : conv_sk(p.sk, a.X, a.Wt, a.bias, a.residual, a.Y, N, H, W, Cin, Cout, Cout_pad, taps, a.zero_page, s, a.ws, a.ws_floats, gnp,
+                                    &chunks, a.X2, a.X2 ? a.Cin1 : Cin, a.res_up);
+        break;
+    }
+    case CONV_UP_PHASE:
+        rc = conv_up2_phase(a.X, a.Wt, a.bias, a.Y, N, H / 2, W / 2, Cin, Cout, Cout_pad, a.zero_page, s, a.gn_part, &chunks);
+        break;
+    case CONV_IGEMM: {
+        const half_t *X = a.X, *Wt = a.Wt, *residual = a.residual, *zero_page = a.zero_page, *X2 = a.X2;
+        const float* bias = a.bias;
+        half_t* Y = a.Y;
+        const int Cin1 = X2 ? a.Cin1 : Cin, bk = p.bk, geo = p.geo, splits = p.splits;
+        PD_REQUIRE(a.res_up == 0, "conv_igemm: an up-sampled residual needs a layer the halo-resident kernel (unsplit), k_conv_rr, k_conv_ht or k_conv_sk takes");
+        const int bmt = geo == 2 ? 128 : 256, bnt = geo == 8 ? 256 : 128;
+        const int m_tiles = (int)((M + bmt - 1) / bmt), n_tiles = Cout_pad / bnt;
+        const int total = m_tiles * n_tiles;
+        float* partial = splits > 1 ? part_ws : nullptr;
+        dim3 grid(total, splits);
+        const bool fuse = a.gn_part != nullptr && splits == 1 && hw % bmt == 0;
+        const bool fuse_sk = a.gn_part != nullptr && splits > 1 && hw % SK_ROWS == 0;   // stats from the reduce kernel
+        chunks = fuse ? (int)(hw / bmt) : fuse_sk ? (int)(hw / SK_ROWS) : 0;
+        float* gnp = fuse ? a.gn_part : nullptr;
+        // 12 = two stages + register-pipelined schedule: the default for the 256x256 tile (+8..16 % over the compiler's schedule)
+        int stages = g_force_stages ? g_force_stages : (bk == 64 ? (geo == 8 ? 12 : 2) : 3);
+        const bool pipe = stages == 12 && bk == 64 && (geo == 8 || geo == 16);   // written for the 128-row wave tile
+        if (stages == 12) stages = 2;
+        if (stages < 2) stages = 2;
+        if (stages > 4) stages = 4;
+        const size_t stage_bytes = (size_t)(bmt + bnt) * bk * 2;
+        while (stages > 2 && stages * stage_bytes > 160 * 1024) --stages;
+        const size_t smem = std::max<size_t>((size_t)stages * stage_bytes, (size_t)bmt * (bnt + 8) * 2);
+        if (pipe) stages = 12;
+#define ARGS grid, smem, s, X, Wt, bias, residual, Y, N, H, W, Cin, Cout, n_tiles, total, zero_page, splits, partial, gnp, X2, Cin1
+#define BY_STAGE(T, B, WM_, WN_, TM_)                                                   \
+    (stages == 2 ? launch_conv<T, B, 2, WM_, WN_, TM_>(ARGS) : stages == 3 ? launch_conv<T, B, 3, WM_, WN_, TM_>(ARGS) \
+                                                              : launch_conv<T, B, 4, WM_, WN_, TM_>(ARGS))
+#define BY_STAGE64(T, WM_, WN_, TM_) (stages == 12 ? launch_conv<T, 64, 12, WM_, WN_, TM_>(ARGS) : BY_STAGE(T, 64, WM_, WN_, TM_))
+#define BY_GEO(T, B) (geo == 2 ? BY_STAGE(T, B, 2, 2, 4) : geo == 4 ? BY_STAGE(T, B, 4, 2, 4) : geo == 8 ? BY_STAGE(T, B, 2, 4, 8) : BY_STAGE(T, B, 2, 2, 8))
+#define BY_GEO64(T) (geo == 2 ? BY_STAGE(T, 64, 2, 2, 4) : geo == 4 ? BY_STAGE(T, 64, 4, 2, 4) : geo == 8 ? BY_STAGE64(T, 2, 4, 8) : BY_STAGE64(T, 2, 2, 8))
+        if (taps == 9) rc = (bk == 64) ? BY_GEO64(9) : BY_GEO(9, 32);
+        else rc = (bk == 64) ? BY_GEO64(1) : BY_GEO(1, 32);
+#undef BY_GEO64
+#undef BY_GEO
+#undef BY_STAGE64
+#undef BY_STAGE
+#undef ARGS
+        if (rc) return rc;
+        if (splits > 1) rc = splitk_reduce(partial, splits, M, Cout, bias, residual, Y, fuse_sk ? a.gn_part : nullptr, H * W, s);
+        else PD_LAUNCH_CHECK();
+        break;
+    }
+    }
+    if (gn_chunks) *gn_chunks = chunks;
+    return rc;
+}
+
+// stand-alone form (the C entry points and the kernel tests): plan + launch, a wish the layer's kernel cannot absorb is an error
 int conv_igemm(const half_t* X, const half_t* Wt, const float* bias, const half_t* residual, half_t* Y, int N, int H,
                int W, int Cin, int Cout, int Cout_pad, int taps, const half_t* zero_page, hipStream_t s, float* splitk_ws,
                size_t splitk_ws_floats, float* gn_part, int* gn_fused, const half_t* X2, int Cin1, const float* apply_table, int res_up, int in_up) {
@@ -622,105 +792,15 @@ int conv_igemm(const half_t* X, const half_t* Wt, const float* bias, const half_
                "conv_igemm: a two-source input needs a 1x1 conv and channel counts that are multiples of 64");
     PD_REQUIRE(Cin % 32 == 0 && Cout % 8 == 0 && Cout_pad % 128 == 0 && Cout_pad >= Cout,
                "conv_igemm: need Cin %% 32 == 0, Cout %% 8 == 0, padded Cout %% 128 == 0 (Cin=%d Cout=%d pad=%d)", Cin, Cout, Cout_pad);
-    const long long M = (long long)N * H * W;
-    // large-image 3x3 layers: halo-resident kernel (2.1x less L2 -> LDS traffic per flop) once it fills the chip
-    // (tuning hook: tile geometry 32 forces it, any other forced geometry disables it)
-    SkPlan pl{0, 0, 0, 0};
-    const int route = conv_route(N, H, W, Cin, Cout, Cout_pad, taps, splitk_ws ? splitk_ws_floats : 0, X2 != nullptr, in_up != 0, apply_table != nullptr, &pl);
-    if (route == 0) {
-        // (the first PD_SK_TICKET_FLOATS words of the workspace are k_conv_sk's self-resetting ticket counters: the halo kernel's f32
-        // partials -- only under the forced-split tuning hooks -- must not land on them, or the next split k_conv_sk launch never
-        // sees its last ticket)
-        float* hws = splitk_ws != nullptr && splitk_ws_floats > PD_SK_TICKET_FLOATS ? splitk_ws + PD_SK_TICKET_FLOATS : nullptr;
-        const size_t hfl = hws != nullptr ? splitk_ws_floats - PD_SK_TICKET_FLOATS : 0;
-        return conv3x3_halo(X, Wt, bias, residual, Y, N, H, W, Cin, Cout, Cout_pad, zero_page, s, gn_part, gn_fused, hws, hfl, apply_table,
-                            res_up, in_up);
-    }
-    if (route == 3) {
-        int chunks = 0;
-        const int rc = conv_ht(X, Wt, bias, residual, Y, N, H, W, Cin, Cout, Cout_pad, zero_page, s, gn_part, &chunks, res_up, splitk_ws, splitk_ws_floats);
-        if (gn_fused) *gn_fused = chunks;
-        return rc;
-    }
-    // small-M layers (output tiles do not fill the chip): small tiles, deep staging, split-K combined inside the launch
-    if (route == 1) {
-        float* gnp = (gn_part != nullptr && (((long long)H * W) % pl.bm == 0 || pl.bm == 2 * H * W)) ? gn_part : nullptr;
-        return conv_sk(pl, X, Wt, bias, residual, Y, N, H, W, Cin, Cout, Cout_pad, taps, zero_page, s, splitk_ws, splitk_ws_floats, gnp,
-                       gn_fused, X2, Cin1, res_up);
-    }
-    // (the first PD_SK_TICKET_FLOATS words of the split-K workspace are k_conv_sk's ticket counters)
-    if (splitk_ws != nullptr) {
-        if (splitk_ws_floats > PD_SK_TICKET_FLOATS) { splitk_ws += PD_SK_TICKET_FLOATS; splitk_ws_floats -= PD_SK_TICKET_FLOATS; }
-        else { splitk_ws = nullptr; splitk_ws_floats = 0; }
-    }
-    PD_REQUIRE(in_up == 0, "conv_igemm: an up-sampled input needs a layer the halo-resident kernel takes");
-    PD_REQUIRE(res_up == 0, "conv_igemm: an up-sampled residual needs a layer the halo-resident kernel (unsplit) or k_conv_sk takes");
-    PD_REQUIRE(apply_table == nullptr, "conv_igemm: an input transform needs a layer the halo-resident kernel takes");
-    const int bk = (g_force_bk == 32 || Cin % 64 != 0) ? 32 : 64;
-    // tile geometry: 256x256 (wave tile 128x64: 25 % fewer LDS reads per MFMA, half the L2 traffic) once it still yields
-    // at least one workgroup per CU; 128x128 otherwise
-    int geo = g_force_wmw;
-    if (geo != 2 && geo != 4 && geo != 8 && geo != 16)
-        geo = (Cout_pad % 256 == 0 && ((M + 255) / 256) * (Cout_pad / 256) >= 256) ? 8 : 2;
-    if (geo == 8 && Cout_pad % 256 != 0) geo = 2;
-    const int bmt = geo == 2 ? 128 : 256, bnt = geo == 8 ? 256 : 128;    // geo 16: 256x128, 4 waves with 128x64 wave tiles
-    const int m_tiles = (int)((M + bmt - 1) / bmt), n_tiles = Cout_pad / bnt;
-    const int total = m_tiles * n_tiles;
-    // small-M 3x3 layers (32x32 .. 8x8 levels) leave most of the 256 CUs idle: split the K loop across workgroups, aiming at
-    // ~512 work items but never more than 8 splits -- the f32 partial round trip costs more than it buys beyond that, and
-    // never for 1x1 convs, whose K loop is too short to amortise it (tools/bench_splitk.py holds the measured table)
-    const int KI = taps * (Cin / bk);
-    int splits = 1;
-    if (splitk_ws != nullptr && taps == 9 && total <= 256) {
-        // up to 8 splits in general; tiny-M layers (the 8x8 / 16x16 levels at batch 1-2: 8-16 tiles, a weight stream of 19-38 MB
-        // per conv) go on splitting while the f32 partials stay small (<= 8 MB: L2-resident), up to 32 -- measured at batch 1
-        // (tools/time_unet.py): 22-24 us -> see DESIGN section 8
-        int cap = 8;
-        while (cap < 32 && total * cap < 256 && (size_t)(2 * cap) * M * Cout * sizeof(float) <= (size_t)8 << 20) cap *= 2;
-        splits = std::min(std::min((512 + total / 2) / total, KI / 2), cap);
-        while (splits > 1 && (size_t)splits * M * Cout > splitk_ws_floats) --splits;
-    }
-    if (g_force_splits >= 1 && splitk_ws != nullptr)
-        splits = (int)std::min<size_t>(std::min(g_force_splits, std::max(KI / 2, 1)), splitk_ws_floats / ((size_t)M * Cout));
-    if (splits < 1 || X2 != nullptr) splits = 1;
-    float* partial = splits > 1 ? splitk_ws : nullptr;
-    dim3 grid(total, splits);
-    // fused GroupNorm partial statistics: only when a tile never straddles two images
-    const bool fuse = gn_part != nullptr && splits == 1 && ((long long)H * W) % bmt == 0;
-    const bool fuse_sk = gn_part != nullptr && splits > 1 && ((long long)H * W) % SK_ROWS == 0;   // stats from the reduce kernel
-    if (gn_fused) *gn_fused = fuse ? (int)(((long long)H * W) / bmt) : fuse_sk ? (int)(((long long)H * W) / SK_ROWS) : 0;
-    float* gnp = fuse ? gn_part : nullptr;
-    // 12 = two stages + register-pipelined schedule: the default for the 256x256 tile (+8..16 % over the compiler's schedule)
-    int stages = g_force_stages ? g_force_stages : (bk == 64 ? (geo == 8 ? 12 : 2) : 3);
-    const bool pipe = stages == 12 && bk == 64 && (geo == 8 || geo == 16);   // written for the 128-row wave tile
-    if (stages == 12) stages = 2;
-    if (stages < 2) stages = 2;
-    if (stages > 4) stages = 4;
-    const size_t stage_bytes = (size_t)(bmt + bnt) * bk * 2;
-    while (stages > 2 && stages * stage_bytes > 160 * 1024) --stages;
-    const size_t smem = std::max<size_t>((size_t)stages * stage_bytes, (size_t)bmt * (bnt + 8) * 2);
-    if (pipe) stages = 12;
-#define ARGS grid, smem, s, X, Wt, bias, residual, Y, N, H, W, Cin, Cout, n_tiles, total, zero_page, splits, partial, gnp, X2, Cin1
-#define BY_STAGE(T, B, WM_, WN_, TM_)                                                   \
-    (stages == 2 ? launch_conv<T, B, 2, WM_, WN_, TM_>(ARGS) : stages == 3 ? launch_conv<T, B, 3, WM_, WN_, TM_>(ARGS) \
-                                                              : launch_conv<T, B, 4, WM_, WN_, TM_>(ARGS))
-#define BY_STAGE64(T, WM_, WN_, TM_) (stages == 12 ? launch_conv<T, 64, 12, WM_, WN_, TM_>(ARGS) : BY_STAGE(T, 64, WM_, WN_, TM_))
-#define BY_GEO(T, B) (geo == 2 ? BY_STAGE(T, B, 2, 2, 4) : geo == 4 ? BY_STAGE(T, B, 4, 2, 4) : geo == 8 ? BY_STAGE(T, B, 2, 4, 8) : BY_STAGE(T, B, 2, 2, 8))
-#define BY_GEO64(T) (geo == 2 ? BY_STAGE(T, 64, 2, 2, 4) : geo == 4 ? BY_STAGE(T, 64, 4, 2, 4) : geo == 8 ? BY_STAGE64(T, 2, 4, 8) : BY_STAGE64(T, 2, 2, 8))
-    int rc;
-    if (taps == 9) rc = (bk == 64) ? BY_GEO64(9) : BY_GEO(9, 32);
-    else rc = (bk == 64) ? BY_GEO64(1) : BY_GEO(1, 32);
-#undef BY_GEO64
-#undef BY_GEO
-#undef BY_STAGE64
-#undef BY_STAGE
-#undef ARGS
-    if (rc) return rc;
-    if (splits > 1) {
-        return splitk_reduce(partial, splits, M, Cout, bias, residual, Y, fuse_sk ? gn_part : nullptr, H * W, s);
-    }
-    PD_LAUNCH_CHECK();
-    return PDHIP_OK;
+    if (splitk_ws == nullptr) splitk_ws_floats = 0;
+    ConvNeeds nd;
+    nd.two_source = X2 != nullptr; nd.in_up = in_up != 0; nd.apply = apply_table != nullptr; nd.want_gn = gn_part != nullptr;
+    const ConvPlan p = conv_plan(N, H, W, Cin, Cout, Cout_pad, taps, nd, splitk_ws_floats);
+    PD_REQUIRE(!nd.in_up || p.takes_in_up, "conv_igemm: an up-sampled input needs a layer the halo-resident kernel takes");
+    PD_REQUIRE(res_up == 0 || p.takes_res_up, "conv_igemm: an up-sampled residual needs a layer the halo-resident kernel (unsplit), k_conv_ht or k_conv_sk takes");
+    PD_REQUIRE(!nd.apply || p.takes_apply, "conv_igemm: an input transform needs a layer the halo-resident kernel takes");
+    const ConvArgs a{X, X2, Cin1, Wt, bias, residual, res_up, apply_table, nullptr, nullptr, nullptr, 0, Y, zero_page, splitk_ws, splitk_ws_floats, gn_part};
+    return conv_launch(p, a, s, gn_fused);
 }
 
 // ---- 3x3 conv of a nearest-x2 up-sampled image as four 2x2 phase convs over the half-resolution image: 4/9 of the MACs.

@@ -18,17 +18,18 @@ using namespace pdnn;
 namespace {
 
 struct ConvW { half_t* w = nullptr; float* b = nullptr; int cin = 0, cout = 0, cout_pad = 0, taps = 0; bool have_w = false, have_b = false;
-               half_t* wf = nullptr; half_t* wph = nullptr; };   // wf: fragment-major copy for the row-resident kernel (nn_conv_rr.hip), the 3x3 convs of the <= 64^2 levels; packed at load time   // wph: phase weights [4][cout_pad][4 cin] of an up-ResBlock's in_layers conv (conv_up2_phase), packed at load time
+               half_t* wf = nullptr; half_t* wph = nullptr; bool has_wf = false, has_wph = false; };   // has_*: fixed at graph build, what routing asks; allocation follows them   // wf: fragment-major copy for the row-resident kernel (nn_conv_rr.hip), the 3x3 convs of the <= 64^2 levels; packed at load time   // wph: phase weights [4][cout_pad][4 cin] of an up-ResBlock's in_layers conv (conv_up2_phase), packed at load time
 struct NormW { float* g = nullptr; float* b = nullptr; int c = 0; bool have_g = false, have_b = false; };
 struct ResB { std::string name; int cin, cout, mode; NormW n1, n2; ConvW c1, c2, skip; long long emb_off; bool has_skip; bool have_ew = false, have_eb = false;
-              half_t* c2s_w = nullptr; float* c2s_b = nullptr; bool c2s_ready = false; half_t* c2s_wf = nullptr; int hw = 0; };   // hw: resolution the block's convs run at   // conv2 with the skip 1x1 appended to its K loop (conv_sk_skip), built by pdhip_unet_load_tensor once its four sources are loaded
+              half_t* c2s_w = nullptr; float* c2s_b = nullptr; bool c2s_ready = false; half_t* c2s_wf = nullptr; int hw = 0; bool has_c2s = false, has_c2s_wf = false; };   // hw: resolution the block's convs run at   // conv2 with the skip 1x1 appended to its K loop (conv_sk_skip), built by pdhip_unet_load_tensor once its four sources are loaded
 struct AttB { std::string name; int c; NormW n; ConvW qkv, proj; };
 struct Block { int kind; int idx; };          // 0 conv_in, 1 res, 2 attn
 
 // gn_part: octet partial sums fused into the producing conv's epilogue ([N][chunks][C/8][2]); for a channel concat the
 // second source's partials are gn_partB (first Ca channels come from gn_part)
 struct Act { half_t* p; int C, H, W; const float* gn_part = nullptr; int gn_chunks = 0; const float* gn_partB = nullptr; int Ca = 0; int gn_chunksB = 0;
-             half_t* p2 = nullptr; };   // p2: virtual channel concat [p (Ca channels) | p2 (C - Ca channels)], never materialised
+             half_t* p2 = nullptr;      // p2: virtual channel concat [p (Ca channels) | p2 (C - Ca channels)], never materialised
+             int row = -1, rowB = -1; };   // route table only: the rows of the convs that produced p / p2
 
 }  // namespace
 // tuning / test hook (pdhip_debug_set_fuse_gn).  Default 0 = stand-alone GroupNorm-apply passes: MEASURED faster.  The in-conv
@@ -60,7 +61,7 @@ namespace pdnn { thread_local int g_fold_finalize = 8; thread_local int g_fold_f
 namespace pdnn { thread_local int g_fuse_skip = 1; thread_local int g_fuse_skip_min_tiles = 1; }
 // tuning / test hook (pdhip_debug_set_up_phase): the in_layers conv of an up-ResBlock, conv3x3(nearest_x2(h)), as four 2x2 phase convs over the
 // half-resolution h with the coinciding taps summed in the weights (4/9 of the MACs; k_conv_igemm<4>).  0 = never, 1 (default) = where it
-// measured faster than the 9-tap route (up_phase_routes below), 2 = every eligible layer.  Independent of g_fold_resample.
+// measured faster than the 9-tap route (wish_up_phase below), 2 = every eligible layer.  Independent of g_fold_resample.
 namespace pdnn { thread_local int g_up_phase = 1; }
 namespace {
 struct Prof { std::vector<hipEvent_t> ev; std::vector<uint8_t> cls; size_t used = 0; double flops[2] = {0, 0}; bool on = false;
@@ -114,11 +115,10 @@ int dalloc(pdhip_unet* u, T** p, size_t count) {
 }
 #define PD_TRY(expr) do { int rc_ = (expr); if (rc_ != PDHIP_OK) return rc_; } while (0)
 
-int alloc_conv(pdhip_unet* u, ConvW& c, int cin, int cout, int taps) {
-    c.cin = cin; c.cout = cout; c.taps = taps; c.cout_pad = ((cout + 127) / 128) * 128;
-    PD_TRY(dalloc(u, &c.w, (size_t)c.cout_pad * taps * cin));
-    PD_HIP(hipMemset(c.w, 0, (size_t)c.cout_pad * taps * cin * sizeof(half_t)));
-    PD_TRY(dalloc(u, &c.b, (size_t)cout));
+int alloc_conv(pdhip_unet* u, ConvW& c) {      // (shape: build_graph)
+    PD_TRY(dalloc(u, &c.w, (size_t)c.cout_pad * c.taps * c.cin));
+    PD_HIP(hipMemset(c.w, 0, (size_t)c.cout_pad * c.taps * c.cin * sizeof(half_t)));
+    PD_TRY(dalloc(u, &c.b, (size_t)c.cout));
     return PDHIP_OK;
 }
 int alloc_norm(pdhip_unet* u, NormW& n, int c) {
@@ -178,11 +178,14 @@ half_t* arena_take(pdhip_unet* u, size_t halfs) {
     return p;
 }
 
-struct Ctx { pdhip_unet* u; int N; hipStream_t s; bool dry; const float* film_base; long long film_stride; };
+struct Act;
+struct Table { std::vector<std::string> name, line; };      // pdhip_unet_route_table: one line per conv of a forward
+struct Ctx { pdhip_unet* u; int N; hipStream_t s; bool dry; const float* film_base; long long film_stride; Table* table;
+             bool go() const { return !dry && table == nullptr; } };   // go: a real forward; dry: the sizing pass; table: planning only (real routing, no launches)
 
 int prof_begin(Ctx& c, double flops, int cls = 0) {
     Prof& p = c.u->prof;
-    if (!p.on || !p.armed || c.dry) return PDHIP_OK;
+    if (!p.on || !p.armed || !c.go()) return PDHIP_OK;
     if (p.used + 2 > p.ev.size()) {
         for (int i = 0; i < 256; ++i) { hipEvent_t e; PD_HIP(hipEventCreate(&e)); p.ev.push_back(e); p.cls.push_back(0); }
     }
@@ -193,43 +196,86 @@ int prof_begin(Ctx& c, double flops, int cls = 0) {
 }
 int prof_end(Ctx& c) {
     Prof& p = c.u->prof;
-    if (!p.on || !p.armed || c.dry) return PDHIP_OK;
+    if (!p.on || !p.armed || !c.go()) return PDHIP_OK;
     PD_HIP(hipEventRecord(p.ev[p.used + 1], c.s));
     p.used += 2;
     return PDHIP_OK;
 }
 
-int run_conv(Ctx& c, const Act& x, const ConvW& w, const half_t* residual, Act* out, bool want_gn = false,
-             const float* apply_table = nullptr, int res_up = 0, int in_up = 0) {
-    // in_up: x is the half-resolution input, the conv runs on its nearest x2 (out has twice x's height / width)
-    const int cH = x.H << in_up, cW = x.W << in_up;
-    *out = Act{nullptr, w.cout, cH, cW};
-    out->p = arena_take(c.u, (size_t)c.N * cH * cW * w.cout);
-    // octet partials: [N][chunks][cout/8][2] floats, chunks <= HW/16 (split-K reduce) -- sized for the finest chunking
-    float* part = want_gn ? reinterpret_cast<float*>(arena_take(c.u, (size_t)c.N * ((cH * cW + 15) / 16) * (w.cout / 8) * 2 * 2)) : nullptr;
-    if (c.dry) return PDHIP_OK;
-    PD_REQUIRE(w.have_w && w.have_b, "unet: conv weights not loaded");
-    // profile hook (bench.py roofline): the dominant kernel only -- the halo-resident 3x3 conv
-    const bool prof = x.p2 == nullptr && conv_uses_halo(c.N, cH, cW, w.cin, w.cout, w.cout_pad, w.taps, c.u->splitk_floats) &&
-                      conv3x3_halo_splits(c.N, cH, cW, w.cin, w.cout, w.cout_pad, c.u->splitk_floats) == 1;
-    if (prof) PD_TRY(prof_begin(c, 2.0 * c.N * cH * cW * (double)w.cout * 9.0 * w.cin));
-    // small batch, <= 64^2: the row-resident kernel (register-resident fragment-major weights, halo staged once per channel chunk)
-    if (w.wf != nullptr && w.taps == 9 && x.p2 == nullptr && apply_table == nullptr && in_up == 0 && !prof) {
-        const RrPlan pl = conv_rr_plan(c.N, cH, cW, w.cin, w.cout, 9, 0, c.u->splitk_floats);
-        if (pl.variant != 0) {
-            const RrIn in{x.p, nullptr, w.cin, w.cin, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 1e-5f};
-            int chunks = 0;
-            PD_TRY(conv_rr(pl, in, nullptr, 9, w.wf, w.b, residual, res_up, out->p, c.N, cH, cW, w.cout, c.u->splitk_ws, c.u->splitk_floats, part, &chunks, c.s));
-            if (part != nullptr && chunks > 0) { out->gn_part = part; out->gn_chunks = chunks; out->Ca = w.cout; }
-            return PDHIP_OK;
-        }
+// room for a conv's octet partials: [N][chunks][cout/8][2] floats, chunks <= HW/16 (split-K reduce) -- sized for the finest chunking
+float* take_parts(Ctx& c, int H, int W, int cout) {
+    return reinterpret_cast<float*>(arena_take(c.u, (size_t)c.N * ((H * W + 15) / 16) * (cout / 8) * 2 * 2));
+}
+void adopt_parts(Act* out, float* part, int chunks) {
+    if (part != nullptr && chunks > 0) { out->gn_part = part; out->gn_chunks = chunks; out->Ca = out->C; }
+}
+
+// what a conv reads besides its plan: x (raw when the plan absorbs the GroupNorm), the residual, and the sources of what the plan absorbs
+struct ConvIn { const Act* x; const half_t* residual = nullptr; int res_up = 0; const float* apply_table = nullptr; const RrIn* rr_in = nullptr;
+                const Act* skip_src = nullptr; const ResB* skip_w = nullptr;      // takes_skip: the block input and the block holding the fused weights
+                const Act* parts_of = nullptr; const char* note = nullptr; };     // route table only: the tensor whose partials this conv's input pass depends on
+
+void table_row(Ctx& c, const std::string& name, const ConvPlan& p, const ConvIn& in, Act* out) {
+    char detail[64];
+    switch (p.kernel) {
+    case CONV_HALO: case CONV_IGEMM: snprintf(detail, sizeof detail, "splits=%d", p.splits); break;
+    case CONV_HT: snprintf(detail, sizeof detail, "slabs=%d", p.slabs); break;
+    case CONV_RR: snprintf(detail, sizeof detail, "variant=%d,slabs=%d", p.rr.variant, p.rr.S0); break;
+    case CONV_SK: snprintf(detail, sizeof detail, "tile=%dx%d,splits=%d", p.sk.bm, p.sk.bn, p.sk.splits); break;
+    default: snprintf(detail, sizeof detail, "-"); break;
     }
-    int fused = 0;
-    int rc = conv_igemm(x.p, w.w, w.b, residual, out->p, c.N, cH, cW, w.cin, w.cout, w.cout_pad, w.taps, c.u->zero_page, c.s,
-                        c.u->splitk_ws, c.u->splitk_floats, part, &fused, x.p2, x.p2 ? x.Ca : 0, apply_table, res_up, in_up);
-    if (fused) { out->gn_part = part; out->gn_chunks = fused; out->Ca = w.cout; }
-    if (prof) PD_TRY(prof_end(c));
-    return rc;
+    std::string folds;
+    auto add = [&](const std::string& f) { folds += (folds.empty() ? "" : ",") + f; };
+    if (in.note) add(in.note);
+    if (in.x->p2) add("two_source");
+    if (p.takes_apply) add("apply");
+    if (p.takes_in_gn) add("in_gn");
+    if (p.takes_in_up) add("in_up");
+    if (in.res_up) add("res_up");
+    if (p.takes_skip) add("skip");
+    if (in.parts_of) {
+        const Act& a = *in.parts_of;
+        add("parts<-" + (a.gn_part && a.row >= 0 ? c.table->name[a.row] : std::string("?")) +
+            (a.p2 ? "+" + (a.gn_partB && a.rowB >= 0 ? c.table->name[a.rowB] : std::string("?")) : std::string()));
+    }
+    char line[512];
+    snprintf(line, sizeof line, "%s %dx%d %d->%d %s %s gn=%d %s", name.c_str(), p.H, p.W, p.Cin, p.Cout, conv_kernel_name(p.kernel), detail, p.gn_chunks,
+             folds.empty() ? "-" : folds.c_str());
+    out->row = (int)c.table->line.size();
+    c.table->name.push_back(name);
+    c.table->line.push_back(line);
+}
+
+// one conv, as planned: output (+ partials) from the arena, the launch, and the plan / launcher agreement on the partials left behind
+int run_conv(Ctx& c, const std::string& name, const ConvPlan& p, const ConvW& w, const ConvIn& in, Act* out) {
+    *out = Act{nullptr, p.Cout, p.H, p.W};
+    out->p = arena_take(c.u, (size_t)c.N * p.H * p.W * p.Cout);
+    float* part = p.want_gn ? take_parts(c, p.H, p.W, p.Cout) : nullptr;
+    if (c.table) { table_row(c, name, p, in, out); adopt_parts(out, part, p.gn_chunks); }
+    if (!c.go()) return PDHIP_OK;
+    PD_REQUIRE(w.have_w && w.have_b, "unet: weights of %s not loaded", name.c_str());
+    const ResB* fs = p.takes_skip ? in.skip_w : nullptr;
+    PD_REQUIRE(fs == nullptr || (fs->skip.have_w && fs->skip.have_b && fs->c2s_ready), "unet: fused conv2 + skip weights of %s were not built at load time", name.c_str());
+    const half_t* wt = fs ? (p.kernel == CONV_RR ? fs->c2s_wf : fs->c2s_w) : p.kernel == CONV_RR ? w.wf : p.kernel == CONV_UP_PHASE ? w.wph : w.w;
+    const Act& x = *in.x;
+    const Act* xs = p.takes_skip ? in.skip_src : nullptr;
+    const ConvArgs a{x.p, x.p2, x.p2 ? x.Ca : 0, wt, fs ? fs->c2s_b : w.b, in.residual, in.res_up, in.apply_table, in.rr_in,
+                     xs ? xs->p : nullptr, xs ? xs->p2 : nullptr, xs && xs->p2 ? xs->Ca : 0, out->p, c.u->zero_page, c.u->splitk_ws, c.u->splitk_floats, part};
+    // profile hook (bench.py roofline): the dominant kernel only -- the halo-resident 3x3 conv, unsplit
+    const bool booked = p.kernel == CONV_HALO && p.splits == 1;
+    if (booked) PD_TRY(prof_begin(c, 2.0 * c.N * p.H * p.W * (double)p.Cout * 9.0 * p.Cin));
+    int chunks = 0;
+    PD_TRY(conv_launch(p, a, c.s, &chunks));
+    if (booked) PD_TRY(prof_end(c));
+    PD_REQUIRE(chunks == p.gn_chunks, "unet: %s: planned for %d partial chunks per image, the %s launcher left %d", name.c_str(), p.gn_chunks,
+               conv_kernel_name(p.kernel), chunks);
+    adopt_parts(out, part, chunks);
+    return PDHIP_OK;
+}
+ConvPlan plan_conv(const Ctx& c, const Act& x, const ConvW& w, bool want_gn) {      // a conv outside the ResBlocks: nothing to absorb
+    ConvNeeds nd;
+    nd.two_source = x.p2 != nullptr; nd.want_gn = want_gn; nd.have_wf = w.has_wf;
+    return conv_plan(c.N, x.H, x.W, w.cin, w.cout, w.cout_pad, w.taps, nd, c.u->splitk_floats);
 }
 
 // GroupNorm statistics of x: from the fused conv-epilogue partials when available, else a pass over the tensor
@@ -246,7 +292,7 @@ int run_gn(Ctx& c, const Act& x, const NormW& n, const float* film, long long fi
     out->H = resample == 1 ? x.H / 2 : (resample == 2 ? x.H * 2 : x.H);
     out->W = resample == 1 ? x.W / 2 : (resample == 2 ? x.W * 2 : x.W);
     out->p = arena_take(c.u, (size_t)c.N * out->H * out->W * x.C);
-    if (c.dry) return PDHIP_OK;
+    if (!c.go()) return PDHIP_OK;
     PD_REQUIRE(n.have_g && n.have_b, "unet: norm weights not loaded");
 #ifdef PD_LAB_SKIP_GN                                       // (lab, timing only -- WRONG results: what the small-level GroupNorm-apply launches cost)
     if (resample == 0 && x.p2 == nullptr && x.W <= 128 && silu) { out->p = x.p; return PDHIP_OK; }
@@ -264,180 +310,155 @@ int run_gn(Ctx& c, const Act& x, const NormW& n, const float* film, long long fi
                     raw_pool);
 }
 
-// GroupNorm (+ FiLM) + SiLU of x folded into the conv that consumes it (the halo-resident kernel transforms its input tile in LDS,
-// nn_conv_halo.hip APPLY): statistics -> (A, B) table -> conv on the RAW tensor.  The stand-alone apply pass and its output
-// tensor disappear.  Taken for the 3x3 convs the halo kernel serves, single-source input, no resampling in between.
-bool can_fuse_gn(const Ctx& c, const Act& x, const ConvW& w) {
-    if (c.dry) return false;                     // the sizing pass takes the two-pass form: it needs the larger arena
-    if (g_fuse_gn == 0 || x.p2 != nullptr || w.taps != 9 || (x.W == 256 && x.H % 4 != 0)) return false;
-    return conv_uses_halo(c.N, x.H, x.W, w.cin, w.cout, w.cout_pad, w.taps, c.u->splitk_floats);
-}
-int run_gn_conv(Ctx& c, const Act& x, const NormW& n, const float* film, long long film_stride, const ConvW& w,
-                const half_t* residual, Act* out, int res_up = 0) {
-    if (!c.dry) {
-        PD_REQUIRE(n.have_g && n.have_b, "unet: norm weights not loaded");
-        PD_TRY(run_gn_stats(c, x));
-        PD_TRY(gn_table(c.u->stats, n.g, n.b, film, film_stride, c.N, x.C, c.u->ap_table, c.s));
+// GroupNorm (+ FiLM) + SiLU of x, then the conv, in the form the plan took:
+//   takes_apply  statistics -> (A, B) table -> the halo-resident kernel transforms its input tile of the RAW tensor in LDS (nn_conv_halo.hip APPLY)
+//   takes_in_gn  the row-resident kernel normalises the RAW tensor while staging, from the producer's octet partials (nn_conv_rr.hip; see g_rr_gn)
+//   neither      a stand-alone GroupNorm-apply pass (with the block's resampling, and AvgPool2d(2) of the raw input into raw_pool), then the conv
+// In the first two the stand-alone pass and its output tensor disappear; all three give the same bits.
+int run_gn_then_conv(Ctx& c, const std::string& name, const ConvPlan& p, const Act& x, const NormW& n, const float* film, long long film_stride,
+                     int resample, half_t* raw_pool, const ConvW& w, ConvIn in, Act* out) {
+    if (p.takes_apply) {
+        if (c.go()) {
+            PD_REQUIRE(n.have_g && n.have_b, "unet: norm weights not loaded");
+            PD_TRY(run_gn_stats(c, x));
+            PD_TRY(gn_table(c.u->stats, n.g, n.b, film, film_stride, c.N, x.C, c.u->ap_table, c.s));
+            in.apply_table = c.u->ap_table;
+        }
+        in.x = &x;
+        return run_conv(c, name, p, w, in, out);
     }
-    return run_conv(c, x, w, residual, out, true, c.dry ? nullptr : c.u->ap_table, res_up);
+    if (p.takes_in_gn) {
+        if (c.go()) PD_REQUIRE(n.have_g && n.have_b, "unet: norm weights not loaded");
+        const RrIn rr_in{x.p, nullptr, x.C, x.C, 2, n.g, n.b, film, film_stride, x.gn_part, nullptr, x.gn_chunks, 0, 1e-5f};
+        in.x = &x; in.rr_in = &rr_in; in.parts_of = &x;
+        return run_conv(c, name, p, w, in, out);
+    }
+    Act h;
+    PD_TRY(run_gn(c, x, n, film, film_stride, 1, resample, &h, raw_pool));
+    in.x = &h;
+    if (x.p2 != nullptr) in.parts_of = &x;
+    return run_conv(c, name, p, w, in, out);
 }
 
-// GroupNorm (+ FiLM) + SiLU of x applied INSIDE the row-resident conv that consumes it (nn_conv_rr.hip; bit-identical to run_gn + run_conv on the same
-// kernel): taken where it measured a gain -- see g_rr_gn.  Returns false (nothing launched) when the layer is not one of those.
-bool rr_gn_ok(const Ctx& c, const Act& x, const ConvW& w, int H, int W) {
-    if (c.dry || g_rr_gn <= 0 || W > g_rr_gn || w.wf == nullptr || w.taps != 9 || x.p2 != nullptr || x.gn_part == nullptr || x.gn_partB != nullptr ||
-        ((x.C / 32) % 8) != 0 || w.cin > 1024 || x.C != w.cin) return false;
+// ---- the plan of one ResBlock: pure host code, decided before anything is taken from the arena or launched
+struct ResPlan {
+    bool fuse_skip = false;        // in_layers' GroupNorm-apply and the skip 1x1 read the same (virtual concat) input: one pass (k_gn_skip)
+    bool fold_down = false;        // x branch of a down block: AvgPool2d(2)(x) is the second output of the GroupNorm-apply pass
+    bool fold_up = false;          // x branch of an up block: nearest x2 is index arithmetic in conv2's residual read (c2.takes_res_up)
+    bool skip_conv = false;        // the skip 1x1 runs as a launch of its own (plan: skip)
+    ConvPlan c1, c2, skip;         // c1: takes_apply / takes_in_gn / CONV_UP_PHASE / takes_in_up say its form; c2: takes_skip / takes_apply / takes_in_gn
+};
+// the row-resident kernel's in-staging GroupNorm is wished for where it measured a gain (g_rr_gn) and the input carries what it reads
+bool wish_in_gn(const Act& x, const ConvW& w, int W) {
+    if (g_rr_gn <= 0 || W > g_rr_gn || x.p2 != nullptr || x.gn_part == nullptr || x.gn_partB != nullptr || ((x.C / 32) % 8) != 0 || w.cin > 1024 ||
+        x.C != w.cin) return false;
     const int pps = std::max(1, 256 / (x.C >> 3));
-    if ((x.gn_chunks + pps - 1) / pps > PD_RR_MAX_PART_LOADS) return false;
-    return conv_rr_plan(c.N, H, W, w.cin, w.cout, 9, 0, c.u->splitk_floats, true).variant != 0;
+    return (x.gn_chunks + pps - 1) / pps <= PD_RR_MAX_PART_LOADS;
 }
-int run_rr_gn_conv(Ctx& c, const Act& x, const NormW& n, const float* film, long long film_stride, const ConvW& w, const half_t* residual, int res_up,
-                   Act* out) {
-    *out = Act{nullptr, w.cout, x.H, x.W};
-    out->p = arena_take(c.u, (size_t)c.N * x.H * x.W * w.cout);
-    float* part = reinterpret_cast<float*>(arena_take(c.u, (size_t)c.N * ((x.H * x.W + 15) / 16) * (w.cout / 8) * 2 * 2));
-    PD_REQUIRE(n.have_g && n.have_b && w.have_w && w.have_b, "unet: norm / conv weights not loaded");
-    const RrPlan pl = conv_rr_plan(c.N, x.H, x.W, w.cin, w.cout, 9, 0, c.u->splitk_floats, true);
-    const RrIn in{x.p, nullptr, x.C, x.C, 2, n.g, n.b, film, film_stride, x.gn_part, nullptr, x.gn_chunks, 0, 1e-5f};
-    int chunks = 0;
-    PD_TRY(conv_rr(pl, in, nullptr, 9, w.wf, w.b, residual, res_up, out->p, c.N, x.H, x.W, w.cout, c.u->splitk_ws, c.u->splitk_floats, part, &chunks, c.s));
-    if (chunks > 0) { out->gn_part = part; out->gn_chunks = chunks; out->Ca = w.cout; }
-    return PDHIP_OK;
-}
-
 // the up-ResBlock in_layers conv on the phase kernel?  (H, W: the half-resolution input)
-bool up_phase_routes(const Ctx& c, const ResB& rb, int H, int W) {
-    if (c.dry || g_up_phase == 0 || rb.mode != 2 || rb.c1.wph == nullptr || (H * W) % 256 != 0 ||
-        !conv_up2_phase_eligible(c.N, H, W, rb.c1.cin, rb.c1.cout, rb.c1.cout_pad)) return false;
+bool wish_up_phase(int N, const ResB& rb, int H, int W) {
+    if (g_up_phase == 0 || rb.mode != 2 || !rb.c1.has_wph || (H * W) % 256 != 0 ||
+        !conv_up2_phase_eligible(N, H, W, rb.c1.cin, rb.c1.cout, rb.c1.cout_pad)) return false;
     if (g_up_phase == 2) return true;
     // automatic, by measurement (profiles/up_phase_layers.txt, batch 1 ... 32 x the five up blocks): from 128 tiles (4 phases x 256-pixel tiles x
     // channel tiles) on the phase conv beat the 9-tap route in every case (1.19x at 128 tiles ... 1.94x), at 64 tiles and below it lost (0.23 ... 0.92x:
     // 256 x 256 tiles on a quarter of the CUs)
-    const long long tiles = (long long)c.N * H * W / 256 * 4 * (rb.c1.cout_pad / (rb.c1.cout_pad % 256 == 0 ? 256 : 128));
+    const long long tiles = (long long)N * H * W / 256 * 4 * (rb.c1.cout_pad / (rb.c1.cout_pad % 256 == 0 ? 256 : 128));
     return tiles >= 128;
 }
-int run_conv_up_phase(Ctx& c, const Act& x, const ConvW& w, Act* out) {      // (not booked by the --full profile hook: 4 Cin MACs per output, not 9 Cin)
-    *out = Act{nullptr, w.cout, 2 * x.H, 2 * x.W};
-    out->p = arena_take(c.u, (size_t)c.N * 4 * x.H * x.W * w.cout);
-    float* part = reinterpret_cast<float*>(arena_take(c.u, (size_t)c.N * ((4 * x.H * x.W + 15) / 16) * (w.cout / 8) * 2 * 2));
-    PD_REQUIRE(w.have_w && w.have_b, "unet: conv weights not loaded");
-    int fused = 0;
-    PD_TRY(conv_up2_phase(x.p, w.wph, w.b, out->p, c.N, x.H, x.W, w.cin, w.cout, w.cout_pad, c.u->zero_page, c.s, part, &fused));
-    if (fused) { out->gn_part = part; out->gn_chunks = fused; out->Ca = w.cout; }
-    return PDHIP_OK;
+// conservative = the sizing pass: every tensor a routing could need is materialised (two-pass GroupNorm, resampled x branch, skip tensor), since
+// the hooks and the batch of a later forward may route differently; it assumes the input carries partials (k_gn_skip's two outputs are the larger form)
+ResPlan plan_res(int N, size_t ws_floats, bool conservative, const Act& x, const ResB& rb) {
+    ResPlan r;
+    const int Ho = rb.mode == 1 ? x.H / 2 : (rb.mode == 2 ? x.H * 2 : x.H), Wo = rb.mode == 1 ? x.W / 2 : (rb.mode == 2 ? x.W * 2 : x.W);
+    const bool lean = !conservative;
+    // x branch of an up / down block (unet.py:190-195, 237-242: h and x go through the same Upsample / Downsample)
+    const bool fold = g_fold_resample != 0 && lean && x.p2 == nullptr && !rb.has_skip;
+    r.fold_down = fold && rb.mode == 1;
+    r.fuse_skip = rb.has_skip && rb.mode == 0 && g_fuse_skip != 0 && rb.skip.taps == 1 && x.C == rb.skip.cin &&
+                  gn_skip_eligible(N, x.H * x.W, x.p2 ? x.Ca : x.C, x.C, rb.skip.cout, rb.skip.cout_pad) &&
+                  (g_fuse_skip == 2 || (long long)N * x.H * x.W / 128 >= g_fuse_skip_min_tiles) &&
+                  (conservative || (x.gn_part != nullptr && ((x.C / 32) % 8) == 0));
+    ConvNeeds n1;
+    n1.want_gn = true; n1.have_wf = rb.c1.has_wf;
+    if (lean && !r.fuse_skip && rb.mode == 0 && x.p2 == nullptr) { n1.apply = g_fuse_gn != 0; n1.in_gn = wish_in_gn(x, rb.c1, x.W); }
+    n1.in_up = fold && rb.mode == 2;       // nearest x2 of the normalised input: index arithmetic in conv1's halo staging, the GroupNorm pass stays at half resolution
+    if (lean && x.p2 == nullptr && !rb.has_skip && wish_up_phase(N, rb, x.H, x.W))
+        r.c1 = conv_up2_phase_plan(N, Ho, Wo, rb.c1.cin, rb.c1.cout, rb.c1.cout_pad, true);   // GroupNorm at half resolution, the x2 lives in the weights
+    else
+        r.c1 = conv_plan(N, Ho, Wo, rb.c1.cin, rb.c1.cout, rb.c1.cout_pad, 9, n1, ws_floats);
+    // conv2 reads h1 = conv1's output; small-M layers: the skip 1x1 rides in its K loop (no launch of its own, no skip tensor, no residual read)
+    Act h1{nullptr, rb.cout, Ho, Wo};
+    if (r.c1.gn_chunks > 0) { h1.gn_part = x.gn_part ? x.gn_part : reinterpret_cast<const float*>(&r); h1.gn_chunks = r.c1.gn_chunks; h1.Ca = rb.cout; }
+    ConvNeeds n2;
+    n2.want_gn = true; n2.have_wf = rb.c2.has_wf;
+    if (lean) { n2.apply = g_fuse_gn != 0; n2.in_gn = wish_in_gn(h1, rb.c2, Wo); }
+    if (lean && rb.has_skip && !r.fuse_skip && g_fold_skip != 0 && rb.mode == 0 && rb.has_c2s && rb.skip.taps == 1 &&
+        (x.p2 == nullptr || (x.Ca % 64 == 0 && (x.C - x.Ca) % 64 == 0))) {
+        n2.skip_cs = rb.skip.cin;
+        n2.have_wf_skip = rb.has_c2s_wf && (x.p2 == nullptr || (x.Ca % 128 == 0 && (x.C - x.Ca) % 128 == 0));
+    }
+    r.c2 = conv_plan(N, Ho, Wo, rb.c2.cin, rb.c2.cout, rb.c2.cout_pad, 9, n2, ws_floats);
+    r.fold_up = fold && rb.mode == 2 && r.c2.takes_res_up;
+    r.skip_conv = rb.has_skip && !r.fuse_skip && !r.c2.takes_skip;
+    if (r.skip_conv) {
+        ConvNeeds ns;
+        ns.two_source = x.p2 != nullptr;
+        r.skip = conv_plan(N, Ho, Wo, rb.skip.cin, rb.skip.cout, rb.skip.cout_pad, rb.skip.taps, ns, ws_floats);
+    }
+    return r;
 }
 
 int run_res(Ctx& c, const Act& x, ResB& rb, Act* out) {
-    Act h0, h1, h2, xr = x, sk;
-    const float* film = c.dry ? nullptr : c.film_base + rb.emb_off;
-    if (!c.dry) PD_REQUIRE(rb.have_ew && rb.have_eb, "unet: emb_layers of %s not loaded", rb.name.c_str());
-    const int Ho = rb.mode == 1 ? x.H / 2 : (rb.mode == 2 ? x.H * 2 : x.H), Wo = rb.mode == 1 ? x.W / 2 : (rb.mode == 2 ? x.W * 2 : x.W);
-    // x branch of an up / down block (unet.py:190-195, 237-242: h and x go through the same Upsample / Downsample)
-    const bool fold = g_fold_resample != 0 && !c.dry && x.p2 == nullptr && !rb.has_skip;
-    const bool fold_down = fold && rb.mode == 1;                     // AvgPool2d(2)(x): second output of the GroupNorm-apply pass
-    const bool fold_up = fold && rb.mode == 2 &&
-                         ((Wo <= 256 && (Wo != 256 || Ho % 4 == 0) &&      // nearest x2: index arithmetic in conv2's
-                           conv_uses_halo(c.N, Ho, Wo, rb.c2.cin, rb.c2.cout, rb.c2.cout_pad, 9, c.u->splitk_floats) &&   // residual read
-                           conv3x3_halo_splits(c.N, Ho, Wo, rb.c2.cin, rb.c2.cout, rb.c2.cout_pad, c.u->splitk_floats) == 1) ||
-                          (g_fuse_gn == 0 && conv_routes_small(c.N, Ho, Wo, rb.c2.cin, rb.c2.cout, rb.c2.cout_pad, 9, c.u->splitk_floats)) ||   // (round 4 / 6: k_conv_sk's and k_conv_ht's epilogues too)
-                          (g_fuse_gn == 0 && rb.c2.wf != nullptr && conv_rr_plan(c.N, Ho, Wo, rb.c2.cin, rb.c2.cout, 9, 0, c.u->splitk_floats).variant != 0));   // (round 6: k_conv_rr's)
+    const ResPlan r = plan_res(c.N, c.u->splitk_floats, c.dry, x, rb);
+    Act h1, xr = x, sk;
+    const float* film = c.go() ? c.film_base + rb.emb_off : nullptr;
+    if (c.go()) PD_REQUIRE(rb.have_ew && rb.have_eb, "unet: emb_layers of %s not loaded", rb.name.c_str());
     if (rb.mode != 0) {
-        xr.H = Ho; xr.W = Wo;
-        xr.p = arena_take(c.u, (size_t)c.N * Ho * Wo * x.C);     // (the sizing pass always reserves it: routing may differ later)
+        xr.H = r.c2.H; xr.W = r.c2.W;
+        xr.p = arena_take(c.u, (size_t)c.N * xr.H * xr.W * x.C);     // (always reserved: the sizing pass cannot know the folds of a later forward)
     }
-    // nearest x2 of the normalised input: index arithmetic in conv1's halo staging, the GroupNorm pass stays at half resolution
-    const bool fold_in_up = fold && rb.mode == 2 && Wo <= 256 && (Wo != 256 || Ho % 4 == 0) &&
-                            conv_uses_halo(c.N, Ho, Wo, rb.c1.cin, rb.c1.cout, rb.c1.cout_pad, 9, c.u->splitk_floats);
-    // channel-changing block: in_layers' GroupNorm-apply and the skip 1x1 read the same (virtual concat) input -- one pass (k_gn_skip)
-    const bool fuse_skip = rb.has_skip && rb.mode == 0 && g_fuse_skip != 0 && rb.skip.taps == 1 && x.C == rb.skip.cin &&
-                           gn_skip_eligible(c.N, x.H * x.W, x.p2 ? x.Ca : x.C, x.C, rb.skip.cout, rb.skip.cout_pad) &&
-                           (g_fuse_skip == 2 || (long long)c.N * x.H * x.W / 128 >= g_fuse_skip_min_tiles) &&
-                           (c.dry || (x.gn_part != nullptr && ((x.C / 32) % 8) == 0));
-    if (fuse_skip) {
-        h0 = Act{nullptr, x.C, x.H, x.W};
+    const std::string n1 = rb.name + ".in_layers.2";
+    if (r.fuse_skip) {
+        Act h0{nullptr, x.C, x.H, x.W};
         h0.p = arena_take(c.u, (size_t)c.N * x.H * x.W * x.C);
         sk = Act{nullptr, rb.skip.cout, x.H, x.W};
         sk.p = arena_take(c.u, (size_t)c.N * x.H * x.W * rb.skip.cout);
-        if (!c.dry) {
+        if (c.go()) {
             PD_REQUIRE(rb.n1.have_g && rb.n1.have_b && rb.skip.have_w && rb.skip.have_b, "unet: norm / skip weights of %s not loaded", rb.name.c_str());
             PD_TRY(run_gn_stats(c, x));
             PD_TRY(gn_skip(x.p, x.p2, x.p2 ? x.Ca : x.C, x.C, c.u->stats, rb.n1.g, rb.n1.b, rb.skip.w, rb.skip.b, h0.p, sk.p, c.N, x.H * x.W, c.s));
         }
-        PD_TRY(run_conv(c, h0, rb.c1, nullptr, &h1, true));
-    } else if (rb.mode == 0 && can_fuse_gn(c, x, rb.c1)) {
-        PD_TRY(run_gn_conv(c, x, rb.n1, nullptr, 0, rb.c1, nullptr, &h1));
-    } else if (rb.mode == 0 && rr_gn_ok(c, x, rb.c1, x.H, x.W)) {
-        PD_TRY(run_rr_gn_conv(c, x, rb.n1, nullptr, 0, rb.c1, nullptr, 0, &h1));
-    } else if (x.p2 == nullptr && !rb.has_skip && up_phase_routes(c, rb, x.H, x.W)) {
-        PD_TRY(run_gn(c, x, rb.n1, nullptr, 0, 1, 0, &h0));                  // GroupNorm at half resolution, the x2 lives in the weights
-        PD_TRY(run_conv_up_phase(c, h0, rb.c1, &h1));
-    } else if (fold_in_up) {
-        PD_TRY(run_gn(c, x, rb.n1, nullptr, 0, 1, 0, &h0));
-        PD_TRY(run_conv(c, h0, rb.c1, nullptr, &h1, true, nullptr, 0, 1));
+        ConvIn in{&h0};
+        in.parts_of = &x; in.note = "gn_skip";
+        PD_TRY(run_conv(c, n1, r.c1, rb.c1, in, &h1));
     } else {
-        PD_TRY(run_gn(c, x, rb.n1, nullptr, 0, 1, rb.mode, &h0, fold_down ? xr.p : nullptr));
-        PD_TRY(run_conv(c, h0, rb.c1, nullptr, &h1, true));
+        const bool half_res = r.c1.kernel == CONV_UP_PHASE || r.c1.takes_in_up;       // the GroupNorm pass stays at the input's resolution
+        PD_TRY(run_gn_then_conv(c, n1, r.c1, x, rb.n1, nullptr, 0, half_res ? 0 : rb.mode, r.fold_down ? xr.p : nullptr, rb.c1, ConvIn{nullptr}, &h1));
     }
-    if (rb.mode != 0 && !c.dry && !fold_down && !fold_up) PD_TRY(resample2x(x.p, c.N, x.H, x.W, x.C, rb.mode, xr.p, c.s));
-    if (!fuse_skip) sk = fold_up ? x : xr;
-    // small-M layers: the skip 1x1 rides in conv2's K loop (k_conv_sk<10, ..>): no launch of its own, no skip tensor, no residual read
-    if (rb.has_skip && !fuse_skip && !c.dry && g_fold_skip != 0 && rb.mode == 0 && rb.c2s_w != nullptr && rb.skip.taps == 1 &&
-        (x.p2 == nullptr || (x.Ca % 64 == 0 && (x.C - x.Ca) % 64 == 0)) &&
-        !conv_uses_halo(c.N, h1.H, h1.W, rb.c2.cin, rb.c2.cout, rb.c2.cout_pad, 9, c.u->splitk_floats) && !can_fuse_gn(c, h1, rb.c2)) {
-        const RrPlan rp = rb.c2s_wf != nullptr && (x.p2 == nullptr || (x.Ca % 128 == 0 && (x.C - x.Ca) % 128 == 0))
-                              ? conv_rr_plan(c.N, h1.H, h1.W, rb.c2.cin, rb.cout, 9, rb.skip.cin, c.u->splitk_floats) : RrPlan{0, 0, 0, 0, 0, 0, 0};
-        if (rp.variant != 0) {                           // round 6: conv2 + skip 1x1 as slabs of one row-resident launch
-            PD_REQUIRE(rb.c2.have_w && rb.c2.have_b && rb.skip.have_w && rb.skip.have_b && rb.c2s_ready, "unet: conv2 / skip weights of %s not loaded", rb.name.c_str());
-            PD_TRY(run_gn(c, h1, rb.n2, film, c.film_stride, 1, 0, &h2));
-            *out = Act{nullptr, rb.cout, h1.H, h1.W};
-            out->p = arena_take(c.u, (size_t)c.N * h1.H * h1.W * rb.cout);
-            float* part = reinterpret_cast<float*>(arena_take(c.u, (size_t)c.N * ((h1.H * h1.W + 15) / 16) * (rb.cout / 8) * 2 * 2));
-            const RrIn in{h2.p, nullptr, rb.c2.cin, rb.c2.cin, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 1e-5f};
-            const RrIn sk_in{x.p, x.p2, x.C, x.p2 ? x.Ca : x.C, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 1e-5f};
-            int chunks = 0;
-            PD_TRY(conv_rr(rp, in, &sk_in, 9, rb.c2s_wf, rb.c2s_b, nullptr, 0, out->p, c.N, h1.H, h1.W, rb.cout, c.u->splitk_ws, c.u->splitk_floats, part, &chunks, c.s));
-            if (chunks > 0) { out->gn_part = part; out->gn_chunks = chunks; out->Ca = rb.cout; }
-            return PDHIP_OK;
-        }
-        const SkPlan pl = conv_sk_plan(c.N, h1.H, h1.W, rb.c2.cin, rb.c2.cout, rb.c2.cout_pad, 9, false, c.u->splitk_floats, rb.skip.cin);
-        if (pl.bm > 0) {
-            PD_REQUIRE(rb.c2.have_w && rb.c2.have_b && rb.skip.have_w && rb.skip.have_b, "unet: conv2 / skip weights of %s not loaded", rb.name.c_str());
-            PD_REQUIRE(rb.c2s_ready, "unet: fused conv2 + skip weights of %s were not built at load time", rb.name.c_str());
-            PD_TRY(run_gn(c, h1, rb.n2, film, c.film_stride, 1, 0, &h2));
-            *out = Act{nullptr, rb.cout, h1.H, h1.W};
-            out->p = arena_take(c.u, (size_t)c.N * h1.H * h1.W * rb.cout);
-            float* part = reinterpret_cast<float*>(arena_take(c.u, (size_t)c.N * ((h1.H * h1.W + 15) / 16) * (rb.cout / 8) * 2 * 2));
-            const long long hw = (long long)h1.H * h1.W;
-            float* gnp = (hw % pl.bm == 0 || pl.bm == 2 * hw) ? part : nullptr;
-            int fused = 0;
-            PD_TRY(conv_sk_skip(pl, h2.p, rb.c2s_w, rb.c2s_b, out->p, c.N, h1.H, h1.W, rb.c2.cin, rb.cout, rb.c2.cout_pad, x.p, x.p2,
-                                x.p2 ? x.Ca : x.C, x.C, c.u->zero_page, c.s, c.u->splitk_ws, c.u->splitk_floats, gnp, &fused));
-            if (fused) { out->gn_part = part; out->gn_chunks = fused; out->Ca = rb.cout; }
-            return PDHIP_OK;
-        }
-    }
-    if (rb.has_skip && !fuse_skip) PD_TRY(run_conv(c, xr, rb.skip, nullptr, &sk));
-    if (can_fuse_gn(c, h1, rb.c2)) return run_gn_conv(c, h1, rb.n2, film, c.film_stride, rb.c2, sk.p, out, fold_up ? 1 : 0);
-    if (rr_gn_ok(c, h1, rb.c2, h1.H, h1.W)) return run_rr_gn_conv(c, h1, rb.n2, film, c.film_stride, rb.c2, sk.p, fold_up ? 1 : 0, out);
-    PD_TRY(run_gn(c, h1, rb.n2, film, c.film_stride, 1, 0, &h2));
-    return run_conv(c, h2, rb.c2, sk.p, out, true, nullptr, fold_up ? 1 : 0);
+    if (rb.mode != 0 && c.go() && !r.fold_down && !r.fold_up) PD_TRY(resample2x(x.p, c.N, x.H, x.W, x.C, rb.mode, xr.p, c.s));
+    if (!r.fuse_skip) sk = r.fold_up ? x : xr;
+    if (r.skip_conv) PD_TRY(run_conv(c, rb.name + ".skip_connection", r.skip, rb.skip, ConvIn{&xr}, &sk));
+    ConvIn in2{nullptr, r.c2.takes_skip ? nullptr : sk.p, r.fold_up ? 1 : 0};
+    in2.skip_src = &x; in2.skip_w = &rb;
+    return run_gn_then_conv(c, rb.name + ".out_layers.3", r.c2, h1, rb.n2, film, c.film_stride, 0, nullptr, rb.c2, in2, out);
 }
 
 int run_att(Ctx& c, const Act& x, AttB& ab, Act* out) {
     Act xn, qkv, a;
     PD_TRY(run_gn(c, x, ab.n, nullptr, 0, 0, 0, &xn));
-    PD_TRY(run_conv(c, xn, ab.qkv, nullptr, &qkv));
+    PD_TRY(run_conv(c, ab.name + ".qkv", plan_conv(c, xn, ab.qkv, false), ab.qkv, ConvIn{&xn}, &qkv));
     a = x;
     a.p = arena_take(c.u, (size_t)c.N * x.H * x.W * x.C);
     half_t* vt = arena_take(c.u, (size_t)c.N * x.H * x.W * x.C);      // transposed V of the T >= 128 attention kernel
-    if (!c.dry) {
+    if (c.go()) {
         // profile hook (bench.py roofline.attention): QK^T + PV = 4 T^2 C flop per image (12.18 GFLOP per forward)
         const double T = (double)x.H * x.W;
         PD_TRY(prof_begin(c, 4.0 * c.N * T * T * x.C, 1));
         PD_TRY(attention(qkv.p, a.p, c.N, x.H * x.W, x.C, c.u->head, c.s, vt));
         PD_TRY(prof_end(c));
     }
-    return run_conv(c, a, ab.proj, x.p, out, true);
+    return run_conv(c, ab.name + ".proj_out", plan_conv(c, a, ab.proj, true), ab.proj, ConvIn{&a, x.p}, out);
 }
 
 int run_blocks(Ctx& c, std::vector<Block>& blocks, Act* h, const float* x_nchw) {
@@ -445,15 +466,20 @@ int run_blocks(Ctx& c, std::vector<Block>& blocks, Act* h, const float* x_nchw) 
         Act o;
         if (b.kind == 0) {
             o.C = c.u->mult[0] * c.u->mc; o.H = o.W = c.u->image_size;
+            const int cpad = ((o.C + 127) / 128) * 128;
+            ConvNeeds nd;
+            nd.want_gn = true;
+            const ConvPlan p = conv_plan(c.N, o.H, o.W, 32, o.C, cpad, 1, nd, 0);      // the 1x1 conv over the im2col rows conv_in_3x3 launches (no workspace)
             o.p = arena_take(c.u, (size_t)c.N * o.H * o.W * o.C);
             half_t* col = arena_take(c.u, (size_t)c.N * o.H * o.W * 32);
             float* part = reinterpret_cast<float*>(arena_take(c.u, (size_t)c.N * ((o.H * o.W + 127) / 128) * (o.C / 8) * 2 * 2));
-            if (!c.dry) {
+            if (c.table) { Act in{nullptr, 32, o.H, o.W}; table_row(c, "input_blocks.0.0", p, ConvIn{&in}, &o); adopt_parts(&o, part, p.gn_chunks); }
+            if (c.go()) {
                 PD_REQUIRE(c.u->have_win && c.u->have_bin, "unet: input conv not loaded");
-                int fused = 0;
-                PD_TRY(conv_in_3x3(x_nchw, c.u->w_in, c.u->b_in, o.p, c.N, o.H, o.W, o.C, ((o.C + 127) / 128) * 128, col,
-                                   c.u->zero_page, c.s, part, &fused));
-                if (fused) { o.gn_part = part; o.gn_chunks = fused; o.Ca = o.C; }
+                int chunks = 0;
+                PD_TRY(conv_in_3x3(x_nchw, c.u->w_in, c.u->b_in, o.p, c.N, o.H, o.W, o.C, cpad, col, c.u->zero_page, c.s, part, &chunks));
+                PD_REQUIRE(chunks == p.gn_chunks, "unet: input conv: planned for %d partial chunks per image, the launcher left %d", p.gn_chunks, chunks);
+                adopt_parts(&o, part, chunks);
             }
         } else if (b.kind == 1) {
             PD_TRY(run_res(c, *h, c.u->res[b.idx], &o));
@@ -465,15 +491,15 @@ int run_blocks(Ctx& c, std::vector<Block>& blocks, Act* h, const float* x_nchw) 
     return PDHIP_OK;
 }
 
-// the whole forward; dry = sizing pass (no launches)
+// the whole forward; dry = sizing pass (no launches); table != NULL = planning only (real routing, no launches, one line per conv)
 // shared_emb: one precomputed row of ResBlock embeddings [emb_rows] used by every image (t is then ignored), or nullptr
 int forward_impl(pdhip_unet* u, const float* x, const float* t, int N, float* out, hipStream_t s, bool dry,
-                 const float* shared_emb = nullptr, int head_ch = 0) {   // head_ch 3: only eps (out [N,3,H,W]); 0 = all out_ch
-    Ctx c{u, N, s, dry, shared_emb ? shared_emb : u->emb_all, shared_emb ? 0 : u->emb_rows};
+                 const float* shared_emb = nullptr, int head_ch = 0, Table* table = nullptr) {   // head_ch 3: only eps (out [N,3,H,W]); 0 = all out_ch
+    Ctx c{u, N, s, dry, shared_emb ? shared_emb : u->emb_all, shared_emb ? 0 : u->emb_rows, table};
     u->arena_off = 0;
     u->arena_overflow = false;
-    if (!dry && u->prof.on) u->prof.armed = (u->prof.forwards++ % u->prof.period) == 0;      // events around every period-th forward's launches
-    if (!dry && shared_emb == nullptr) {
+    if (c.go() && u->prof.on) u->prof.armed = (u->prof.forwards++ % u->prof.period) == 0;      // events around every period-th forward's launches
+    if (c.go() && shared_emb == nullptr) {
         PD_REQUIRE(u->have_te[0] && u->have_te[1] && u->have_te[2] && u->have_te[3], "unet: time_embed not loaded");
         PD_TRY(timestep_mlp(t, N, u->mc, u->te_w0, u->te_b0, u->te_w2, u->te_b2, u->emb_silu, u->emb_tmp, s));
         PD_TRY(gemv_rows(u->emb_w, u->emb_b, u->emb_silu, u->emb_all, (int)u->emb_rows, u->ted, N, s));
@@ -493,6 +519,7 @@ int forward_impl(pdhip_unet* u, const float* x, const float* t, int N, float* ou
         const bool part_ok = h.gn_part && sk.gn_part && !h.gn_partB && !sk.gn_partB && !h.p2 && !sk.p2;
         if (part_ok) {
             cat.gn_part = h.gn_part; cat.gn_partB = sk.gn_part; cat.Ca = h.C; cat.gn_chunks = h.gn_chunks; cat.gn_chunksB = sk.gn_chunks;
+            cat.row = h.row; cat.rowB = sk.row;
         }
         const Block& first = blk.front();
         const bool virt = part_ok && h.C % 64 == 0 && sk.C % 64 == 0 && ((cat.C / 32) % 8) == 0 && first.kind == 1 &&
@@ -501,12 +528,12 @@ int forward_impl(pdhip_unet* u, const float* x, const float* t, int N, float* ou
             cat.p = h.p; cat.p2 = sk.p;
         } else {
             cat.p = arena_take(u, (size_t)N * h.H * h.W * (h.C + sk.C));
-            if (!dry) PD_TRY(concat_channels(h.p, h.C, sk.p, sk.C, (long long)N * h.H * h.W, cat.p, s));
+            if (c.go()) PD_TRY(concat_channels(h.p, h.C, sk.p, sk.C, (long long)N * h.H * h.W, cat.p, s));
         }
         h = cat;
         PD_TRY(run_blocks(c, blk, &h, x));
     }
-    if (!dry) {
+    if (c.go()) {
         PD_REQUIRE(!u->arena_overflow, "unet: activation arena too small for this routing (sized at create())");
         PD_REQUIRE(u->out_norm.have_g && u->out_norm.have_b && u->have_ow && u->have_ob, "unet: output head not loaded");
         PD_TRY(run_gn_stats(c, h));
@@ -517,38 +544,44 @@ int forward_impl(pdhip_unet* u, const float* x, const float* t, int N, float* ou
     return PDHIP_OK;
 }
 
-}  // namespace
-
-// =================================================================================================
-extern "C" int pdhip_unet_create(int image_size, int model_channels, int num_res_blocks, const int* channel_mult, int n_mult,
-                                 const int* attention_ds, int n_att, int num_head_channels, int out_channels, int max_batch,
-                                 pdhip_unet** out) {
-    PD_REQUIRE(out && channel_mult && n_mult > 0 && (n_att == 0 || attention_ds), "pdhip_unet_create: null argument");
+// ---- graph (unet.py:481-617): host only.  Every conv gets its shape here, and routing's "do the packed copies exist" questions their answers
+// (has_wf, has_wph, has_c2s, has_c2s_wf); pdhip_unet_create allocates what they say, pdhip_unet_route_table plans without a device.
+const size_t kSplitkFloats = (size_t)16 * 384 * 128 * 128;               // 16 splits x (< 384 tiles of 128x128) f32
+void shape_conv(ConvW& c, int cin, int cout, int taps) { c.cin = cin; c.cout = cout; c.taps = taps; c.cout_pad = ((cout + 127) / 128) * 128; }
+int build_graph(pdhip_unet* u, int image_size, int model_channels, int num_res_blocks, const int* channel_mult, int n_mult,
+                const int* attention_ds, int n_att, int num_head_channels, int out_channels, int max_batch) {
+    PD_REQUIRE(channel_mult && n_mult > 0 && (n_att == 0 || attention_ds), "pdhip_unet_create: null argument");
     PD_REQUIRE(model_channels % 32 == 0 && image_size % (1 << (n_mult - 1)) == 0 && max_batch >= 1 && max_batch <= 64,
                "pdhip_unet_create: model_channels %% 32, image_size %% 2^(levels-1), 1 <= max_batch <= 64 required");
     PD_REQUIRE(num_head_channels == 32 || num_head_channels == 64, "pdhip_unet_create: num_head_channels must be 32 or 64");
     PD_REQUIRE(out_channels == 3 || out_channels == 6, "pdhip_unet_create: out_channels must be 3 or 6");
-    pdhip_unet* u = new pdhip_unet();
-    *out = nullptr;
     u->image_size = image_size; u->mc = model_channels; u->nres = num_res_blocks; u->head = num_head_channels;
     u->out_ch = out_channels; u->max_batch = max_batch; u->ted = model_channels * 4;
+    u->splitk_floats = kSplitkFloats;
     u->mult.assign(channel_mult, channel_mult + n_mult);
     u->att_ds.assign(attention_ds, attention_ds + n_att);
     auto is_att = [&](int ds) { for (int a : u->att_ds) if (a == ds) return true; return false; };
-    auto fail = [&](int rc) { for (void* p : u->owned) (void)hipFree(p); delete u; return rc; };
     long long emb_rows = 0;
     auto add_res = [&](const std::string& name, int cin, int cout, int mode, int hw) -> int {
         ResB rb; rb.name = name; rb.cin = cin; rb.cout = cout; rb.mode = mode; rb.has_skip = cin != cout; rb.hw = hw;
         rb.emb_off = emb_rows; emb_rows += 2 * cout;
+        shape_conv(rb.c1, cin, cout, 9); shape_conv(rb.c2, cout, cout, 9);
+        if (rb.has_skip) shape_conv(rb.skip, cin, cout, 1);
+        rb.has_c2s = rb.has_skip && mode == 0 && cin % 64 == 0 && cout % 64 == 0;       // fused [conv2 | skip] weights
+        // phase weights of an up block's in_layers conv, 16 Cin Cout_pad f16 (50 MB over the four up blocks whose half-resolution image holds whole 256-pixel tiles)
+        rb.c1.has_wph = mode == 2 && ((hw / 2) * (hw / 2)) % 256 == 0 && conv_up2_phase_eligible(1, hw / 2, hw / 2, cin, cout, rb.c1.cout_pad);
+        // fragment-major copies for the row-resident kernel (small-batch route of the <= 64^2 levels; +~1 GB at the 256^2 config: 288 GB HBM)
+        rb.c1.has_wf = rb.c2.has_wf = hw <= 64 && cin % 128 == 0 && cout % 128 == 0;
+        rb.has_c2s_wf = rb.c2.has_wf && rb.has_c2s;
         u->res.push_back(rb);
         return (int)u->res.size() - 1;
     };
     auto add_att = [&](const std::string& name, int c) -> int {
         AttB ab; ab.name = name; ab.c = c;
+        shape_conv(ab.qkv, c, 3 * c, 1); shape_conv(ab.proj, c, c, 1);
         u->att.push_back(ab);
         return (int)u->att.size() - 1;
     };
-    // ---- graph (unet.py:481-617)
     int ch = u->mult[0] * u->mc;
     std::vector<int> chans{ch};
     u->input.push_back({Block{0, 0}});
@@ -595,30 +628,40 @@ extern "C" int pdhip_unet_create(int image_size, int model_channels, int num_res
     }
     u->final_ch = ch;
     u->emb_rows = emb_rows;
+    return PDHIP_OK;
+}
+
+}  // namespace
+
+// =================================================================================================
+extern "C" int pdhip_unet_create(int image_size, int model_channels, int num_res_blocks, const int* channel_mult, int n_mult,
+                                 const int* attention_ds, int n_att, int num_head_channels, int out_channels, int max_batch,
+                                 pdhip_unet** out) {
+    PD_REQUIRE(out, "pdhip_unet_create: null argument");
+    pdhip_unet* u = new pdhip_unet();
+    *out = nullptr;
+    auto fail = [&](int rc) { for (void* p : u->owned) (void)hipFree(p); delete u; return rc; };
+    int rc = build_graph(u, image_size, model_channels, num_res_blocks, channel_mult, n_mult, attention_ds, n_att, num_head_channels, out_channels, max_batch);
+    if (rc) return fail(rc);
+    const long long emb_rows = u->emb_rows;
     // ---- parameters
-    int rc = PDHIP_OK;
     auto chk = [&](int r) { if (rc == PDHIP_OK) rc = r; };
     for (ResB& rb : u->res) {
         chk(alloc_norm(u, rb.n1, rb.cin)); chk(alloc_norm(u, rb.n2, rb.cout));
-        chk(alloc_conv(u, rb.c1, rb.cin, rb.cout, 9)); chk(alloc_conv(u, rb.c2, rb.cout, rb.cout, 9));
-        if (rb.has_skip) chk(alloc_conv(u, rb.skip, rb.cin, rb.cout, 1));
-        if (rb.has_skip && rb.mode == 0 && rb.cin % 64 == 0 && rb.cout % 64 == 0) {       // fused [conv2 | skip] weights (built at the first forward that routes there)
+        chk(alloc_conv(u, rb.c1)); chk(alloc_conv(u, rb.c2));
+        if (rb.has_skip) chk(alloc_conv(u, rb.skip));
+        if (rb.has_c2s) {       // (filled by pdhip_unet_load_tensor once its four sources are loaded)
             chk(dalloc(u, &rb.c2s_w, (size_t)rb.c2.cout_pad * (9 * (size_t)rb.cout + rb.cin)));
             chk(dalloc(u, &rb.c2s_b, (size_t)rb.cout));
         }
-        // fragment-major copies for the row-resident kernel (small-batch route of the <= 64^2 levels; +~1 GB at the 256^2 config: 288 GB HBM)
-        // phase weights of an up block's in_layers conv, 16 Cin Cout_pad f16 (50 MB over the four up blocks whose half-resolution image holds whole 256-pixel tiles)
-        if (rb.mode == 2 && ((rb.hw / 2) * (rb.hw / 2)) % 256 == 0 && conv_up2_phase_eligible(1, rb.hw / 2, rb.hw / 2, rb.cin, rb.cout, rb.c1.cout_pad))
-            chk(dalloc(u, &rb.c1.wph, (size_t)16 * rb.c1.cout_pad * rb.cin));
-        if (rb.hw <= 64 && rb.cin % 128 == 0 && rb.cout % 128 == 0) {
-            chk(dalloc(u, &rb.c1.wf, conv_rr_weight_halfs(rb.cin, 9, 0, rb.cout)));
-            chk(dalloc(u, &rb.c2.wf, conv_rr_weight_halfs(rb.cout, 9, 0, rb.cout)));
-            if (rb.c2s_w != nullptr) chk(dalloc(u, &rb.c2s_wf, conv_rr_weight_halfs(rb.cout, 9, rb.cin, rb.cout)));
-        }
+        if (rb.c1.has_wph) chk(dalloc(u, &rb.c1.wph, (size_t)16 * rb.c1.cout_pad * rb.cin));
+        if (rb.c1.has_wf) chk(dalloc(u, &rb.c1.wf, conv_rr_weight_halfs(rb.cin, 9, 0, rb.cout)));
+        if (rb.c2.has_wf) chk(dalloc(u, &rb.c2.wf, conv_rr_weight_halfs(rb.cout, 9, 0, rb.cout)));
+        if (rb.has_c2s_wf) chk(dalloc(u, &rb.c2s_wf, conv_rr_weight_halfs(rb.cout, 9, rb.cin, rb.cout)));
         if (rc) return fail(rc);
     }
     for (AttB& ab : u->att) {
-        chk(alloc_norm(u, ab.n, ab.c)); chk(alloc_conv(u, ab.qkv, ab.c, 3 * ab.c, 1)); chk(alloc_conv(u, ab.proj, ab.c, ab.c, 1));
+        chk(alloc_norm(u, ab.n, ab.c)); chk(alloc_conv(u, ab.qkv)); chk(alloc_conv(u, ab.proj));
         if (rc) return fail(rc);
     }
     const int c0 = u->mult[0] * u->mc;
@@ -653,7 +696,6 @@ extern "C" int pdhip_unet_create(int image_size, int model_channels, int num_res
     { float* wz = nullptr; chk(dalloc(u, &wz, (size_t)64 * u->final_ch)); u->head_wz = reinterpret_cast<half_t*>(wz); }
     { float* wz = nullptr; chk(dalloc(u, &wz, (size_t)64 * u->final_ch)); u->head_wz3 = reinterpret_cast<half_t*>(wz); }
     chk(dalloc(u, &u->t_dev, (size_t)max_batch));
-    u->splitk_floats = (size_t)16 * 384 * 128 * 128;               // 16 splits x (< 384 tiles of 128x128) f32
     chk(dalloc(u, &u->splitk_ws, u->splitk_floats));
     if (rc == PDHIP_OK && hipMemset(u->splitk_ws, 0, PD_SK_TICKET_FLOATS * sizeof(float)) != hipSuccess) rc = PDHIP_E_HIP;   // k_conv_sk's tickets
     chk(dalloc(u, &u->sx, (size_t)max_batch * 3 * S2)); chk(dalloc(u, &u->sy, (size_t)max_batch * 3 * S2));
@@ -671,6 +713,28 @@ extern "C" void pdhip_unet_destroy(pdhip_unet* u) {
 }
 
 extern "C" long long pdhip_unet_arena_bytes(const pdhip_unet* u) { return u ? (long long)u->arena_bytes : -1; }
+
+// host-only: the route of every conv of a batch-N forward of the network pdhip_unet_create would build from the same arguments, under the hooks
+// in force -- the forward walked in planning mode (real routing, nothing allocated, nothing launched).  One line per conv, in launch order:
+//   <layer> <H>x<W> <Cin>-><Cout> <kernel> <splits / slabs / variant> gn=<chunks per image> <folds taken, or ->
+// Returns the length of the whole table (a negative error code on bad arguments); buf (may be NULL) gets as much of it as fits, NUL-terminated.
+extern "C" int pdhip_unet_route_table(int image_size, int model_channels, int num_res_blocks, const int* channel_mult, int n_mult,
+                                      const int* attention_ds, int n_att, int num_head_channels, int out_channels, int max_batch, int N,
+                                      char* buf, int buf_len) {
+    pdhip_unet u;
+    int rc = build_graph(&u, image_size, model_channels, num_res_blocks, channel_mult, n_mult, attention_ds, n_att, num_head_channels, out_channels, max_batch);
+    if (rc == PDHIP_OK && (N < 1 || N > max_batch)) { set_error("pdhip_unet_route_table: batch %d outside [1, %d]", N, max_batch); rc = PDHIP_E_ARG; }
+    if (rc != PDHIP_OK) return rc;
+    u.arena = reinterpret_cast<char*>((size_t)1 << 20);      // addresses to tell "has a tensor" from "has none" by; never dereferenced
+    u.arena_bytes = ~(size_t)0 >> 1;
+    Table table;
+    rc = forward_impl(&u, nullptr, nullptr, N, nullptr, nullptr, false, nullptr, 0, &table);
+    if (rc != PDHIP_OK) return rc;
+    std::string all;
+    for (const std::string& l : table.line) { all += l; all += '\n'; }
+    if (buf && buf_len > 0) { strncpy(buf, all.c_str(), buf_len - 1); buf[buf_len - 1] = 0; }
+    return (int)all.size();
+}
 
 // names still missing after loading (count); if buf != NULL the first names are written, '\n'-separated
 extern "C" int pdhip_unet_missing_tensors(const pdhip_unet* u, char* buf, int buf_len) {
@@ -733,8 +797,8 @@ extern "C" int pdhip_unet_load_tensor(pdhip_unet* u, const char* name_c, const v
         PD_REQUIRE(shape[0] == c.cout && shape[1] == c.cin, "pdhip_unet_load_tensor: %s: shape mismatch", name_c);
         k_pack_conv<<<grid_for(numel), 256, 0, s>>>(data, is_f16, c.cout, c.cin, c.taps, c.w);
         PD_LAUNCH_CHECK();
-        if (c.wf != nullptr) PD_TRY(conv_rr_pack(c.w, c.cin, c.taps, 0, c.cout, c.wf, s));      // (same stream: ordered behind the repack above)
-        if (c.wph != nullptr) PD_TRY(conv_up2_phase_pack(c.w, c.cin, c.cout_pad, c.wph, s));   // (from the f16-rounded taps: an f32 and an f16 checkpoint give the same bytes)
+        if (c.has_wf) PD_TRY(conv_rr_pack(c.w, c.cin, c.taps, 0, c.cout, c.wf, s));      // (same stream: ordered behind the repack above)
+        if (c.has_wph) PD_TRY(conv_up2_phase_pack(c.w, c.cin, c.cout_pad, c.wph, s));   // (from the f16-rounded taps: an f32 and an f16 checkpoint give the same bytes)
         c.have_w = true;
         return PDHIP_OK;
     };
@@ -780,11 +844,11 @@ extern "C" int pdhip_unet_load_tensor(pdhip_unet* u, const char* name_c, const v
         // present (built lazily inside the first forward it could be merely RECORDED by a HIP-graph capture, and an eager
         // forward issued before the replay would have read uninitialised weights).
         auto refuse = [&](int rc) -> int {
-            if (rc != PDHIP_OK || rb.c2s_w == nullptr) return rc;
+            if (rc != PDHIP_OK || !rb.has_c2s) return rc;
             rb.c2s_ready = false;
             if (rb.c2.have_w && rb.c2.have_b && rb.skip.have_w && rb.skip.have_b && rb.skip.taps == 1) {
                 PD_TRY(fuse_skip_weights(rb.c2.w, 9 * rb.c2.cin, rb.skip.w, rb.skip.cin, rb.c2.cout_pad, rb.c2.b, rb.skip.b, rb.cout, rb.c2s_w, rb.c2s_b, s));
-                if (rb.c2s_wf != nullptr) PD_TRY(conv_rr_pack(rb.c2s_w, rb.c2.cin, 9, rb.skip.cin, rb.cout, rb.c2s_wf, s));
+                if (rb.has_c2s_wf) PD_TRY(conv_rr_pack(rb.c2s_w, rb.c2.cin, 9, rb.skip.cin, rb.cout, rb.c2s_wf, s));
                 rb.c2s_ready = true;
             }
             return PDHIP_OK;
@@ -1000,7 +1064,9 @@ extern "C" int pdhip_conv3x3_up2_phase_nhwc_f16(const void* x, const void* w_pha
 extern "C" int pdhip_conv3x3_up2_halo_nhwc_f16(const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W, int Cin, int Cout,
                                                int Cout_pad, const void* zero_page, void* stream) {
     PD_REQUIRE(x && w_packed && y && zero_page, "pdhip_conv3x3_up2_halo_nhwc_f16: null argument");
-    PD_REQUIRE(conv_uses_halo(N, 2 * H, 2 * W, Cin, Cout, Cout_pad, 9, 0) && (2 * W != 256 || (2 * H) % 4 == 0),
+    pdnn::ConvNeeds nd;
+    nd.in_up = true;
+    PD_REQUIRE(conv_plan(N, 2 * H, 2 * W, Cin, Cout, Cout_pad, 9, nd, 0).takes_in_up,
                "pdhip_conv3x3_up2_halo_nhwc_f16: not a layer the halo-resident kernel takes unsplit");
     return conv_igemm((const half_t*)x, (const half_t*)w_packed, bias, nullptr, (half_t*)y, N, 2 * H, 2 * W, Cin, Cout, Cout_pad, 9,
                       (const half_t*)zero_page, as_stream(stream), nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, 1);

@@ -67,6 +67,7 @@ _reg('pdhip_debug_set_conv_rr', C.c_int, [i32, i32, i32])
 _reg('pdhip_debug_set_rr_gn', C.c_int, [i32])
 _reg('pdhip_debug_set_conv_ht', C.c_int, [i32, i32])
 _reg('pdhip_conv_ht_plan', C.c_int, [i32, i32, i32, i32, i32, i32, C.c_longlong, C.POINTER(C.c_int), C.POINTER(C.c_int)])
+_reg('pdhip_unet_route_table', C.c_int, [i32, i32, i32, C.POINTER(C.c_int), i32, C.POINTER(C.c_int), i32, i32, i32, i32, i32, C.c_char_p, i32])
 _reg('pdhip_conv_ht_f16', C.c_int, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, C.c_longlong, vp, C.POINTER(C.c_int), vp])
 _reg('pdhip_conv_rr_weight_halfs', C.c_longlong, [i32, i32, i32, i32])
 _reg('pdhip_conv_rr_pack_f16', C.c_int, [vp, i32, i32, i32, i32, vp, vp])
@@ -89,6 +90,22 @@ DEFAULT_CKPT = 'models/DDNM/256x256_diffusion_uncond.pt'
 
 def default_channel_mult(image_size):
     return {512: (0.5, 1, 1, 2, 2, 4, 4), 256: (1, 1, 2, 2, 4, 4), 128: (1, 1, 2, 3, 4), 64: (1, 2, 3, 4)}[image_size]
+
+
+def unet_route_table(N, image_size=256, num_channels=256, num_res_blocks=2, attention_resolutions="32,16,8", num_head_channels=64,
+                     learn_sigma=True, channel_mult="", max_batch=64, **unused):
+    """Host-only (no GPU): the route of every conv of a batch-N forward of the UNet these arguments build, under the debug hooks in force, as a list
+    of lines "<layer> <H>x<W> <Cin>-><Cout> <kernel> <splits / slabs / variant> gn=<chunks> <folds or ->" (include/pdhip.h: pdhip_unet_route_table)."""
+    L = _lib.lib()
+    cm = tuple(int(c) for c in channel_mult.split(",")) if channel_mult else default_channel_mult(image_size)
+    ads = tuple(image_size // int(r) for r in attention_resolutions.split(","))
+    args = (image_size, num_channels, num_res_blocks, (C.c_int * len(cm))(*cm), len(cm), (C.c_int * len(ads))(*ads), len(ads), num_head_channels,
+            6 if learn_sigma else 3, max_batch, N)
+    n = L.pdhip_unet_route_table(*args, None, 0)
+    check(min(n, 0), 'pdhip_unet_route_table')
+    buf = C.create_string_buffer(n + 1)
+    check(min(L.pdhip_unet_route_table(*args, buf, n + 1), 0), 'pdhip_unet_route_table')
+    return buf.value.decode().splitlines()
 
 
 class UNetModel:

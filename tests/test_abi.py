@@ -123,3 +123,84 @@ def test_halo_tile_conv_routing_table_on_host():
     assert plan(2, 64, 1024, 512) == (1, 1) and plan(4, 64, 512, 512) == (1, 1) and plan(8, 64, 512, 512)[0] == 0
     assert plan(1, 64, 1024, 512, ws=0) == (0, 1)            # no workspace: unsplit, and at half the chip the 1 024-channel layer is k_conv_sk's
     assert plan(1, 32, 512, 512)[0] == 0 and plan(1, 256, 256, 256)[0] == 0 and plan(1, 64, 48, 512)[0] == 0             # 32^2 / 256^2 / Cin % 32
+
+
+# ---- pdhip_unet_route_table (host-only): the route of every conv of a UNet forward, planned without a device (DESIGN.md section 5)
+ROUTE_SMALL = dict(image_size=32, num_channels=256, num_res_blocks=2, attention_resolutions="16,8", num_head_channels=64, channel_mult="1,2,4")
+
+
+def _routes(N, **kw):
+    """[(layer, HxW, Cin->Cout, kernel, detail, gn_chunks, set of folds)] of a batch-N forward (production config unless kw says otherwise)."""
+    import pointdreamer_amd.ddnm_inpainting as di
+    rows = []
+    for line in di.unet_route_table(N, **kw):
+        name, hw, ch, kernel, detail, gn, folds = line.split(' ')
+        assert gn.startswith('gn=')
+        rows.append((name, hw, ch, kernel, detail, int(gn[3:]), set() if folds == '-' else set(folds.split(','))))
+    return rows
+
+
+def test_unet_route_table_matches_the_committed_snapshot():
+    """Production config (image 256, 256 channels, 2 ResBlocks per level, attention at 8 / 16 / 32, 64-channel heads, 6 outputs, the engine's split-K
+    workspace) at batch 1, 2, 4, 8, 32: the table equals tests/golden/unet_route_table_256.txt, taken from the build whose kernel-launch sequence
+    was compared, launch by launch, with the engine before the plan structs existed (profiles/route_plan_trace_check.txt)."""
+    import __graft_entry__ as ge
+    ge.build()
+    import pointdreamer_amd.ddnm_inpainting as di
+    got = ''.join(f"# N={N}\n" + '\n'.join(di.unet_route_table(N)) + '\n' for N in (1, 2, 4, 8, 32))
+    want = open(os.path.join(ROOT, 'tests', 'golden', 'unet_route_table_256.txt')).read()
+    assert got == want
+
+
+@pytest.mark.parametrize("kw", [{}, ROUTE_SMALL], ids=["256", "32"])
+def test_unet_route_table_is_consistent_at_every_batch(kw):
+    """N = 1 ... 64: a row that takes res_up / in_up / apply names a kernel that can (res_up: rr, ht, sk or the unsplit halo kernel; in_up and apply:
+    the halo kernel), and every conv whose input pass reads GroupNorm partials names producers, each a row that leaves some (gn > 0)."""
+    import __graft_entry__ as ge
+    ge.build()
+    for N in range(1, 65):
+        rows = _routes(N, **kw)
+        gn = {r[0]: r[5] for r in rows}
+        assert len(gn) == len(rows)                          # layer names are unique
+        for name, _, _, kernel, detail, _, folds in rows:
+            if 'res_up' in folds:
+                assert kernel in ('rr', 'ht', 'sk') or (kernel == 'halo' and detail == 'splits=1'), (N, name, kernel, detail)
+            if 'in_up' in folds or 'apply' in folds:
+                assert kernel == 'halo', (N, name, kernel)
+            if 'in_gn' in folds or 'skip' in folds:
+                assert kernel in ('rr', 'sk') if 'skip' in folds else kernel == 'rr', (N, name, kernel)
+            needs = [f for f in folds if f.startswith('parts<-')]
+            assert needs or not ({'gn_skip', 'in_gn'} & folds), (N, name, folds)      # k_gn_skip and the in-staging GroupNorm read partials
+            for f in needs:
+                for producer in f[len('parts<-'):].split('+'):
+                    assert gn.get(producer, 0) > 0, (N, name, producer)
+        two = [r for r in rows if 'two_source' in r[6]]
+        assert all(r[0].endswith('.skip_connection') for r in two)
+
+
+def test_unet_route_table_follows_the_hooks():
+    """up_phase 0 -> no phase rows, conv_rr mode 0 -> no rr rows, fold_skip 0 -> no +skip rows; every other row of the table stays as it was
+    (apart from the rows of the blocks the hook changes), and the hooks are restored."""
+    import __graft_entry__ as ge
+    ge.build()
+    from pointdreamer_amd import _lib
+    import pointdreamer_amd.ddnm_inpainting  # noqa: F401
+    L = _lib.lib()
+    for N in (1, 32):
+        base = _routes(N)
+        assert any(r[3] == 'phase' for r in base) and any('skip' in r[6] for r in base)
+        assert any(r[3] == 'rr' for r in base) == (N == 1)
+        hooks = [(lambda: L.pdhip_debug_set_up_phase(0), lambda old: L.pdhip_debug_set_up_phase(old), lambda r: r[3] == 'phase'),
+                 (lambda: L.pdhip_debug_set_conv_rr(0, 0, 0), lambda old: L.pdhip_debug_set_conv_rr(old, 0, 0), lambda r: r[3] == 'rr'),
+                 (lambda: L.pdhip_debug_set_fold_skip(0), lambda old: L.pdhip_debug_set_fold_skip(old), lambda r: 'skip' in r[6])]
+        for flip, restore, hit in hooks:
+            old = flip()
+            try:
+                off = _routes(N)
+            finally:
+                restore(old)
+            assert not any(hit(r) for r in off)
+            block = lambda r: re.match(r'(input_blocks|output_blocks)\.\d+\.\d+|middle_block\.\d+', r[0]).group(0)
+            changed = {block(r) for r in base if hit(r)}     # the blocks whose rows the hook touches
+            assert [r for r in off if block(r) not in changed] == [r for r in base if block(r) not in changed]
+            assert _routes(N) == base                        # restored
