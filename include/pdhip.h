@@ -392,7 +392,8 @@ int pdhip_debug_set_gn_skip_variant(int v);   /* lab hook of the one-pass GroupN
 int pdhip_debug_set_fuse_skip(int mode, int min_tiles);   /* ResBlock GroupNorm-apply + skip 1x1 as one pass: mode 0 never / 1 (default) layers of at least min_tiles 128-pixel tiles (default 1024; <= 0 keeps the value) / 2 every eligible layer; returns the previous mode */
 int pdhip_debug_set_fuse_gn(int on);   /* 1: the UNet uses the fused form wherever the halo kernel serves a conv; 0 (default, measured faster): stand-alone passes */
 /* ---- complete_unseen_by='neighbor' (pointdreamer/unproject.py:93-196, demo.py:180-200).
- * The mesh subdivision stays on the host (as in the reference); these are the per-texel / per-vertex kernels. */
+ * These are the per-texel / per-vertex kernels; the mesh work (subdivision, per-vertex UVs, neighbour table, list of uncoloured
+ * vertices) runs on the device as well, through the entries of csrc/neighbor_mesh.hip declared after them. */
 /* flags[f] = 1 for every face f that owns a chart texel no view painted (demo.py:180-181). face_id [A*A] int64 (-1 = background). */
 int pdhip_mark_unpainted_faces(const int64_t* face_id, const uint8_t* painted, int A, int F, uint8_t* flags /*[F]*/, void* stream);
 /* texel (row, col) = long(clip(uv * A, 0, A-1))[(1, 0)], colours = atlas[texel], count = mask[texel] (unproject.py:130-139) */
@@ -405,6 +406,38 @@ int pdhip_neighbor_diffuse_round(const int32_t* rowptr /*[V+1]*/, const int32_t*
 /* atlas[texel[v]] = colors[v], mask[texel[v]] = 1 (unproject.py:187-188); several vertices on one texel: largest index wins */
 int pdhip_scatter_vertex_colors(const int32_t* texel, const float* colors, int V, float* atlas, uint8_t* mask,
                                 int32_t* owner_ws /*[A*A]*/, int A, void* stream);
+/* ---- the mesh side of 'neighbor' (utils/mesh_utils.py:7-114, unproject.py:105-127, 145-155) on the device, bit-identical to the numpy forms in
+ * pointdreamer_amd/mesh_utils.py.  Sizes are int32; every entry checks them.  counts: device int32; counts_host (may be NULL): the same
+ * values on the host -- each entry with a counts_host reads its counts and error flags back once, at its end (it synchronises
+ * `stream`), and that one read is handed on, so a caller that needs the sizes reads nothing itself.
+ *      pdhip_subdivide_with_uv: one round of midpoint subdivision of the faces in face_index [K] (duplicates allowed; NULL with K = -1:
+ *      all faces; K = 0: the input comes back unchanged).  Untouched faces first in their order, then four children per picked face in
+ *      ascending face order: (v0 m01 m20) (m01 v1 m12) (m20 m12 v2) (m01 m12 m20).  New vertices follow the old ones, one per unique
+ *      undirected edge of the picked faces, ordered by (larger endpoint, smaller endpoint), value (x[lo] + x[hi]) / 2 in float32; the
+ *      same rule runs independently on the UV index space.  With T picked faces (T <= Tmax = min(K, F), or F for all faces) the
+ *      outputs hold V + E <= V + 3T vertices, U + Euv <= U + 3T UVs and F + 3T faces; the caller provides V + 3 Tmax, U + 3 Tmax and
+ *      F + 3 Tmax rows.  counts[4] = V', U', F', T.  ws: pdhip_subdivide_with_uv_ws_bytes(V, U, F, K) bytes (non-decreasing in K >= 0).
+ *      F <= 2^27, V, U <= 2^29.  A face_index entry outside [0, F), or a picked face with an index outside [0, V) / [0, U):
+ *      PDHIP_E_ARG with the cause (the outputs are then undefined, within their capacities). */
+size_t pdhip_subdivide_with_uv_ws_bytes(int V, int U, int F, int K);
+int pdhip_subdivide_with_uv(const float* vertices /*[V,3]*/, int V, const int64_t* faces /*[F,3]*/, int F, const float* uvs /*[U,2]*/, int U,
+                            const int64_t* face_uv_idx /*[F,3]*/, const int64_t* face_index /*[K] or NULL*/, int K,
+                            float* out_vertices, int64_t* out_faces, float* out_uvs, int64_t* out_face_uv_idx,
+                            int32_t* counts /*device [4]*/, int32_t* counts_host /*[4] or NULL*/, void* ws, void* stream);
+/* one UV per vertex (unproject.py:123-127): of the UVs a vertex is used with, the one with the largest UV index; zeros for a vertex
+ * no face uses.  counts[1] (device) = corners skipped because an index lies outside [0, V) / [0, U).  Does not synchronise. */
+size_t pdhip_vertex_uv_table_ws_bytes(int V, int F);
+int pdhip_vertex_uv_table(int V, const int64_t* faces /*[F,3]*/, const int64_t* face_uv_idx /*[F,3]*/, int F, const float* uvs /*[U,2]*/,
+                          int U, float* vert_uvs /*[V,2]*/, int32_t* counts /*device [1]*/, void* ws, void* stream);
+/* unique undirected vertex neighbours as CSR: rowptr [V+1], colidx ascending per row (capacity 6F), self pairs dropped;
+ * counts[1] = nnz.  F <= 2^28.  A vertex index outside [0, V): PDHIP_E_ARG. */
+size_t pdhip_neighbour_csr_ws_bytes(int V, int F);
+int pdhip_neighbour_csr(int V, const int64_t* faces /*[F,3]*/, int F, int32_t* rowptr /*[V+1]*/, int32_t* colidx /*[6F] capacity*/,
+                        int32_t* counts /*device [1]*/, int32_t* counts_host /*[1] or NULL*/, void* ws, void* stream);
+/* invalid = ascending list of the vertices with count[v] == 0 (capacity V), counts[1] = its length (unproject.py:145-147) */
+size_t pdhip_compact_zero_count_ws_bytes(int V);
+int pdhip_compact_zero_count(const float* count /*[V]*/, int V, int32_t* invalid /*[V] capacity*/, int32_t* counts /*device [1]*/,
+                             int32_t* counts_host /*[1] or NULL*/, void* ws, void* stream);
 
 /* ---- I/O edges in native code (host functions; no device work except pdhip_chw_f32_to_hwc_u8).
  * PLY (utils/other_utils.py:155-163): vertex element with x,y,z and red,green,blue, binary_little_endian or ascii. */

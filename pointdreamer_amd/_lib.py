@@ -78,6 +78,14 @@ _SIGS = {
     'pdhip_vertex_texel_fetch': (C.c_int, [vp, i32, vp, vp, i32, vp, vp, vp, vp]),
     'pdhip_neighbor_diffuse_round': (C.c_int, [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     'pdhip_scatter_vertex_colors': (C.c_int, [vp, vp, i32, vp, vp, vp, i32, vp]),
+    'pdhip_subdivide_with_uv_ws_bytes': (sz, [i32, i32, i32, i32]),
+    'pdhip_subdivide_with_uv': (C.c_int, [vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'pdhip_vertex_uv_table_ws_bytes': (sz, [i32, i32]),
+    'pdhip_vertex_uv_table': (C.c_int, [i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]),
+    'pdhip_neighbour_csr_ws_bytes': (sz, [i32, i32]),
+    'pdhip_neighbour_csr': (C.c_int, [i32, vp, i32, vp, vp, vp, vp, vp, vp]),
+    'pdhip_compact_zero_count_ws_bytes': (sz, [i32]),
+    'pdhip_compact_zero_count': (C.c_int, [vp, i32, vp, vp, vp, vp, vp]),
 }
 
 

@@ -1,7 +1,7 @@
 // SURVEY 8(f)-2, complete_unseen_by='neighbor' (pointdreamer/unproject.py:93-196, demo.py:180-200): colour the texels no view
-// painted from their mesh neighbours.  The mesh work that the reference also does on the host (two rounds of midpoint
-// subdivision of the unpainted faces, utils/mesh_utils.py:7-114) stays on the host (pointdreamer_amd/mesh_utils.py); the
-// per-vertex and per-texel work runs here:
+// painted from their mesh neighbours.  The mesh work that the reference does on the host (two rounds of midpoint subdivision of
+// the unpainted faces, utils/mesh_utils.py:7-114, the per-vertex UV table and the neighbour table) runs on the device in
+// neighbor_mesh.hip; the per-vertex and per-texel work runs here:
 //   k_mark_unpainted_faces   faces that own an unpainted chart texel               (demo.py:180-181)
 //   k_vertex_texel_fetch     vertex -> texel, colour, has-colour                    (unproject.py:130-139)
 //   k_nb_gather / k_nb_apply one Jacobi round of the (L + I) neighbour average      (unproject.py:160-166)

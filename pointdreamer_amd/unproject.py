@@ -192,26 +192,52 @@ def unpainted_face_ids(per_atlas_pixel_face_id, atlas_painted_mask, num_faces):
     return np.nonzero(flags.cpu().numpy())[0].astype(np.int64)
 
 
+def _mesh_on_device(vertices, faces, uvs, face_uv_idx):
+    return all(torch.is_tensor(t) and t.is_cuda and t.dtype == dt for t, dt in
+               ((vertices, torch.float32), (uvs, torch.float32), (faces, torch.int64), (face_uv_idx, torch.int64)))
+
+
 def paint_invisible_areas_by_neighbors(vertices, faces, uvs, face_uv_idx, to_inpaint_face_id, atlas_img, atlas_inpainted_mask,
-                                       use_atlas=True):
+                                       use_atlas=True, *, mesh_on=None):
     """unproject.py:93-196, same arguments.  atlas_img [A,A,3] f32, atlas_inpainted_mask [A,A] bool (both on the GPU).
-    Two rounds of midpoint subdivision of the unpainted faces (host numpy, as in the reference), per-vertex colour fetch,
-    Jacobi neighbour averaging with the reference's loop control, scatter back, exact nearest fill.
+    Two rounds of midpoint subdivision of the unpainted faces, per-vertex colour fetch, Jacobi neighbour averaging with the
+    reference's loop control, scatter back, exact nearest fill.
+    mesh_on: where the mesh work before the diffusion loop runs (subdivision, per-vertex UVs, neighbour table, list of uncoloured
+    vertices).  'device': the HIP entries of csrc/neighbor_mesh.hip -- no mesh data crosses to the host, only the counts (a few
+    words per call); 'host': the numpy forms of mesh_utils.py, as the reference does it; None: 'device' when the mesh comes as CUDA
+    float32 / int64 tensors, else 'host'.  Both give the same bytes.  to_inpaint_face_id may be numpy or a tensor.
     use_atlas=True -> atlas [A,A,3]; False -> (subdivided_vertices, subdivided_faces, vertex_colors)."""
     import numpy as np
     from . import mesh_utils as mu
     L = _lib.lib()
     dev = _dev(atlas_img)
     A = atlas_inpainted_mask.shape[1]
-    to_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-    sv, sf, su, sfu = to_np(vertices), to_np(faces), to_np(uvs), to_np(face_uv_idx)
-    tif = to_np(to_inpaint_face_id).astype(np.int64)
+    if mesh_on is None:
+        mesh_on = 'device' if _mesh_on_device(vertices, faces, uvs, face_uv_idx) else 'host'
+    if mesh_on not in ('host', 'device'):
+        raise _lib.PdhipError(f"paint_invisible_areas_by_neighbors: mesh_on={mesh_on!r}, expected None, 'host' or 'device'")
+    on_device = mesh_on == 'device'
+    if on_device:
+        to_dev = lambda t, dt: (t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))).to(dev).to(dt)
+        sv, sf = to_dev(vertices, torch.float32), to_dev(faces, torch.int64)
+        su, sfu = to_dev(uvs, torch.float32), to_dev(face_uv_idx, torch.int64)
+        tif = to_dev(to_inpaint_face_id, torch.int64).reshape(-1)
+    else:
+        to_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        sv, sf, su, sfu = to_np(vertices), to_np(faces), to_np(uvs), to_np(face_uv_idx)
+        tif = to_np(to_inpaint_face_id).astype(np.int64)
     for _ in range(2):                      # unproject.py:111-114: the same index list both rounds (not re-mapped) -- kept
         sv, sf, su, sfu = mu.subdivide_with_uv(sv, sf, sfu, su, face_index=tif)
     V = len(sv)
-    vert_uvs = torch.from_numpy(mu.vertex_uv_table(V, sf, sfu, su)).to(dev)
-    rowptr, colidx = mu.neighbour_csr(V, sf)
-    rowptr_d, colidx_d = torch.from_numpy(rowptr).to(dev), torch.from_numpy(colidx).to(dev)
+    if on_device:
+        vert_uvs = mu.vertex_uv_table(V, sf, sfu, su)
+        rowptr_d, colidx_d = mu.neighbour_csr(V, sf)
+        if colidx_d.shape[0] == 0:
+            colidx_d = torch.zeros((1,), dtype=torch.int32, device=dev)
+    else:
+        vert_uvs = torch.from_numpy(mu.vertex_uv_table(V, sf, sfu, su)).to(dev)
+        rowptr, colidx = mu.neighbour_csr(V, sf)
+        rowptr_d, colidx_d = torch.from_numpy(rowptr).to(dev), torch.from_numpy(colidx).to(dev)
     atlas = atlas_img.float().contiguous().clone()
     mask = as_u8(atlas_inpainted_mask.contiguous()).clone()
     texel = torch.empty((V, 2), dtype=torch.int32, device=dev)
@@ -219,9 +245,15 @@ def paint_invisible_areas_by_neighbors(vertices, faces, uvs, face_uv_idx, to_inp
     count = torch.empty((V,), device=dev)
     check(L.pdhip_vertex_texel_fetch(ptr(vert_uvs), V, ptr(atlas), ptr(mask), A, ptr(texel), ptr(colors), ptr(count), stream()),
           'pdhip_vertex_texel_fetch')
-    invalid_np = np.nonzero(count.cpu().numpy() == 0)[0].astype(np.int32)
-    IV = len(invalid_np)
-    invalid = torch.from_numpy(invalid_np).to(dev) if IV else torch.zeros((1,), dtype=torch.int32, device=dev)
+    if on_device:
+        invalid = mu.zero_count_vertices(count)
+        IV = invalid.shape[0]
+        if IV == 0:
+            invalid = torch.zeros((1,), dtype=torch.int32, device=dev)
+    else:
+        invalid_np = np.nonzero(count.cpu().numpy() == 0)[0].astype(np.int32)
+        IV = len(invalid_np)
+        invalid = torch.from_numpy(invalid_np).to(dev) if IV else torch.zeros((1,), dtype=torch.int32, device=dev)
     tmp = torch.empty((max(IV, 1) * 4,), device=dev)
     colored = torch.zeros((1,), dtype=torch.int32, device=dev)
     total, rounds, stage = V - IV, 0, "uncolored"
@@ -236,6 +268,8 @@ def paint_invisible_areas_by_neighbors(vertices, faces, uvs, face_uv_idx, to_inp
         if rounds > 10000:
             break
     if not use_atlas:
+        if on_device:
+            return sv, sf, colors
         return torch.from_numpy(sv).to(dev), torch.from_numpy(sf).to(dev).long(), colors
     owner = torch.empty((A * A,), dtype=torch.int32, device=dev)
     check(L.pdhip_scatter_vertex_colors(ptr(texel), ptr(colors), V, ptr(atlas), ptr(mask), ptr(owner), A, stream()),
