@@ -58,6 +58,20 @@ namespace { LabMark pd_lab_mark_; }
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// ---- caller-allocated workspaces: a unit's carve function hands out its regions through one Carve, and both the unit's
+// _ws_bytes query (base == nullptr: sizes only) and its entry (base == ws) call that function, so size and layout cannot disagree.
+struct Carve {
+    char* base;
+    size_t off;
+    template <class T> T* take(size_t n) {                         // n elements at the next multiple of 256 bytes
+        off = bytes();
+        T* p = reinterpret_cast<T*>(base ? base + off : nullptr);
+        off += n * sizeof(T);
+        return p;
+    }
+    size_t bytes() const { return (off + 255) & ~(size_t)255; }    // everything taken so far, rounded up to 256
+};
+
 // ---- arithmetic contract: float32, one rounding per op, this order, no FMA.
 // All geometry translation units are compiled with -ffp-contract=off.
 struct Cam {

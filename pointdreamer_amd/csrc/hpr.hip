@@ -31,6 +31,7 @@
 // wave-cooperative f64 scans) -> 0.38 ms; all points queried: 17 -> 1.3 ms.
 // The order of the sorted support set inside a Morton cell comes from atomics; the scans break ties by cloud index and every
 // verdict is certified, so the visibility does not depend on it (the fallback counters may differ by a query between runs).
+#include <stddef.h>
 #include "common.h"
 using namespace pdhip;
 
@@ -1500,18 +1501,60 @@ __global__ void k_hpr_extremes_fin(const double* __restrict__ flipped, int N, co
     cidx[(size_t)v * HPR_KC + pos] = id;
 }
 
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
-static size_t flipped_bytes(int V, int N) { return a256((size_t)V * 3 * (size_t)(N > 0 ? N : 1) * sizeof(double)); }
-static size_t lists_bytes(int V, int N) { return a256((size_t)V * ((size_t)N + 64) * sizeof(int)); }
-static size_t boxes_bytes(int V, int N) { return a256((size_t)V * (size_t)((N + 63) / 64 + 1) * HPR_BOX_FLOATS * sizeof(float)); }
-static size_t hist_bytes(int V) { return a256((size_t)V * HPR_NCELL * sizeof(int)); }
-// workspace head: counters int[64][4] (double-double queries, unresolved, double-double rounds, f64 distance-iteration queries),
-// maxabs u64[64] at 1024, bounding-box keys u64[64][6] at 2048, six per-view counters int[64] at 5120
-#define HPR_HEAD_BYTES 8192
+// workspace head, at offset 0 (pdhip_hpr_read_counters reads `counters` from the workspace pointer itself)
+struct HprHead {
+    int counters[64][4];                  // per view: double-double queries, unresolved, double-double rounds, f64 distance-iteration queries
+    unsigned long long maxabs[64];
+    unsigned long long pad0_[64];
+    unsigned long long bbox[64][6];       // order keys of max(-x), max(-y), max(-z), max(x), max(y), max(z)
+    int count[6][64];                     // six per-view counters
+    char pad1_[1536];
+};
+static_assert(offsetof(HprHead, counters) == 0 && offsetof(HprHead, maxabs) == 1024 && offsetof(HprHead, bbox) == 2048 &&
+              offsetof(HprHead, count) == 5120 && sizeof(HprHead) == 8192, "the head keeps its layout: 8 KiB, counters first");
+struct HprWs {
+    HprHead* head;
+    int *hist, *pos_of, *mdir, *list, *list2, *sidx, *ulist, *useed, *u2list, *u2seed, *cellkey, *cidx;
+    uint8_t* outside;
+    float4 *csf, *boxes, *f32pts;
+    unsigned long long *sgrid, *ekeys;
+    double *flipped, *ss, *csd, *fdir, *qdir;
+    size_t zero_bytes;                    // everything that must start at zero sits at the front of the workspace: one fill
+};
+static size_t carve_hpr(HprWs& w, void* base, int V, int N) {
+    const size_t n1 = N > 0 ? N : 1;
+    const size_t lists = ((size_t)V * ((size_t)N + 64) + 63) & ~(size_t)63;   // ints of a per-view list, whole 256-byte lines (the seeds: four lists)
+    Carve c{static_cast<char*>(base), 0};
+    w.head = c.take<HprHead>(1);
+    w.hist = c.take<int>((size_t)V * HPR_NCELL);
+    w.outside = c.take<uint8_t>((size_t)V * N);
+    w.csf = c.take<float4>((size_t)V * HPR_KC);                    // (entries past the set's end: the eye)
+    w.pos_of = c.take<int>(lists);                                 // (the extremes' claim flags until the scatter fills it)
+    w.mdir = c.take<int>(lists);
+    w.sgrid = c.take<unsigned long long>((size_t)V * HPR_GRID * HPR_GRID);
+    w.zero_bytes = c.bytes();
+    w.flipped = c.take<double>((size_t)V * 3 * n1);
+    w.ss = c.take<double>((size_t)V * 3 * n1);                     // level-2 support set, cell-sorted
+    w.list = c.take<int>(lists);
+    w.list2 = c.take<int>(lists);
+    w.sidx = c.take<int>(lists);
+    w.ulist = c.take<int>(lists);                                  // queries for the f64 distance iteration of level 3
+    w.useed = c.take<int>(4 * lists);                              // ... and the simplex each stopped at
+    w.u2list = c.take<int>(lists);                                 // queries for the double-double iteration
+    w.u2seed = c.take<int>(4 * lists);
+    w.cellkey = c.take<int>(lists);
+    w.csd = c.take<double>((size_t)V * HPR_KC * 4);
+    w.cidx = c.take<int>((size_t)V * HPR_KC);
+    w.boxes = c.take<float4>((size_t)V * (size_t)((N + 63) / 64 + 1) * (HPR_BOX_FLOATS / 4));
+    w.fdir = c.take<double>((size_t)HPR_KC * 4);
+    w.qdir = c.take<double>((size_t)V * 3 * n1);
+    w.ekeys = c.take<unsigned long long>((size_t)HPR_EXT_SLABS * V * HPR_KC);   // [slab][V][KC]
+    w.f32pts = c.take<float4>((size_t)V * n1);
+    return c.bytes();
+}
 extern "C" size_t pdhip_hpr_ws_bytes(int V, int N) {
-    return HPR_HEAD_BYTES + 3 * flipped_bytes(V, N) + 16 * lists_bytes(V, N) + a256((size_t)V * N) + a256((size_t)V * HPR_KC * sizeof(float4)) + a256((size_t)V * HPR_KC * 4 * sizeof(double)) + a256((size_t)HPR_EXT_SLABS * V * HPR_KC * sizeof(unsigned long long)) + a256((size_t)V * (size_t)(N > 0 ? N : 1) * sizeof(float4)) +
-           a256((size_t)V * HPR_KC * sizeof(int)) + boxes_bytes(V, N) + hist_bytes(V) + a256((size_t)HPR_KC * 4 * sizeof(double)) +
-           a256((size_t)V * HPR_GRID * HPR_GRID * sizeof(unsigned long long));
+    HprWs w;
+    return carve_hpr(w, nullptr, V, N);
 }
 
 static int hpr_impl(const float* points, int N, const double* eyes_dev, int V, int vps, double radius, const uint8_t* skip, uint8_t* visibility,
@@ -1534,59 +1577,33 @@ static int hpr_impl(const float* points, int N, const double* eyes_dev, int V, i
     PD_REQUIRE(points && eyes_dev && visibility && ws, "pdhip_hidden_point_removal: null pointer");
     PD_REQUIRE(V <= 64, "pdhip_hidden_point_removal: at most 64 views");
     hipStream_t s = as_stream(stream);
-    // everything that must start at zero sits at the front of the workspace: one fill
-    char* p = reinterpret_cast<char*>(ws);
-    int* counters = reinterpret_cast<int*>(p);
-    unsigned long long* maxabs = reinterpret_cast<unsigned long long*>(p + 1024);
-    unsigned long long* bbox = reinterpret_cast<unsigned long long*>(p + 2048);
-    int* count = reinterpret_cast<int*>(p + 5120);                 // six per-view counters of 64 ints each
-    int* count2 = count + 64; int* scount = count + 128; int* ucount = count + 192; int* u2count = count + 256; int* kcount = count + 320;
-    p += HPR_HEAD_BYTES;
-    int* hist = reinterpret_cast<int*>(p); p += hist_bytes(V);
-    uint8_t* outside = reinterpret_cast<uint8_t*>(p); p += a256((size_t)V * N);
-    float4* csf = reinterpret_cast<float4*>(p); p += a256((size_t)V * HPR_KC * sizeof(float4));      // (entries past the set's end: the eye)
-    int* pos_of = reinterpret_cast<int*>(p); p += lists_bytes(V, N);   // (the extremes' claim flags until the scatter fills it)
-    int* mdir = reinterpret_cast<int*>(p); p += lists_bytes(V, N);
-    unsigned long long* sgrid = reinterpret_cast<unsigned long long*>(p); p += a256((size_t)V * HPR_GRID * HPR_GRID * sizeof(unsigned long long));
-    const size_t zero_bytes = (size_t)(p - reinterpret_cast<char*>(ws));
-    double* flipped = reinterpret_cast<double*>(p); p += flipped_bytes(V, N);
-    double* ss = reinterpret_cast<double*>(p); p += flipped_bytes(V, N);          // level-2 support set, cell-sorted
-    int* list = reinterpret_cast<int*>(p); p += lists_bytes(V, N);
-    int* list2 = reinterpret_cast<int*>(p); p += lists_bytes(V, N);
-    int* sidx = reinterpret_cast<int*>(p); p += lists_bytes(V, N);
-    int* ulist = reinterpret_cast<int*>(p); p += lists_bytes(V, N);               // queries for the f64 distance iteration of level 3
-    int* useed = reinterpret_cast<int*>(p); p += 4 * lists_bytes(V, N);           // ... and the simplex each stopped at
-    int* u2list = reinterpret_cast<int*>(p); p += lists_bytes(V, N);              // queries for the double-double iteration
-    int* u2seed = reinterpret_cast<int*>(p); p += 4 * lists_bytes(V, N);
-    int* cellkey = reinterpret_cast<int*>(p); p += lists_bytes(V, N);
-    double* csd = reinterpret_cast<double*>(p); p += a256((size_t)V * HPR_KC * 4 * sizeof(double));
-    int* cidx = reinterpret_cast<int*>(p); p += a256((size_t)V * HPR_KC * sizeof(int));
-    float4* boxes = reinterpret_cast<float4*>(p); p += boxes_bytes(V, N);
-    double* fdir = reinterpret_cast<double*>(p); p += a256((size_t)HPR_KC * 4 * sizeof(double));
-    double* qdir = reinterpret_cast<double*>(p); p += flipped_bytes(V, N);
-    unsigned long long* ekeys = reinterpret_cast<unsigned long long*>(p); p += a256((size_t)HPR_EXT_SLABS * V * HPR_KC * sizeof(unsigned long long));   // [slab][V][KC]
-    float4* f32pts = reinterpret_cast<float4*>(p); p += a256((size_t)V * (size_t)(N > 0 ? N : 1) * sizeof(float4));
+    HprWs w;
+    carve_hpr(w, ws, V, N);
+    HprHead* h = w.head;
+    int* counters = &h->counters[0][0];
+    unsigned long long *maxabs = h->maxabs, *bbox = &h->bbox[0][0];
+    int *count = h->count[0], *count2 = h->count[1], *scount = h->count[2], *ucount = h->count[3], *u2count = h->count[4], *kcount = h->count[5];
     dim3 gf(V, min(cdiv(N, 256), 256));      // (the view is the FASTEST grid index in these kernels: workgroup b runs on XCD b % 8, so with 8 views an XCD's L2 holds ONE view's flipped cloud / grid / support set -- k_hpr_shield fetched 12x its input when every XCD touched every view)
     const bool two_level = N > 4 * HPR_KC;   // the coarse level pays off only when the cloud is much larger than the coarse set
-    PD_HIP(hipMemsetAsync(ws, 0, zero_bytes, s));
+    PD_HIP(hipMemsetAsync(ws, 0, w.zero_bytes, s));
     k_hpr_flip<<<dim3(V, min(cdiv(N, 1024), 64)), 1024, 0, s>>>
-       (points, N, eyes_dev, radius, flipped, maxabs, bbox, skip, count, list, visibility, two_level ? 0 : 1, two_level ? f32pts : nullptr, vps);      // (one level: + marks the skipped points visible; `list` = the queries)
+       (points, N, eyes_dev, radius, w.flipped, maxabs, bbox, skip, count, w.list, visibility, two_level ? 0 : 1, two_level ? w.f32pts : nullptr, vps);      // (one level: + marks the skipped points visible; `list` = the queries)
     constexpr int KC = HPR_KC;
     if (two_level) {
-        k_hpr_grid<<<gf, 256, 0, s>>>(flipped, N, bbox, sgrid, fdir);
-        k_hpr_shield<<<dim3(V, min(cdiv(N, 1024), 64)), 1024, 0, s>>>(flipped, N, bbox, sgrid, skip, count, list, visibility, counters);
+        k_hpr_grid<<<gf, 256, 0, s>>>(w.flipped, N, bbox, w.sgrid, w.fdir);
+        k_hpr_shield<<<dim3(V, min(cdiv(N, 1024), 64)), 1024, 0, s>>>(w.flipped, N, bbox, w.sgrid, skip, count, w.list, visibility, counters);
         const int slab_points = ext_slab_points(N), slabs = cdiv(N, slab_points);
-        k_hpr_extremes<<<dim3(slabs, KC / 256, V), 256, 0, s>>>(f32pts, N, fdir, slab_points, ekeys);
-        k_hpr_extremes_fin<<<dim3(KC / 256, V), 256, 0, s>>>(flipped, N, ekeys, slabs, csf, csd, cidx, kcount, pos_of, mdir);
-        k_hpr_coarse<2><<<dim3(V, cdiv(N, 256)), 256, 0, s>>>(flipped, N, count, list, csf, csd, cidx, kcount, outside, visibility, maxabs, qdir);
+        k_hpr_extremes<<<dim3(slabs, KC / 256, V), 256, 0, s>>>(w.f32pts, N, w.fdir, slab_points, w.ekeys);
+        k_hpr_extremes_fin<<<dim3(KC / 256, V), 256, 0, s>>>(w.flipped, N, w.ekeys, slabs, w.csf, w.csd, w.cidx, kcount, w.pos_of, w.mdir);
+        k_hpr_coarse<2><<<dim3(V, cdiv(N, 256)), 256, 0, s>>>(w.flipped, N, count, w.list, w.csf, w.csd, w.cidx, kcount, w.outside, visibility, maxabs, w.qdir);
     }
-    k_hpr_bin<<<dim3(V, min(cdiv(N, 1024), 64)), 1024, 0, s>>>(flipped, N, two_level ? outside : nullptr, skip, bbox, cellkey, hist, count2, list2, visibility);
-    k_hpr_cellscan<<<V, 1024, 0, s>>>(hist, scount);
-    k_hpr_scatter<<<gf, 256, 0, s>>>(flipped, N, cellkey, hist, ss, sidx, pos_of);
-    k_hpr_boxes<<<dim3(cdiv(cdiv(N, 64), 4), V), 256, 0, s>>>(ss, N, scount, boxes);
-    k_hpr_fine_dist<<<dim3(V, min(cdiv(N, 4), 512)), 256, 0, s>>>(flipped, N, count2, list2, visibility, ss, sidx, scount, boxes, pos_of, two_level ? mdir : nullptr, fdir, two_level ? qdir : nullptr, maxabs, ucount, ulist, useed);
-    k_hpr_exact<double><<<dim3(64, V), 64, 0, s>>>(flipped, N, ucount, ulist, useed, visibility, ss, sidx, N, scount, boxes, pos_of, maxabs, u2count, u2list, u2seed, counters);
-    k_hpr_exact<dd><<<dim3(32, V), 512, 0, s>>>(flipped, N, u2count, u2list, u2seed, visibility, ss, sidx, N, scount, boxes, pos_of, maxabs, nullptr, nullptr, nullptr, counters);
+    k_hpr_bin<<<dim3(V, min(cdiv(N, 1024), 64)), 1024, 0, s>>>(w.flipped, N, two_level ? w.outside : nullptr, skip, bbox, w.cellkey, w.hist, count2, w.list2, visibility);
+    k_hpr_cellscan<<<V, 1024, 0, s>>>(w.hist, scount);
+    k_hpr_scatter<<<gf, 256, 0, s>>>(w.flipped, N, w.cellkey, w.hist, w.ss, w.sidx, w.pos_of);
+    k_hpr_boxes<<<dim3(cdiv(cdiv(N, 64), 4), V), 256, 0, s>>>(w.ss, N, scount, w.boxes);
+    k_hpr_fine_dist<<<dim3(V, min(cdiv(N, 4), 512)), 256, 0, s>>>(w.flipped, N, count2, w.list2, visibility, w.ss, w.sidx, scount, w.boxes, w.pos_of, two_level ? w.mdir : nullptr, w.fdir, two_level ? w.qdir : nullptr, maxabs, ucount, w.ulist, w.useed);
+    k_hpr_exact<double><<<dim3(64, V), 64, 0, s>>>(w.flipped, N, ucount, w.ulist, w.useed, visibility, w.ss, w.sidx, N, scount, w.boxes, w.pos_of, maxabs, u2count, w.u2list, w.u2seed, counters);
+    k_hpr_exact<dd><<<dim3(32, V), 512, 0, s>>>(w.flipped, N, u2count, w.u2list, w.u2seed, visibility, w.ss, w.sidx, N, scount, w.boxes, w.pos_of, maxabs, nullptr, nullptr, nullptr, counters);
     PD_LAUNCH_CHECK();
     return PDHIP_OK;
 }
@@ -1596,10 +1613,11 @@ static int hpr_impl(const float* points, int N, const double* eyes_dev, int V, i
 // rounds, out[3] = queries sent to the f64 distance iteration (level 3's first stage)
 extern "C" int pdhip_hpr_read_counters(const void* ws, int V, long long* out /*[4]*/, void* stream) {
     PD_REQUIRE(ws && out && V > 0 && V <= 64, "pdhip_hpr_read_counters: bad arguments");
-    int h[64 * 4];
-    PD_HIP(hipMemcpyAsync(h, ws, sizeof(int) * 4 * V, hipMemcpyDeviceToHost, as_stream(stream)));
+    int h[64][4];
+    PD_HIP(hipMemcpyAsync(h, static_cast<const HprHead*>(ws)->counters, sizeof(h[0]) * V, hipMemcpyDeviceToHost, as_stream(stream)));
     PD_HIP(hipStreamSynchronize(as_stream(stream)));
     out[0] = out[1] = out[2] = out[3] = 0;
-    for (int v = 0; v < V; ++v) { out[0] += h[4 * v]; out[1] += h[4 * v + 1]; out[2] += h[4 * v + 2]; out[3] += h[4 * v + 3]; }
+    for (int v = 0; v < V; ++v)
+        for (int k = 0; k < 4; ++k) out[k] += h[v][k];
     return PDHIP_OK;
 }

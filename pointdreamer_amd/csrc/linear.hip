@@ -509,11 +509,32 @@ __global__ __launch_bounds__(64) void k_linear_boundary(const float* __restrict_
     }
 }
 
+struct LinearWs {
+    float* sites;
+    int *qlist, *counts, *unresolved, *bcount, *blist, *rowstart, *rowq, *fbcount;
+    uint8_t* todo;
+};
+static size_t carve_linear(LinearWs& w, void* base, int B, int H, int W) {
+    const size_t n = (size_t)H * W;
+    Carve c{static_cast<char*>(base), 0};
+    w.sites = c.take<float>((size_t)B * 3 * n);
+    w.qlist = c.take<int>((size_t)B * n);
+    w.counts = c.take<int>(2 * (size_t)B);
+    w.unresolved = c.take<int>(2);                          // queries that hit the round cap (pdhip_linear_fill_unresolved), then ...
+    w.bcount = w.unresolved + 1;                            // ... the length of blist: cleared together
+    w.blist = c.take<int>((size_t)B * n * 3);
+    w.rowstart = c.take<int>((size_t)B * (H + 1));
+    w.rowq = c.take<int>((size_t)B * (H + 1));
+    w.fbcount = c.take<int>(2 * (size_t)B);
+    w.todo = c.take<uint8_t>((size_t)B * n);
+    return c.bytes();
+}
+
 }  // namespace
 
 extern "C" size_t pdhip_linear_fill_ws_bytes(int B, int H, int W) {
-    return (size_t)B * 3 * H * W * sizeof(float) + (size_t)B * H * W * sizeof(int) + (size_t)(2 * B + 64) * sizeof(int) +
-           (size_t)B * H * W * 3 * sizeof(int) + 2 * (size_t)B * (H + 1) * sizeof(int) + (size_t)2 * B * sizeof(int) + (size_t)B * H * W;
+    LinearWs w;
+    return carve_linear(w, nullptr, B, H, W);
 }
 static thread_local int g_linear_local = 1;             // tuning / test hook: 0 = global scans only (the round-2 path), 2 = one local pass (the 48 x 48 window only: round 3), 1 = two
 extern "C" int pdhip_debug_set_linear_local(int on) { int old = g_linear_local; g_linear_local = on; return old; }
@@ -526,45 +547,38 @@ extern "C" int pdhip_linear_fill(const float* img, float* out, int B, int C, int
     PD_REQUIRE(img && out && mask && ws && img != out, "pdhip_linear_fill: bad pointers");
     hipStream_t s = as_stream(stream);
     const int n = H * W;
-    float* sites = reinterpret_cast<float*>(ws);
-    int* qlist = reinterpret_cast<int*>(sites + (size_t)B * 3 * n);
-    int* counts = qlist + (size_t)B * n;
-    int* unresolved = counts + 2 * B;
-    int* bcount = unresolved + 1;
-    int* blist = counts + 2 * B + 64;
-    int* rowstart = blist + (size_t)B * n * 3;
-    int* rowq = rowstart + (size_t)B * (H + 1);
-    int* fbcount = rowq + (size_t)B * (H + 1);
-    uint8_t* todo = reinterpret_cast<uint8_t*>(fbcount + 2 * (size_t)B);
+    LinearWs w;
+    carve_linear(w, ws, B, H, W);
     const bool local = g_linear_local != 0 && W < 65536 && H < 65536;
-    PD_HIP(hipMemsetAsync(unresolved, 0, 2 * sizeof(int), s));
-    k_linear_rowcount<<<dim3(cdiv(H, 4), B), 256, 0, s>>>(mask, mask_is_f32, mask_batch_stride, H, W, rowstart);
-    k_linear_rowscan<<<B, 1024, 0, s>>>(H, W, rowstart, rowq, counts, fbcount);
-    k_linear_rowwrite<<<dim3(cdiv(H, 4), B), 256, 0, s>>>(mask, mask_is_f32, mask_batch_stride, H, W, rowstart, rowq, sites, qlist, local ? 0 : 1);
+    PD_HIP(hipMemsetAsync(w.unresolved, 0, 2 * sizeof(int), s));
+    k_linear_rowcount<<<dim3(cdiv(H, 4), B), 256, 0, s>>>(mask, mask_is_f32, mask_batch_stride, H, W, w.rowstart);
+    k_linear_rowscan<<<B, 1024, 0, s>>>(H, W, w.rowstart, w.rowq, w.counts, w.fbcount);
+    k_linear_rowwrite<<<dim3(cdiv(H, 4), B), 256, 0, s>>>(mask, mask_is_f32, mask_batch_stride, H, W, w.rowstart, w.rowq, w.sites, w.qlist, local ? 0 : 1);
     k_linear_copy_sites<<<dim3(min(cdiv(n, 256), 1024), B), 256, 0, s>>>(img, out, mask, mask_is_f32, mask_batch_stride, C, n, tri);
     if (local) {
         // local pass over 16 x 16 tiles (window sites in LDS); what it cannot certify lands in the fallback list (written over the unused
         // query list), which the global kernel then finishes with (NS, count) = fbcount
         const int tiles = cdiv(W, LT) * cdiv(H, LT), tiles1 = cdiv(W, LT1) * cdiv(H, LT1);
         if (g_linear_local == 2)
-            k_linear_local<LW, LT, false, false><<<dim3(cdiv(tiles, 4), B), 256, 0, s>>>(img, out, C, H, W, mask, mask_is_f32, mask_batch_stride, rowstart, tri, qlist, fbcount, todo);
+            k_linear_local<LW, LT, false, false><<<dim3(cdiv(tiles, 4), B), 256, 0, s>>>(img, out, C, H, W, mask, mask_is_f32, mask_batch_stride, w.rowstart, tri, w.qlist, w.fbcount, w.todo);
         else {
             // (every pixel the second pass reads was written by the first: sites and background are never queries, their bytes are never read)
-            PD_HIP(hipMemsetAsync(todo, 0, (size_t)B * n, s));
-            k_linear_local<LW1, LT1, false, true><<<dim3(cdiv(tiles1, 4), B), 256, 0, s>>>(img, out, C, H, W, mask, mask_is_f32, mask_batch_stride, rowstart, tri, qlist, fbcount, todo);
-            k_linear_local<LW, LT, true, false><<<dim3(cdiv(tiles, 4), B), 256, 0, s>>>(img, out, C, H, W, mask, mask_is_f32, mask_batch_stride, rowstart, tri, qlist, fbcount, todo);
+            PD_HIP(hipMemsetAsync(w.todo, 0, (size_t)B * n, s));
+            k_linear_local<LW1, LT1, false, true><<<dim3(cdiv(tiles1, 4), B), 256, 0, s>>>(img, out, C, H, W, mask, mask_is_f32, mask_batch_stride, w.rowstart, tri, w.qlist, w.fbcount, w.todo);
+            k_linear_local<LW, LT, true, false><<<dim3(cdiv(tiles, 4), B), 256, 0, s>>>(img, out, C, H, W, mask, mask_is_f32, mask_batch_stride, w.rowstart, tri, w.qlist, w.fbcount, w.todo);
         }
-        k_linear_tri<<<dim3(cdiv(n, 4 * LQ), B), 256, 0, s>>>(img, out, C, H, W, sites, qlist, fbcount, tri, unresolved, bcount, blist);
+        k_linear_tri<<<dim3(cdiv(n, 4 * LQ), B), 256, 0, s>>>(img, out, C, H, W, w.sites, w.qlist, w.fbcount, tri, w.unresolved, w.bcount, w.blist);
     } else
-    k_linear_tri<<<dim3(cdiv(n, 4 * LQ), B), 256, 0, s>>>(img, out, C, H, W, sites, qlist, counts, tri, unresolved, bcount, blist);
-    k_linear_boundary<<<256, 64, 0, s>>>(img, out, C, H, W, sites, counts, bcount, blist, tri);
+    k_linear_tri<<<dim3(cdiv(n, 4 * LQ), B), 256, 0, s>>>(img, out, C, H, W, w.sites, w.qlist, w.counts, tri, w.unresolved, w.bcount, w.blist);
+    k_linear_boundary<<<256, 64, 0, s>>>(img, out, C, H, W, w.sites, w.counts, w.bcount, w.blist, tri);
     PD_LAUNCH_CHECK();
     return PDHIP_OK;
 }
 extern "C" int pdhip_linear_fill_unresolved(const void* ws, int B, int H, int W, int* out, void* stream) {
     PD_REQUIRE(ws && out, "pdhip_linear_fill_unresolved: null pointer");
-    const int* p = reinterpret_cast<const int*>(reinterpret_cast<const float*>(ws) + (size_t)B * 3 * H * W) + (size_t)B * H * W + 2 * B;
-    PD_HIP(hipMemcpyAsync(out, p, sizeof(int), hipMemcpyDeviceToHost, as_stream(stream)));
+    LinearWs w;
+    carve_linear(w, const_cast<void*>(ws), B, H, W);
+    PD_HIP(hipMemcpyAsync(out, w.unresolved, sizeof(int), hipMemcpyDeviceToHost, as_stream(stream)));
     PD_HIP(hipStreamSynchronize(as_stream(stream)));
     return PDHIP_OK;
 }

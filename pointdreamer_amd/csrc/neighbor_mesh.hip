@@ -22,22 +22,6 @@ constexpr int ERR_PICK = 1, ERR_FACE = 2, ERR_TEX = 4;
 // misc words
 constexpr int M_ERR = 0, M_C0 = 1, M_WORDS = 8;                    // M_C0 .. M_C0 + 3: the counts as the host reads them
 
-struct Carve {
-    char* base;
-    size_t off;
-    template <class T> T* take(size_t n) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = reinterpret_cast<T*>(base ? base + off : nullptr);
-        off += n * sizeof(T);
-        return p;
-    }
-};
-
-static void carve_sort(Carve& c, SortBufs& sb, size_t N) {
-    sb.k[0] = c.take<uint64_t>(N); sb.k[1] = c.take<uint64_t>(N); sb.v[0] = c.take<int>(N); sb.v[1] = c.take<int>(N);
-    sb.hist = c.take<int>(2 * 256 * (size_t)cdiv((long long)N, RS_TILE));
-}
-
 // ---- subdivision -------------------------------------------------------------------------------------------------------------
 __global__ void k_nm_fill(int* __restrict__ p, int n, int value) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

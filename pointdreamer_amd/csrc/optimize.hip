@@ -405,13 +405,33 @@ __global__ __launch_bounds__(64) void k_oc_backward_adam(const int* __restrict__
     }
 }
 
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
-extern "C" size_t pdhip_optimize_color_ws_bytes(int V, int res, int A) {
+constexpr long long OC_TX_MAX = 4096LL * 1024;             // texels of the largest atlas
+struct OptWs {
+    float *target, *m, *v;
+    uint8_t *wmask, *sgn;
+    int *pix, *cntb, *boff, *cursor, *bsum, *npix;
+    float2* fxy;
+    float4 *tgt4, *at4;
+};
+static size_t carve_opt(OptWs& w, void* base, int V, int res, int A) {
     const size_t px = (size_t)V * res * res, tx = (size_t)A * A;
-    return a256(px * 3 * 4) /*target*/ + a256(px) /*wmask*/ + a256((px + 64) * 4) /*sorted pixel ids*/ + a256((px + 64) * 8) /*fractions*/ +
-           a256((px + 64) * 16) /*targets + base texel*/ + a256(px + 64) /*sign bytes*/ + 2 * a256(tx * 3 * 4) /*m, v*/ +
-           3 * a256((tx + 4096) * 4) /*bucket counts, offsets, cursor*/ + a256(16384 * 4) /*block sums*/ + a256(tx * 16) /*interleaved atlas*/ +
-           256 /*counters*/;
+    Carve c{static_cast<char*>(base), 0};
+    w.target = c.take<float>(px * 3);
+    w.wmask = c.take<uint8_t>(px);
+    w.pix = c.take<int>(px + 64);                            // sorted pixel ids
+    w.fxy = c.take<float2>(px + 64);                         // fractions
+    w.tgt4 = c.take<float4>(px + 64);                        // targets + base texel
+    w.sgn = c.take<uint8_t>(px + 64);                        // sign bytes
+    w.m = c.take<float>(tx * 3); w.v = c.take<float>(tx * 3);
+    w.cntb = c.take<int>(tx + 4096); w.boff = c.take<int>(tx + 4096); w.cursor = c.take<int>(tx + 4096);   // bucket counts, offsets, cursor
+    w.bsum = c.take<int>(OC_SCAN_MAXB);                      // block sums of oc_scan
+    w.at4 = c.take<float4>(tx);                              // interleaved atlas
+    w.npix = c.take<int>(64);                                // [0] masked pixels, [1] texels that receive a contribution
+    return c.bytes();
+}
+extern "C" size_t pdhip_optimize_color_ws_bytes(int V, int res, int A) {
+    OptWs w;
+    return carve_opt(w, nullptr, V, res, A);
 }
 
 extern "C" int pdhip_optimize_color(float* atlas /*[3,A,A] in/out*/, int A, const float* uv_map, const int64_t* face_idxs, int V,
@@ -419,56 +439,42 @@ extern "C" int pdhip_optimize_color(float* atlas /*[3,A,A] in/out*/, int A, cons
                                     float* final_images /*[V,3,res,res] or NULL*/, void* ws, void* stream) {
     PD_REQUIRE(atlas && uv_map && face_idxs && inpainted && ws && A > 0 && V > 0 && res > 0 && r > 0 && iterations >= 0,
                "pdhip_optimize_color: bad arguments");
-    PD_REQUIRE((long long)A * A <= 4096LL * 1024 && (long long)V * res * res <= (1LL << 30),
+    PD_REQUIRE((long long)A * A <= OC_TX_MAX && (long long)V * res * res <= (1LL << 30),
                "pdhip_optimize_color: atlas / view size too large (A^2 <= 4 Mi texels, V res^2 <= 1 Gi pixels)");
     hipStream_t s = as_stream(stream);
     const size_t px = (size_t)V * res * res, tx = (size_t)A * A;
-    char* p = reinterpret_cast<char*>(ws);
-    float* target = reinterpret_cast<float*>(p); p += a256(px * 3 * 4);
-    uint8_t* wmask = reinterpret_cast<uint8_t*>(p); p += a256(px);
-    int* pix = reinterpret_cast<int*>(p); p += a256((px + 64) * 4);
-    float2* fxy = reinterpret_cast<float2*>(p); p += a256((px + 64) * 8);
-    float4* tgt4 = reinterpret_cast<float4*>(p); p += a256((px + 64) * 16);
-    uint8_t* sgn = reinterpret_cast<uint8_t*>(p); p += a256(px + 64);
-    float* m = reinterpret_cast<float*>(p); p += a256(tx * 3 * 4);
-    float* vv = reinterpret_cast<float*>(p); p += a256(tx * 3 * 4);
-    int* cntb = reinterpret_cast<int*>(p); p += a256((tx + 4096) * 4);
-    int* boff = reinterpret_cast<int*>(p); p += a256((tx + 4096) * 4);
-    int* cursor = reinterpret_cast<int*>(p); p += a256((tx + 4096) * 4);
-    int* bsum = reinterpret_cast<int*>(p); p += a256(16384 * 4);
-    float4* at4 = reinterpret_cast<float4*>(p); p += a256(tx * 16);
-    int* npix = reinterpret_cast<int*>(p);                   // [0] masked pixels, [1] texels that receive a contribution
-    int* nact = npix + 1;
+    OptWs w;
+    carve_opt(w, ws, V, res, A);
     const long long n = 3LL * A * A;
-    PD_HIP(hipMemsetAsync(m, 0, n * 4, s));
-    PD_HIP(hipMemsetAsync(vv, 0, n * 4, s));
-    PD_HIP(hipMemsetAsync(cntb, 0, tx * 4, s));
-    PD_HIP(hipMemsetAsync(cursor, 0, tx * 4, s));
-    PD_HIP(hipMemsetAsync(npix, 0, 8, s));
+    PD_HIP(hipMemsetAsync(w.m, 0, n * 4, s));
+    PD_HIP(hipMemsetAsync(w.v, 0, n * 4, s));
+    PD_HIP(hipMemsetAsync(w.cntb, 0, tx * 4, s));
+    PD_HIP(hipMemsetAsync(w.cursor, 0, tx * 4, s));
+    PD_HIP(hipMemsetAsync(w.npix, 0, 8, s));
     if (final_images != nullptr) PD_HIP(hipMemsetAsync(final_images, 0, px * 3 * 4, s));
     dim3 g(min(cdiv((long long)res * res, 256), 2048), V);
-    k_optcolor_target<<<g, 256, 0, s>>>(inpainted, r, uv_map, face_idxs, res, shrinked, A, target, wmask);
+    k_optcolor_target<<<g, 256, 0, s>>>(inpainted, r, uv_map, face_idxs, res, shrinked, A, w.target, w.wmask);
     const int gp = min(cdiv((long long)px, 256), 8192);
     const int gt = min(cdiv((long long)tx, 256), 4096);
     // masked pixels -> buckets by base texel (counting sort, ascending pixel index inside a bucket) -> per-pixel arrays in that order
-    k_oc_count<<<gp, 256, 0, s>>>(uv_map, wmask, V, res, A, cntb);
-    OC_TRY(oc_scan(cntb, (int)tx, boff, bsum, npix, s));
-    PD_HIP(hipMemcpyAsync(boff + tx, npix, 4, hipMemcpyDeviceToDevice, s));
-    k_oc_scatter<<<gp, 256, 0, s>>>(uv_map, wmask, V, res, A, boff, cursor, pix);
+    k_oc_count<<<gp, 256, 0, s>>>(uv_map, w.wmask, V, res, A, w.cntb);
+    OC_TRY(oc_scan(w.cntb, (int)tx, w.boff, w.bsum, w.npix, s));
+    PD_HIP(hipMemcpyAsync(w.boff + tx, w.npix, 4, hipMemcpyDeviceToDevice, s));
+    k_oc_scatter<<<gp, 256, 0, s>>>(uv_map, w.wmask, V, res, A, w.boff, w.cursor, w.pix);
     const int gw = min(cdiv((long long)tx, 64), 16384);
-    k_oc_sortb<<<gw, 64, 0, s>>>(boff, (int)tx, pix);
-    k_oc_records<<<gp, 256, 0, s>>>(pix, npix, uv_map, target, res, A, fxy, tgt4);
-    k_oc_nactive<<<gt, 256, 0, s>>>(boff, A, (int)tx, nact);                 // (256 blocks: 184 us for this counter -- 16 dependent reads per thread)
-    k_oc_pack<<<gt, 256, 0, s>>>(atlas, (int)tx, at4);
+    k_oc_sortb<<<gw, 64, 0, s>>>(w.boff, (int)tx, w.pix);
+    k_oc_records<<<gp, 256, 0, s>>>(w.pix, w.npix, uv_map, w.target, res, A, w.fxy, w.tgt4);
+    k_oc_nactive<<<gt, 256, 0, s>>>(w.boff, A, (int)tx, w.npix + 1);                 // (256 blocks: 184 us for this counter -- 16 dependent reads per thread)
+    k_oc_pack<<<gt, 256, 0, s>>>(atlas, (int)tx, w.at4);
     const double inv_count = 1.0 / ((double)V * 3.0 * res * res);
     const int gf = min(cdiv((long long)px, 256 * OC_FW_PX), 8192);
     for (int it = 0; it < iterations; ++it) {
         const bool last = it == iterations - 1;
-        k_oc_forward<<<gf, 256, 0, s>>>(at4, A, fxy, tgt4, npix, sgn, pix, res, last ? final_images : nullptr);
+        k_oc_forward<<<gf, 256, 0, s>>>(w.at4, A, w.fxy, w.tgt4, w.npix, w.sgn, w.pix, res, last ? final_images : nullptr);
         const int step = it + 1;
         const double cur_lr = lr * pow(0.5, (double)(it / 15));            // StepLR(step_size 15, gamma 0.5)
         const double bc1 = 1.0 - pow(0.9, step), bc2 = 1.0 - pow(0.999, step);
-        k_oc_backward_adam<<<gw, 64, 0, s>>>(boff, A, (int)tx, fxy, sgn, inv_count, atlas, m, vv, (float)(cur_lr / bc1), (float)sqrt(bc2), at4);
+        k_oc_backward_adam<<<gw, 64, 0, s>>>(w.boff, A, (int)tx, w.fxy, w.sgn, inv_count, atlas, w.m, w.v, (float)(cur_lr / bc1), (float)sqrt(bc2), w.at4);
     }
     PD_LAUNCH_CHECK();
     return PDHIP_OK;

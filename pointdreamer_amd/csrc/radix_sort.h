@@ -1,6 +1,7 @@
-// Radix sort (LSD, 8-bit digits, stable) of 64-bit keys with int32 values, and a one-workgroup scan: shared by the geometry units that
-// sort on the device (uv_atlas.hip: edge keys, packing order, UV entries; surface_recon.hip: cell keys).  Written here because rocPRIM's
-// sort carries scratch on gfx950.  Every kernel has internal linkage: each including unit gets its own copy.
+// Radix sort (LSD, 8-bit digits, stable) of 64-bit keys with int32 values, a one-workgroup scan and a tiled exclusive scan over many
+// workgroups: shared by the geometry units that sort or scan on the device (uv_atlas.hip: edge keys, packing order, UV entries;
+// surface_recon.hip: cell keys, vertex / triangle offsets; neighbor_mesh.hip: edge and pair keys).  Written
+// here because rocPRIM's sort carries scratch on gfx950.  Every kernel has internal linkage: each including unit gets its own copy.
 #pragma once
 #include "common.h"
 
@@ -95,11 +96,56 @@ __global__ __launch_bounds__(SC_T) void k_scan(const int* __restrict__ in, int* 
     }
 }
 
+// exclusive scan of n ints over many workgroups: tiles of 2048 (their sums scanned by the one-workgroup k_scan), then the offsets added
+constexpr int SCB_T = 256, SCB_ITEMS = 8, SCB_TILE = SCB_T * SCB_ITEMS;
+__global__ __launch_bounds__(SCB_T) void k_scan_tiles(const int* __restrict__ in, int* __restrict__ out, long long n, int* __restrict__ sums) {
+    __shared__ int part[SCB_T];
+    const int t = threadIdx.x;
+    const long long base = (long long)blockIdx.x * SCB_TILE + (long long)t * SCB_ITEMS;
+    int v[SCB_ITEMS];
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < SCB_ITEMS; ++k) {
+        v[k] = s;
+        s += base + k < n ? in[base + k] : 0;
+    }
+    part[t] = s;
+    __syncthreads();
+    for (int off = 1; off < SCB_T; off <<= 1) {
+        const int add = t >= off ? part[t - off] : 0;
+        __syncthreads();
+        part[t] += add;
+        __syncthreads();
+    }
+    const int excl = part[t] - s;
+#pragma unroll
+    for (int k = 0; k < SCB_ITEMS; ++k)
+        if (base + k < n) out[base + k] = excl + v[k];
+    if (t == SCB_T - 1) sums[blockIdx.x] = part[t];
+}
+__global__ void k_scan_add(int* __restrict__ out, long long n, const int* __restrict__ offs) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] += offs[i / SCB_TILE];
+}
+// ints that tsum and toff must each hold for a scan of n elements (what a carve function takes for them)
+constexpr size_t scan_tiles(size_t n) { return n / SCB_TILE + 1; }
+// out[i] = in[0] + ... + in[i - 1] for 0 < n <= 2^31 elements whose sum fits an int
+static void scan_exclusive(const int* in, int* out, long long n, int* tsum, int* toff, hipStream_t s) {
+    const int nt = cdiv(n, SCB_TILE);
+    k_scan_tiles<<<nt, SCB_T, 0, s>>>(in, out, n, tsum);
+    k_scan<<<1, SC_T, 0, s>>>(tsum, toff, nt, 1);
+    k_scan_add<<<cdiv(n, 256), 256, 0, s>>>(out, n, toff);
+}
+
 struct SortBufs {
     uint64_t* k[2];
     int* v[2];
     int* hist;
 };
+static void carve_sort(Carve& c, SortBufs& sb, size_t N) {
+    sb.k[0] = c.take<uint64_t>(N); sb.k[1] = c.take<uint64_t>(N); sb.v[0] = c.take<int>(N); sb.v[1] = c.take<int>(N);
+    sb.hist = c.take<int>(2 * 256 * (size_t)cdiv((long long)N, RS_TILE));
+}
 
 static int bits_for(unsigned long long maxkey) {
     int b = 0;

@@ -29,31 +29,25 @@ struct SparseWs {
     int32_t* edge_list;   // [V][r*r] edge pixels (row * res + col), any order
 };
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static SparseWs carve(void* ws, int V, int N, int res, size_t* total) {
-    size_t off = 0;
-    char* base = (char*)ws;
-    size_t px = (size_t)V * res * res;
-    SparseWs w;
-    w.params = (ViewParams*)(base + off); off += align256(sizeof(ViewParams) * V);
-    w.counts = (uint32_t*)(base + off); off += align256(8 * (size_t)V);
-    w.mask_new = (uint8_t*)(base + off); off += align256(px);
-    w.winA = (uint32_t*)(base + off); off += align256(4 * px);
-    w.winB = (uint32_t*)(base + off); off += align256(4 * px);
-    w.nn_idx = (int32_t*)(base + off); off += align256(4 * px);
-    w.pp = (int32_t*)(base + off); off += align256(4 * (size_t)V * (N > 0 ? N : 1));
-    w.minidx = (uint32_t*)(base + off); off += align256(4 * px);
-    w.edge_cnt = (uint32_t*)(base + off); off += align256(4 * (size_t)V);
-    w.edge_list = (int32_t*)(base + off); off += align256(4 * px);
-    if (total) *total = off;
-    return w;
+static size_t carve_sparse(SparseWs& w, void* base, int V, int N, int res) {
+    const size_t px = (size_t)V * res * res;
+    Carve c{static_cast<char*>(base), 0};
+    w.params = c.take<ViewParams>(V);
+    w.counts = c.take<uint32_t>(2 * (size_t)V);
+    w.mask_new = c.take<uint8_t>(px);
+    w.winA = c.take<uint32_t>(px);
+    w.winB = c.take<uint32_t>(px);
+    w.nn_idx = c.take<int32_t>(px);
+    w.pp = c.take<int32_t>((size_t)V * (N > 0 ? N : 1));
+    w.minidx = c.take<uint32_t>(px);
+    w.edge_cnt = c.take<uint32_t>(V);
+    w.edge_list = c.take<int32_t>(px);
+    return c.bytes();
 }
 
 extern "C" size_t pdhip_sparse_views_ws_bytes(int V, int N, int res) {
-    size_t t = 0;
-    carve(nullptr, V, N, res, &t);
-    return t;
+    SparseWs w;
+    return carve_sparse(w, nullptr, V, N, res);
 }
 
 __global__ void k_sparse_counts(const uint8_t* __restrict__ hard, const uint8_t* __restrict__ valid, int N, int res,
@@ -391,7 +385,8 @@ static int sparse_impl(const int64_t* point_pixels, const float* colors, const u
     PD_REQUIRE(hard_masks && sparse && mask0 && mask2 && scale_factors && ws && (N == 0 || (point_pixels && colors && validation)),
                "pdhip_sparse_views: null pointer");
     hipStream_t s = as_stream(stream);
-    SparseWs w = carve(ws, V, N, res, nullptr);
+    SparseWs w;
+    carve_sparse(w, ws, V, N, res);
     const float thr = (float)mask_ratio_thresh;
     const float omt = (float)(1.0 - mask_ratio_thresh);
     k_sparse_counts<<<V, 1024, 0, s>>>(hard_masks, validation, N, res, thr, omt, w.params, w.counts);

@@ -595,38 +595,6 @@ __global__ void k_sr_mc_faces(const float* __restrict__ chi, int M, const int* _
     }
 }
 
-// exclusive scan of n ints over many workgroups: tiles of 2048 (their sums scanned by the one-workgroup k_scan), then the offsets added
-constexpr int SCB_T = 256, SCB_ITEMS = 8, SCB_TILE = SCB_T * SCB_ITEMS;
-__global__ __launch_bounds__(SCB_T) void k_sr_scan_tiles(const int* __restrict__ in, int* __restrict__ out, long long n, int* __restrict__ sums) {
-    __shared__ int part[SCB_T];
-    const int t = threadIdx.x;
-    const long long base = (long long)blockIdx.x * SCB_TILE + (long long)t * SCB_ITEMS;
-    int v[SCB_ITEMS];
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < SCB_ITEMS; ++k) {
-        v[k] = s;
-        s += base + k < n ? in[base + k] : 0;
-    }
-    part[t] = s;
-    __syncthreads();
-    for (int off = 1; off < SCB_T; off <<= 1) {
-        const int add = t >= off ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += add;
-        __syncthreads();
-    }
-    const int excl = part[t] - s;
-#pragma unroll
-    for (int k = 0; k < SCB_ITEMS; ++k)
-        if (base + k < n) out[base + k] = excl + v[k];
-    if (t == SCB_T - 1) sums[blockIdx.x] = part[t];
-}
-__global__ void k_sr_scan_add(int* __restrict__ out, long long n, const int* __restrict__ offs) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] += offs[i / SCB_TILE];
-}
-
 // colour of the nearest cloud point (ties: the first in cell order)
 __global__ void k_sr_nearest_color(const float* __restrict__ Q, int nq, const float4* __restrict__ spos, const int* __restrict__ cstart,
                                    const int* __restrict__ cend, CellGrid g, const float* __restrict__ colors, float* __restrict__ out) {
@@ -664,17 +632,6 @@ __global__ void k_sr_nearest_color(const float* __restrict__ Q, int nq, const fl
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-struct Carve {
-    char* base;
-    size_t off;
-    template <class T> T* take(size_t n) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = reinterpret_cast<T*>(base ? base + off : nullptr);
-        off += n * sizeof(T);
-        return p;
-    }
-};
-
 constexpr int CELLS_MAX = 128;                                     // cells per axis of a point cell list
 
 struct Cells {
@@ -684,8 +641,7 @@ struct Cells {
     double* mom;
 };
 static void carve_cells(Carve& c, Cells& w, int N) {
-    w.sb.k[0] = c.take<uint64_t>(N); w.sb.k[1] = c.take<uint64_t>(N); w.sb.v[0] = c.take<int>(N); w.sb.v[1] = c.take<int>(N);
-    w.sb.hist = c.take<int>(2 * 256 * (size_t)cdiv(N, RS_TILE));
+    carve_sort(c, w.sb, N);
     w.cstart = c.take<int>((size_t)CELLS_MAX * CELLS_MAX * CELLS_MAX);
     w.cend = c.take<int>((size_t)CELLS_MAX * CELLS_MAX * CELLS_MAX);
     w.spos = c.take<float4>(N);
@@ -777,7 +733,7 @@ static size_t carve_recon(ReconWs& w, void* base, int N, int depth) {
     w.part_ff = c.take<double>(CG_NB); w.part_rr[0] = c.take<double>(CG_NB); w.part_rr[1] = c.take<double>(CG_NB);
     w.part_pq = c.take<double>(CG_NB);
     w.misc = c.take<int>(M_WORDS);
-    w.tsum = c.take<int>(n3 / SCB_TILE + 1); w.toff = c.take<int>(n3 / SCB_TILE + 1);
+    w.tsum = c.take<int>(scan_tiles(n3)); w.toff = c.take<int>(scan_tiles(n3));
     return c.off + 256;
 }
 
@@ -900,15 +856,9 @@ extern "C" int pdhip_surface_recon(const float* points, const float* normals, co
     int* tbase = reinterpret_cast<int*>(w.f);
     k_sr_iso<<<1, CG_T, 0, s>>>(w.chi, G, points, N, w.misc);
     k_sr_mc_mark<<<gN3, TB, 0, s>>>(w.chi, M, w.misc, vcnt, w.eflag);
-    const int nt = cdiv(n3, SCB_TILE);
-    auto scan = [&](const int* in, int* out) {
-        k_sr_scan_tiles<<<nt, SCB_T, 0, s>>>(in, out, n3, w.tsum);
-        k_scan<<<1, SC_T, 0, s>>>(w.tsum, w.toff, nt, 1);
-        k_sr_scan_add<<<gN3, TB, 0, s>>>(out, n3, w.toff);
-    };
-    scan(vcnt, vbase);
+    scan_exclusive(vcnt, vbase, n3, w.tsum, w.toff, s);
     k_sr_mc_count<<<gN3, TB, 0, s>>>(w.chi, M, w.misc, tcnt);
-    scan(tcnt, tbase);
+    scan_exclusive(tcnt, tbase, n3, w.tsum, w.toff, s);
     k_sr_mc_totals<<<1, 64, 0, s>>>(vcnt, vbase, tcnt, tbase, n3, w.misc);
     k_sr_mc_vertices<<<gN3, TB, 0, s>>>(w.chi, G, w.misc, w.eflag, vbase, vertices, vertex_capacity);
     k_sr_mc_faces<<<gN3, TB, 0, s>>>(w.chi, M, w.misc, w.eflag, vbase, tcnt, tbase, faces, face_capacity);

@@ -515,17 +515,6 @@ __global__ void k_uva_finish(const int* __restrict__ chart, int32_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-struct Carve {
-    char* base;
-    size_t off;
-    template <class T> T* take(size_t n) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = reinterpret_cast<T*>(base ? base + off : nullptr);
-        off += n * sizeof(T);
-        return p;
-    }
-};
-
 struct Ws {
     int *idx, *lab[2], *adj, *par, *chart, *csize, *cmask, *cflag, *cpos, *hmin, *upper, *cstart, *flag, *incl, *misc;
     float *nrm, *fuv;
@@ -545,8 +534,7 @@ static size_t carve(Ws& w, void* base, int F) {
     w.flag = c.take<int>(N); w.incl = c.take<int>(N); w.misc = c.take<int>(M_WORDS);
     w.fuv = c.take<float>(6 * (size_t)F); w.box = c.take<unsigned>(4 * (size_t)F); w.tgt = c.take<unsigned long long>(F);
     w.tbox = c.take<short4>(F);
-    w.sb.k[0] = c.take<uint64_t>(N); w.sb.k[1] = c.take<uint64_t>(N); w.sb.v[0] = c.take<int>(N); w.sb.v[1] = c.take<int>(N);
-    w.sb.hist = c.take<int>(2 * 256 * (size_t)cdiv((long long)N, RS_TILE));
+    carve_sort(c, w.sb, N);
     return c.off + 256;
 }
 
