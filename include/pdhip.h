@@ -477,6 +477,22 @@ int pdhip_conv_rr_pack_f16(const void* w_packed, int Cin, int taps, int Cs, int 
 int pdhip_gn_octet_partials_f16(const void* x, int N, int HW, int C, int chunks, float* part, void* stream);
 int pdhip_gn_apply_parts_f16(const void* x, const void* x2, int Ca, int C, const float* partA, int chunksA, const float* partB, int chunksB, const float* gamma,
                              const float* beta, const float* film, long long film_stride, int N, int H, int W, int silu, void* y, void* stream);
+/* unit-test surface of conv_plan / conv_launch (csrc/nn_gemm.hip): pdhip_conv2d_nhwc_f16 with every operand a conv of the engine can carry.  The layer is
+ * planned under the debug hooks in force and launched as planned; nothing is routed here.  x2 / Cin1: second tensor of a never-materialised channel concat
+ * (1x1 only, Cin1 channels in x); residual read at half resolution with nearest x2 when res_up; xs / xs2 (Cs channels, Cs1 in xs; Cs == 0: none): the
+ * ResBlock's skip 1x1 appended to the K loop -- w_packed is then [Cout_pad][9 Cin + Cs] (the 3x3 rows of pdhip_pack_conv_weight_f16 followed by the 1x1 rows)
+ * and bias the sum of both.  ws (may be NULL): >= 4096 zeroed floats (tickets) + the split-K partials.  gn_part (may be NULL): octet partials of y,
+ * [N][chunks][Cout / 8][2]; gn_part_floats: the floats the caller keeps there.  *kernel = the plan's kernel (0 halo, 1 rr, 2 ht, 3 sk, 4 igemm, 5 phase),
+ * *gn_chunks = chunks per image: the plan's when the call is refused, what the launcher left otherwise.  PDHIP_E_ARG and no launch when the planned kernel
+ * does not take an operand that was passed (x2, res_up, xs; a residual next to xs) or when gn_part_floats < N * chunks * (Cout / 8) * 2 -- a negative
+ * gn_part_floats next to a gn_part therefore only plans (host-only, no device needed). */
+int pdhip_debug_conv_launch_nhwc_f16(const void* x, const void* x2, int Cin1, const void* w_packed, const float* bias, const void* residual, int res_up,
+                                     const void* xs, const void* xs2, int Cs1, int Cs, void* y, int N, int H, int W, int Cin, int Cout, int Cout_pad, int taps,
+                                     const void* zero_page, float* ws, long long ws_floats, float* gn_part, long long gn_part_floats, int* gn_chunks, int* kernel,
+                                     void* stream);
+/* GroupNorm(32) statistics [N][32][2] = (mean, rstd), eps 1e-5, from the octet partials of one tensor (partB NULL, Cb 0) or of the two tensors of a channel
+ * concat [A (Ca channels, chunksA chunks per image) | B (Cb, chunksB)]: the k_gn_finalize_oct launch of the engine.  (Ca + Cb) / 32 a multiple of 8. */
+int pdhip_gn_finalize_oct_f32(const float* partA, int Ca, int chunksA, const float* partB, int Cb, int chunksB, int N, int HW, float* stats, void* stream);
 /* 3x3 conv of the UNet's 64^2 / 128^2 levels at small batch on 256-pixel x 64-channel halo tiles (csrc/nn_conv_ht.hip; nn.Conv2d(k=3, padding=1) of
  * ResBlock.in_layers / out_layers, guided_diffusion/unet.py:185-260): x [N,H,W,Cin] f16, w_packed [Cout_pad][9 * Cin] from pdhip_pack_conv_weight_f16 (Cout_pad % 64 == 0),
  * H == W in {32, 64, 128}; residual optional (res_up: read at half resolution); splitk_ws (may be NULL: K unsplit): >= 4096 + tiles * slabs * 16384 floats, the first 4096

@@ -1019,6 +1019,46 @@ extern "C" int pdhip_conv2d_nhwc_f16(const void* x, const void* w_packed, const 
     return conv_igemm((const half_t*)x, (const half_t*)w_packed, bias, (const half_t*)residual, (half_t*)y, N, H, W, Cin, Cout,
                       Cout_pad, taps, (const half_t*)zero_page, as_stream(stream), pdnn::g_dbg_splitk_ws, pdnn::g_dbg_splitk_floats);
 }
+/* test entry: conv_plan + conv_launch with every operand ConvArgs carries (include/pdhip.h).  What the planned kernel would drop silently is refused. */
+extern "C" int pdhip_debug_conv_launch_nhwc_f16(const void* x, const void* x2, int Cin1, const void* w_packed, const float* bias, const void* residual,
+                                                int res_up, const void* xs, const void* xs2, int Cs1, int Cs, void* y, int N, int H, int W, int Cin, int Cout,
+                                                int Cout_pad, int taps, const void* zero_page, float* ws, long long ws_floats, float* gn_part,
+                                                long long gn_part_floats, int* gn_chunks, int* kernel, void* stream) {
+    const char* const fn = "pdhip_debug_conv_launch_nhwc_f16";
+    PD_REQUIRE(x && w_packed && y && zero_page, "%s: null argument", fn);
+    PD_REQUIRE(N > 0 && H > 0 && W > 0 && (taps == 1 || taps == 9), "%s: bad shape (N=%d H=%d W=%d taps=%d)", fn, N, H, W, taps);
+    PD_REQUIRE(Cin % 32 == 0 && Cout % 8 == 0 && Cout_pad % 128 == 0 && Cout_pad >= Cout && Cin > 0 && Cout > 0,
+               "%s: need Cin %% 32 == 0, Cout %% 8 == 0, padded Cout %% 128 == 0 (Cin=%d Cout=%d pad=%d)", fn, Cin, Cout, Cout_pad);
+    PD_REQUIRE(x2 == nullptr || (taps == 1 && Cin1 > 0 && Cin1 < Cin && Cin1 % 64 == 0 && (Cin - Cin1) % 64 == 0),
+               "%s: a two-source input needs a 1x1 conv and channel counts that are multiples of 64", fn);
+    if (xs == nullptr) Cs = 0;
+    PD_REQUIRE(xs == nullptr || (taps == 9 && Cs > 0 && Cs % 64 == 0 && (xs2 == nullptr || (Cs1 > 0 && Cs1 < Cs && Cs1 % 64 == 0))),
+               "%s: a skip source needs a 3x3 conv and channel counts that are multiples of 64", fn);
+    PD_REQUIRE(xs != nullptr || xs2 == nullptr, "%s: xs2 without xs", fn);
+    PD_REQUIRE(xs == nullptr || residual == nullptr, "%s: the appended skip 1x1 takes the residual's place", fn);
+    PD_REQUIRE(res_up == 0 || residual != nullptr, "%s: res_up without a residual", fn);
+    const size_t wsf = ws != nullptr && ws_floats > 0 ? (size_t)ws_floats : 0;
+    pdnn::ConvNeeds nd;
+    nd.two_source = x2 != nullptr; nd.want_gn = gn_part != nullptr; nd.skip_cs = Cs;
+    const pdnn::ConvPlan p = conv_plan(N, H, W, Cin, Cout, Cout_pad, taps, nd, wsf);
+    if (kernel) *kernel = (int)p.kernel;
+    if (gn_chunks) *gn_chunks = p.gn_chunks;
+    PD_REQUIRE(res_up == 0 || p.takes_res_up, "%s: the planned kernel (%s) does not read its residual at half resolution", fn, conv_kernel_name(p.kernel));
+    PD_REQUIRE(Cs == 0 || p.takes_skip, "%s: the planned kernel (%s) does not append the skip 1x1", fn, conv_kernel_name(p.kernel));
+    PD_REQUIRE(x2 == nullptr || p.kernel == pdnn::CONV_SK || p.kernel == pdnn::CONV_IGEMM, "%s: the planned kernel (%s) reads one source", fn,
+               conv_kernel_name(p.kernel));
+    PD_REQUIRE(gn_part == nullptr || gn_part_floats >= (long long)N * p.gn_chunks * (Cout / 8) * 2,
+               "%s: gn_part holds %lld floats, the launch writes %lld", fn, gn_part_floats, (long long)N * p.gn_chunks * (Cout / 8) * 2);
+    const pdnn::ConvArgs a{(const half_t*)x, (const half_t*)x2, x2 ? Cin1 : 0, (const half_t*)w_packed, bias, (const half_t*)residual, res_up, nullptr, nullptr,
+                           (const half_t*)xs, (const half_t*)xs2, Cs1, (half_t*)y, (const half_t*)zero_page, wsf ? ws : nullptr, wsf, gn_part};
+    return conv_launch(p, a, as_stream(stream), gn_chunks);
+}
+extern "C" int pdhip_gn_finalize_oct_f32(const float* partA, int Ca, int chunksA, const float* partB, int Cb, int chunksB, int N, int HW, float* stats,
+                                         void* stream) {
+    PD_REQUIRE(partA && stats && N > 0 && HW > 0 && Ca > 0 && chunksA > 0, "pdhip_gn_finalize_oct_f32: bad arguments");
+    PD_REQUIRE(partB ? (Cb > 0 && chunksB > 0) : Cb == 0, "pdhip_gn_finalize_oct_f32: partB and Cb / chunksB disagree");
+    return gn_finalize_oct(partA, Ca, chunksA, partB, Cb, partB ? chunksB : 0, N, HW, 1e-5f, stats, as_stream(stream));
+}
 /* tuning / test hook: split-K workspace (device floats) for pdhip_conv2d_nhwc_f16 and a forced split factor (0 = automatic) */
 extern "C" int pdhip_debug_set_conv_splitk(void* ws, long long ws_floats, int splits) {
     int old = pdnn::g_force_splits;

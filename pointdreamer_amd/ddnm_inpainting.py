@@ -75,6 +75,9 @@ _reg('pdhip_gn_octet_partials_f16', C.c_int, [vp, i32, i32, i32, i32, vp, vp])
 _reg('pdhip_gn_apply_parts_f16', C.c_int, [vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, C.c_longlong, i32, i32, i32, i32, vp, vp])
 _reg('pdhip_conv_rr_f16', C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, C.c_longlong, vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp,
                                    i32, i32, i32, i32, vp, C.c_longlong, vp, C.POINTER(C.c_int), vp])
+_reg('pdhip_debug_conv_launch_nhwc_f16', C.c_int, [vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, C.c_longlong,
+                                                  vp, C.c_longlong, C.POINTER(C.c_int), C.POINTER(C.c_int), vp])
+_reg('pdhip_gn_finalize_oct_f32', C.c_int, [vp, i32, i32, vp, i32, i32, i32, i32, vp, vp])
 _reg('pdhip_debug_conv3x3_apply', C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp])
 _reg('pdhip_attention_f16', C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp])
 _reg('pdhip_philox_normal', C.c_int, [vp, C.c_longlong, u64, u64, vp])

@@ -374,7 +374,7 @@ def test_conv3x3_halo_kernel_vs_torch_fp32(nn, N, H, W, Cin, Cout, res, splits):
 def test_conv3x3_halo_tile_geometries_on_256_wide_images(nn, mode, N, H, Cin, Cout, res):
     """256-wide images: tiles of 4 rows x 128 columns (automatic) or full rows (1) -- strip borders inside
     the image must read their neighbours' columns, the image border the zero padding; the fused GroupNorm partials (one chunk per
-    tile) are covered by the UNet tests, which run the automatic geometry."""
+    tile) of both geometries are checked in tests/test_gpu_conv_epilogue.py."""
     L = nn['L']
     old = (L.pdhip_debug_set_conv_tile(32), L.pdhip_debug_set_conv_halo_strips(mode))
     try:
