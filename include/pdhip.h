@@ -506,7 +506,24 @@ int pdhip_debug_set_rr_gn(int max_width);   /* UNet engine: largest image width 
 int pdhip_debug_set_conv_rr(int mode, int variant, int slabs);   /* row-resident conv: mode 0 never / 1 automatic / 2 every eligible layer; variant 0 auto (1: 8^2, 2: 16^2 whole image, 3: 32^2 bands, 4: 16^2 half image, 5: 8^2 with 128-channel units); slabs 0 auto = K slices of the conv source; returns the previous mode */
 int pdhip_attention_f16(const void* qkv /*[N,T,3C]*/, void* out /*[N,T,C]*/, int N, int T, int C, int head_dim,
                         void* vt_ws /*N*T*C halfs, non-NULL selects the 128-query MFMA kernel for T % 128 == 0, head_dim 64, N*heads % 8 == 0 (QKVAttentionLegacy, unet.py:341-373); the buffer is written only in the transposed-V lab form (pdhip_debug_set_attn); NULL: the 64-query kernel*/, void* stream);
+/* out[i] = element i of the N(0,1) stream (seed, stream_id): Philox4x32-10 with counter {i / 4 lo, i / 4 hi, stream_id lo, stream_id hi} and key {seed lo, seed hi};
+ * the four words c give u = (float(c) + 0.5) 2^-32 and (sqrt(-2 ln u0) cos 2 pi u1, .. sin 2 pi u1, sqrt(-2 ln u2) cos 2 pi u3, .. sin 2 pi u3).  The sampler draws
+ * x_T from stream 0 and the noise of step k from stream k + 1: pdhip_ddnm_step(eps NULL, seed, step k) adds exactly pdhip_philox_normal(N 3 HW, seed, k + 1). */
 int pdhip_philox_normal(float* out, long long n, uint64_t seed, uint64_t stream_id, void* stream);
+/* ---- the f32 side ops of the UNet on their own (csrc/nn_misc.hip): unit-test surface, nothing the product calls.
+ * y [N][R] = W [R][K] x [N][K] + b [R], silu_out != 0: SiLU on top -- the batched GEMV behind time_embed and every ResBlock's emb_layers (unet.py:199-205,
+ * 472-476).  All f32, W and x 16-byte aligned, K <= 2048 (8 x rows are staged in 64 KiB of LDS); a larger K is PDHIP_E_ARG and nothing is launched. */
+int pdhip_gemv_rows_f32(const float* W, const float* b, const float* x, float* y, int R, int K, int N, int silu_out, void* stream);
+/* emb_silu [N][4 mc] = silu(time_embed(timestep_embedding(t, mc))) (nn.py:103-121, unet.py:472-476; the SiLU is the first layer of every emb_layers):
+ * w0 [4 mc][mc], w2 [4 mc][4 mc], PyTorch Linear layouts; mc even, <= 512.  tmp: N * 5 mc floats, on return [N][mc] the raw embedding
+ * (cos | sin halves) followed by [N][4 mc] the hidden layer silu(w0 temb + b0). */
+int pdhip_timestep_mlp_f32(const float* t, int N, int mc, const float* w0, const float* b0, const float* w2, const float* b2, float* emb_silu,
+                           float* tmp, void* stream);
+/* Y [N,H,W,Cout] f16 NHWC = conv3x3(x.half(), pad 1) + bias of the UNet's first conv (unet.py:483): x f32 NCHW [N,3,H,W]; Wt [Cout_pad][32] f16 with
+ * k = (ky * 3 + kx) * 3 + c and k >= 27 zero, rows >= Cout zero; im2col_ws: N * H * W * 32 halfs (the gathered patches, one 32-wide row per pixel);
+ * Cout % 8 == 0, Cout_pad % 128 == 0 (the GEMM behind it is pdhip_conv2d_nhwc_f16 as a 1x1 over 32 channels).  No GroupNorm partials. */
+int pdhip_conv_in_f16(const float* x_nchw, const void* Wt, const float* bias, void* Y, int N, int H, int W, int Cout, int Cout_pad, void* im2col_ws,
+                      const void* zero_page, void* stream);
 /* Calibration only (no reference counterpart): a streaming device-to-device copy, 16 bytes per lane, `unroll` & 15 (1, 2, 4, 8; 0 = 4) loads in
  * flight per lane, `unroll` >> 4 the form (0 grid-stride sweep, 1 the same with nontemporal loads / stores, 2 one contiguous slab per workgroup), `blocks` workgroups of 256 threads (0 = 2048).  bench.py reports its rate (read + write bytes) as
  * roofline.calibration.copy16_gbs next to torch's copy_: the ceiling the HBM-bound GroupNorm passes are judged against. */

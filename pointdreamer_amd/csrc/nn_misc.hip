@@ -311,3 +311,23 @@ int copy16(const void* src, void* dst, long long bytes, int blocks, int unroll, 
 }
 
 }  // namespace pdnn
+
+// ---- unit-test surface of the f32 side ops (include/pdhip.h): thin entries, nothing is computed here
+extern "C" int pdhip_gemv_rows_f32(const float* W, const float* b, const float* x, float* y, int R, int K, int N, int silu_out, void* stream) {
+    PD_REQUIRE(W && b && x && y, "pdhip_gemv_rows_f32: null argument");
+    PD_REQUIRE(R >= 1 && K >= 1 && N >= 1, "pdhip_gemv_rows_f32: R, K, N must be positive (R=%d K=%d N=%d)", R, K, N);
+    return pdnn::gemv_launch(W, b, x, y, R, K, N, silu_out != 0, as_stream(stream));
+}
+extern "C" int pdhip_timestep_mlp_f32(const float* t, int N, int mc, const float* w0, const float* b0, const float* w2, const float* b2,
+                                      float* emb_silu, float* tmp, void* stream) {
+    PD_REQUIRE(t && w0 && b0 && w2 && b2 && emb_silu && tmp, "pdhip_timestep_mlp_f32: null argument");
+    PD_REQUIRE(N >= 1 && mc >= 2 && mc % 2 == 0 && mc <= 512, "pdhip_timestep_mlp_f32: N must be positive and mc even, at most 512 (N=%d mc=%d)", N, mc);
+    return pdnn::timestep_mlp(t, N, mc, w0, b0, w2, b2, emb_silu, tmp, as_stream(stream));
+}
+extern "C" int pdhip_conv_in_f16(const float* x_nchw, const void* Wt, const float* bias, void* Y, int N, int H, int W, int Cout, int Cout_pad,
+                                 void* im2col_ws, const void* zero_page, void* stream) {
+    PD_REQUIRE(x_nchw && Wt && bias && Y && im2col_ws && zero_page, "pdhip_conv_in_f16: null argument");
+    PD_REQUIRE(N >= 1 && H >= 1 && W >= 1 && Cout >= 1, "pdhip_conv_in_f16: N, H, W, Cout must be positive");
+    return pdnn::conv_in_3x3(x_nchw, (const pdnn::half_t*)Wt, bias, (pdnn::half_t*)Y, N, H, W, Cout, Cout_pad, (pdnn::half_t*)im2col_ws, (const pdnn::half_t*)zero_page,
+                             as_stream(stream), nullptr, nullptr);
+}

@@ -81,6 +81,9 @@ _reg('pdhip_gn_finalize_oct_f32', C.c_int, [vp, i32, i32, vp, i32, i32, i32, i32
 _reg('pdhip_debug_conv3x3_apply', C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp])
 _reg('pdhip_attention_f16', C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp])
 _reg('pdhip_philox_normal', C.c_int, [vp, C.c_longlong, u64, u64, vp])
+_reg('pdhip_gemv_rows_f32', C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp])
+_reg('pdhip_timestep_mlp_f32', C.c_int, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp])
+_reg('pdhip_conv_in_f16', C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp])
 _reg('pdhip_debug_set_gn_iters', C.c_int, [i32])
 _reg('pdhip_bench_copy16', C.c_int, [vp, vp, C.c_longlong, i32, i32, vp])
 
