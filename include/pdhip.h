@@ -524,6 +524,23 @@ int pdhip_timestep_mlp_f32(const float* t, int N, int mc, const float* w0, const
  * Cout % 8 == 0, Cout_pad % 128 == 0 (the GEMM behind it is pdhip_conv2d_nhwc_f16 as a 1x1 over 32 channels).  No GroupNorm partials. */
 int pdhip_conv_in_f16(const float* x_nchw, const void* Wt, const float* bias, void* Y, int N, int H, int W, int Cout, int Cout_pad, void* im2col_ws,
                       const void* zero_page, void* stream);
+/* ---- the GroupNorm-apply pass and its neighbours on their own (csrc/nn_norm.hip): unit-test surface, nothing the product calls.
+ * y = [SiLU]( GroupNorm32(x) [* (1 + scale) + shift] ), optionally 2x resampled (resample 0 none, 1 AvgPool2d(2) of the activated values, 2 nearest x2), f16 NHWC:
+ * the engine's gn_apply with every operand it can carry.  x [N,H,W,C], or with x2 the never-materialised channel concat [x (Ca channels) | x2 (C - Ca)].
+ * The statistics come as exactly one of: stats [N][32][2] = (mean, rstd) finished, or the producers' octet partials partA ([N][chunksA][Ca / 8][2]; one tensor:
+ * [N][chunksA][C / 8][2]) and, with x2, partB ([N][chunksB][(C - Ca) / 8][2]), reduced inside the kernel (C % 256 == 0, C <= 2048, eps 1e-5).
+ * film: rows (scale[C] | shift[C]) f32, row n at film + n * film_stride, or NULL; only with resample 0.  y_raw (may be NULL; resample 1 and a single source only):
+ * AvgPool2d(2) of the raw x, [N,H/2,W/2,C] f16.  Anything else is PDHIP_E_ARG and nothing is launched. */
+int pdhip_gn_apply_f16(const void* x, const void* x2, int Ca, int C, const float* stats, const float* partA, int chunksA, const float* partB, int chunksB,
+                       const float* gamma, const float* beta, const float* film, long long film_stride, int N, int H, int W, int silu, int resample, void* y,
+                       void* y_raw, void* stream);
+/* table [N][C / 8][16] = (A0..A7, B0..B7) per channel octet with GroupNorm32 (+ FiLM) = A x + B: A = rstd gamma t1, B = (beta - mean rstd gamma) t1 + sh,
+ * t1 = f16(1 + f16(scale)), sh = f16(shift) (1 and 0 without film) -- the input transform of the halo conv's APPLY form.  C % 32 == 0. */
+int pdhip_gn_table_f32(const float* stats, const float* gamma, const float* beta, const float* film, long long film_stride, int N, int C, float* table, void* stream);
+/* y = AvgPool2d(2)(x) (mode 1: f16 of the f32 sum of the four pixels, in row-major order, times 0.25; H, W even) or nearest x2 (mode 2) of x [N,H,W,C] f16 NHWC, C % 8 == 0 */
+int pdhip_resample2x_nhwc_f16(const void* x, int N, int H, int W, int C, int mode, void* y, void* stream);
+/* y [pixels][Ca + Cb] = [a [pixels][Ca] | b [pixels][Cb]] f16 (th.cat over channels, unet.py:661); Ca, Cb % 8 == 0 */
+int pdhip_concat_channels_f16(const void* a, int Ca, const void* b, int Cb, long long pixels, void* y, void* stream);
 /* Calibration only (no reference counterpart): a streaming device-to-device copy, 16 bytes per lane, `unroll` & 15 (1, 2, 4, 8; 0 = 4) loads in
  * flight per lane, `unroll` >> 4 the form (0 grid-stride sweep, 1 the same with nontemporal loads / stores, 2 one contiguous slab per workgroup), `blocks` workgroups of 256 threads (0 = 2048).  bench.py reports its rate (read + write bytes) as
  * roofline.calibration.copy16_gbs next to torch's copy_: the ceiling the HBM-bound GroupNorm passes are judged against. */

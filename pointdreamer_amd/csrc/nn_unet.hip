@@ -1209,3 +1209,37 @@ extern "C" int pdhip_bench_copy16(const void* src, void* dst, long long bytes, i
     return copy16(src, dst, bytes, blocks, unroll, as_stream(stream));
 }
 extern "C" int pdhip_debug_set_gn_iters(int iters) { const int old = g_gn_iters; g_gn_iters = iters; return old; }
+// ---- the GroupNorm-apply pass and its neighbours on their own (csrc/nn_norm.hip): unit-test surface, nothing the product calls
+extern "C" int pdhip_gn_apply_f16(const void* x, const void* x2, int Ca, int C, const float* stats, const float* partA, int chunksA,
+                                  const float* partB, int chunksB, const float* gamma, const float* beta, const float* film,
+                                  long long film_stride, int N, int H, int W, int silu, int resample, void* y, void* y_raw, void* stream) {
+    PD_REQUIRE(x && gamma && beta && y, "pdhip_gn_apply_f16: null argument");
+    PD_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, "pdhip_gn_apply_f16: empty tensor");
+    PD_REQUIRE((stats != nullptr) != (partA != nullptr), "pdhip_gn_apply_f16: the statistics come finished (stats) or as octet partials (partA), not both");
+    PD_REQUIRE(stats == nullptr || (partB == nullptr && chunksA == 0 && chunksB == 0), "pdhip_gn_apply_f16: partials next to finished statistics");
+    PD_REQUIRE(partA == nullptr || (chunksA >= 1 && (x2 == nullptr ? (partB == nullptr && chunksB == 0) : (partB != nullptr && chunksB >= 1))),
+               "pdhip_gn_apply_f16: one set of octet partials (and a chunk count >= 1) per source tensor");
+    PD_REQUIRE(film == nullptr || film_stride >= 2LL * C, "pdhip_gn_apply_f16: film rows hold scale[C] | shift[C]");
+    if (partA != nullptr) {
+        const GnPartsArg pa{partA, x2 ? Ca : C, chunksA, partB, x2 ? C - Ca : 0, chunksB, 1e-5f};
+        return gn_apply((const half_t*)x, nullptr, gamma, beta, film, film_stride, N, H, W, C, silu, resample, y, 0, as_stream(stream),
+                        (const half_t*)x2, x2 ? Ca : 0, (half_t*)y_raw, &pa);
+    }
+    return gn_apply((const half_t*)x, stats, gamma, beta, film, film_stride, N, H, W, C, silu, resample, y, 0, as_stream(stream),
+                    (const half_t*)x2, x2 ? Ca : 0, (half_t*)y_raw, nullptr);
+}
+extern "C" int pdhip_gn_table_f32(const float* stats, const float* gamma, const float* beta, const float* film, long long film_stride, int N, int C,
+                                  float* table, void* stream) {
+    PD_REQUIRE(stats && gamma && beta && table && N > 0 && C > 0, "pdhip_gn_table_f32: bad arguments");
+    PD_REQUIRE(film == nullptr || film_stride >= 2LL * C, "pdhip_gn_table_f32: film rows hold scale[C] | shift[C]");
+    return gn_table(stats, gamma, beta, film, film_stride, N, C, table, as_stream(stream));
+}
+extern "C" int pdhip_resample2x_nhwc_f16(const void* x, int N, int H, int W, int C, int mode, void* y, void* stream) {
+    PD_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && C > 0, "pdhip_resample2x_nhwc_f16: bad arguments");
+    PD_REQUIRE(mode != 1 || (H % 2 == 0 && W % 2 == 0), "pdhip_resample2x_nhwc_f16: avgpool needs even H, W");
+    return resample2x((const half_t*)x, N, H, W, C, mode, (half_t*)y, as_stream(stream));
+}
+extern "C" int pdhip_concat_channels_f16(const void* a, int Ca, const void* b, int Cb, long long pixels, void* y, void* stream) {
+    PD_REQUIRE(a && b && y && Ca > 0 && Cb > 0 && pixels > 0, "pdhip_concat_channels_f16: bad arguments");
+    return concat_channels((const half_t*)a, Ca, (const half_t*)b, Cb, pixels, (half_t*)y, as_stream(stream));
+}

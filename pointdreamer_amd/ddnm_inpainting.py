@@ -85,6 +85,10 @@ _reg('pdhip_gemv_rows_f32', C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp])
 _reg('pdhip_timestep_mlp_f32', C.c_int, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp])
 _reg('pdhip_conv_in_f16', C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp])
 _reg('pdhip_debug_set_gn_iters', C.c_int, [i32])
+_reg('pdhip_gn_apply_f16', C.c_int, [vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, C.c_longlong, i32, i32, i32, i32, i32, vp, vp, vp])
+_reg('pdhip_gn_table_f32', C.c_int, [vp, vp, vp, vp, C.c_longlong, i32, i32, vp, vp])
+_reg('pdhip_resample2x_nhwc_f16', C.c_int, [vp, i32, i32, i32, i32, i32, vp, vp])
+_reg('pdhip_concat_channels_f16', C.c_int, [vp, i32, vp, i32, C.c_longlong, vp, vp])
 _reg('pdhip_bench_copy16', C.c_int, [vp, vp, C.c_longlong, i32, i32, vp])
 
 # models/DDNM/configs/imagenet_256.yml (model + diffusion + time_travel sections); values must be reproduced
