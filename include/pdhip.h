@@ -115,6 +115,26 @@ int pdhip_surface_recon(const float* points /*[N,3]*/, const float* normals /*[N
                         float* vertices, int vertex_capacity, int64_t* faces, int face_capacity, float* vertex_colors /*or NULL*/,
                         int32_t* counts /*device [4]*/, float* info /*device [8]*/, void* ws, void* stream);
 
+/* ---- Mesh decimation to a target face count (baselines/spr.py:63-64 asks pymeshlab's meshing_decimation_quadric_edge_collapse(
+ *      targetfacenum, preservetopology=True) on the CPU; here quadric-error edge collapses in rounds of mutually independent collapses
+ *      on the device, csrc/simplify_mesh.hip -- the mesh is this library's own, not pymeshlab's).  Input: a CLOSED, CONSISTENTLY ORIENTED
+ *      2-manifold (what pdhip_surface_recon emits), any number of components: every directed edge once, its reverse once, three different
+ *      indices in [0, Vn) per face; anything else is refused (PDHIP_E_ARG, counts[3] = 2, no output written).  Per vertex one quadric
+ *      (area-weighted plane quadrics of its faces, f64) carried through the collapses; per edge (u < v) the position minimising
+ *      Q_u + Q_v (else the cheapest of u, v, midpoint), valid if u and v have exactly two common neighbours, at least three vertices
+ *      surround the pair, and every remaining face round them keeps a positive area and turns by less than acos(0.2); per round the about
+ *      (F - target) / 2 cheapest valid edges compete by a hashed unique key for their closed neighbourhoods, the winners collapse
+ *      (v into u, colour of the endpoint nearer to the new position).  The topology is preserved (components, Euler characteristic of each,
+ *      closed, oriented); faces and surviving vertices keep their input order; every output vertex is referenced.  Stops at
+ *      F <= target_faces + 1 (F is even on a closed mesh), or when a round finds no collapse (flags bit 0, `stalled`: the mesh reached so
+ *      far is returned, PDHIP_OK); more than 1024 rounds is PDHIP_E_ARG.  target_faces >= F: the mesh is copied through bit for bit,
+ *      rounds = 0.  Synchronises `stream` (input check; one status read per 8 rounds).  Two calls give equal bytes.
+ *      The size query returns 0 for Vn < 4, F < 4, Vn > 2^22 or F > 2^23 (the widths of the edge keys). */
+size_t pdhip_simplify_mesh_workspace_bytes(int Vn, int F);
+int pdhip_simplify_mesh(const float* vertices /*[Vn,3]*/, int Vn, const int64_t* faces /*[F,3]*/, int F, const float* vertex_colors /*[Vn,3] or NULL*/,
+                        int target_faces, float* out_vertices /*[Vn,3]*/, int64_t* out_faces /*[F,3]*/, float* out_colors /*[Vn,3] or NULL*/,
+                        int32_t* counts /*device [4]: vertices, faces, rounds, flags (1 = stalled, 2 = bad input)*/, void* ws, void* stream);
+
 /* ---- SURVEY 8(e) configs[4], round 4: S independent shapes of EQUAL sizes (Vn vertices, F faces, N points, atlas A) through the same V
  *      cameras in ONE launch per stage.  Per-shape inputs are stacked ([S, ...]); every per-view array has S*V leading entries, view
  *      g = s * V + v; results equal the per-shape entry points bit for bit (tests/test_gpu_round4.py).  The per-view-independent stages

@@ -33,7 +33,7 @@ SUPPORTED_KEYS = ('texture_gen_method', 'camera_distribution', 'cam_res', 'view_
                   'crop_img', 'crop_padding', 'mask_ratio_thresh', 'edge_dilate_kernels', 'optimize_from',
                   'xatlas_texture_res', 'complete_unseen_by', 'output_path')
 # keys of this build's own stages in front of the texturing path (geo_from: 'SPR'): validated like the others, not pipeline arguments
-GEOMETRY_KEYS = ('spr_depth', 'spr_knn')
+GEOMETRY_KEYS = ('spr_depth', 'spr_knn', 'spr_faces')
 
 
 class Cfg(dict):
@@ -89,6 +89,8 @@ def load_config(cfg_file, overrides=None):
         raise ValueError(f"spr_depth={cfg.spr_depth!r}: the dense grid of the SPR geometry supports {spr.DEPTHS} (2^depth cells per axis)")
     if 'spr_knn' in cfg and not (isinstance(cfg.spr_knn, int) and 3 <= cfg.spr_knn <= 32):
         raise ValueError(f"spr_knn={cfg.spr_knn!r}: the normals of the SPR geometry take 3 .. 32 neighbours")
+    if 'spr_faces' in cfg and not (isinstance(cfg.spr_faces, int) and not isinstance(cfg.spr_faces, bool) and cfg.spr_faces >= 4):
+        raise ValueError(f"spr_faces={cfg.spr_faces!r}: the face count the SPR geometry is decimated to is an integer >= 4")
     if cfg.optimize_from == 'None':                      # YAML `None` is the string 'None' (demo.py:213 treats both alike)
         cfg['optimize_from'] = None
     return cfg
@@ -183,9 +185,11 @@ def _load_shape(cfg, pc_file, name, device, logger):
         start = time.time()
         depth = cfg.get('spr_depth', spr.DEFAULT_DEPTH)
         rv, rf, _, rc = spr.recon_one_shape_SPR(xyz, rgb, depth=depth, knn=cfg.get('spr_knn', spr.DEFAULT_KNN), save_path=cached_geo,
-                                                return_counts=True)
+                                                return_counts=True, target_faces=cfg.get('spr_faces'))
+        decimated = (f', decimated from {rc["faces_reconstructed"]} faces in {rc["simplify_rounds"]} rounds'
+                     if 'faces_reconstructed' in rc else '')
         logger.info(f'Get Geometry time: {time.time() - start} s by SPR (depth {depth}: {rc["vertices"]} vertices, {rc["faces"]} '
-                    f'faces, {rc["iterations"]} solver iterations; normals oriented by {rc["orientation"]})')
+                    f'faces{decimated}, {rc["iterations"]} solver iterations; normals oriented by {rc["orientation"]})')
     if os.path.exists(geo_path) or os.path.exists(cached_geo):
         supplied = os.path.exists(geo_path)
         v, f, vt, ft = io_utils.load_obj_mesh(geo_path if supplied else cached_geo, with_uv=True)

@@ -2,7 +2,9 @@
 normals for a point set, screened Poisson reconstruction and quadric decimation.  Here the first two run on the device
 (csrc/surface_recon.hip): oriented normals from k nearest neighbours + visibility votes, a Poisson solve on a dense grid of
 2^depth cells per axis, marching cubes with welded vertices.  The mesh is this project's own (not pymeshlab's): a closed,
-consistently oriented triangle mesh, every component of the iso-surface included.  Decimation is not built."""
+consistently oriented triangle mesh, every component of the iso-surface included.  The third, decimation to a face count, is this
+build's own as well (csrc/simplify_mesh.hip, `simplify_mesh` / `target_faces=`): quadric-error edge collapses in rounds of independent
+collapses on the device, topology preserved; pymeshlab's decimator is not reproduced."""
 import numpy as np
 import torch
 
@@ -94,6 +96,42 @@ def poisson_reconstruct(points, normals, depth=DEFAULT_DEPTH, return_counts=Fals
     return tuple(out)
 
 
+def simplify_mesh(vertices, faces, target_faces, colors=None, return_counts=False):
+    """vertices [Vn,3], faces [F,3] (GPU; a closed, consistently oriented 2-manifold, any number of components) -> (vertices f32,
+    faces int64) with target_faces (+ 1 for an odd target) faces, the topology preserved.  colors [Vn,3]: a third result, per vertex the
+    colour of the collapsed endpoint nearer to it.  return_counts: a last result, dict(vertices, faces, rounds, stalled); stalled = no
+    further collapse keeps the topology and the shape, the mesh has more faces than asked for.  target_faces >= F returns the input."""
+    v = _points(vertices, 'simplify_mesh')
+    if not torch.is_tensor(faces) or not faces.is_cuda:
+        raise PdhipError("simplify_mesh needs tensors on the GPU (cuda:N == HIP device); there is no CPU path")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise PdhipError(f"simplify_mesh: expected faces [F,3], got {tuple(faces.shape)}")
+    f = faces.detach().long().contiguous()
+    c = None
+    if colors is not None:
+        c = _points(colors, 'simplify_mesh')
+        if c.shape != v.shape:
+            raise PdhipError(f"simplify_mesh: vertices {tuple(v.shape)} and colors {tuple(c.shape)} differ")
+    Vn, F, dev = v.shape[0], f.shape[0], v.device
+    L = _lib.lib()
+    nbytes = L.pdhip_simplify_mesh_workspace_bytes(Vn, F)
+    if nbytes == 0:
+        raise PdhipError(f"simplify_mesh: Vn={Vn} F={F}: a closed mesh has at least 4 vertices and 4 faces, and at most 2^22 / 2^23")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    ov, of = torch.empty_like(v), torch.empty_like(f)
+    oc = torch.empty_like(c) if c is not None else None
+    counts = torch.zeros((4,), dtype=torch.int32, device=dev)
+    check(L.pdhip_simplify_mesh(ptr(v), Vn, ptr(f), F, ptr(c, allow_none=True), int(target_faces), ptr(ov), ptr(of), ptr(oc, allow_none=True),
+                                ptr(counts), ptr(ws), stream()), 'pdhip_simplify_mesh')
+    nv, nf, rounds, flags = counts.cpu().tolist()
+    out = [ov[:nv].contiguous(), of[:nf].contiguous()]
+    if c is not None:
+        out.append(oc[:nv].contiguous())
+    if return_counts:
+        out.append(dict(vertices=nv, faces=nf, rounds=rounds, stalled=bool(flags & 1)))
+    return tuple(out)
+
+
 def _to_device(a, name):
     if torch.is_tensor(a):
         if not a.is_cuda:
@@ -103,14 +141,16 @@ def _to_device(a, name):
 
 
 def recon_one_shape_SPR(coords, colors, gt_normals=None, save_path=None, depth=DEFAULT_DEPTH, simplify_face_num=None, *, knn=DEFAULT_KNN,
-                        return_counts=False):
+                        return_counts=False, target_faces=None):
     """baselines/spr.py:16-75 with its argument order and 3-tuple (vertices [Vn,3], faces [F,3], vertex_colors [Vn,3]), as GPU
     tensors.  coords / colors / gt_normals: GPU tensors or numpy arrays (numpy goes to the current device).  gt_normals None: the
     normals are estimated.  save_path: the mesh is written as an OBJ.  depth: 6, 7 or 8 (a dense grid of 2^depth cells per axis, not
-    the reference's octree depth 12).  simplify_face_num: quadric decimation is not built -- anything but None is refused."""
+    the reference's octree depth 12).  simplify_face_num: pymeshlab's decimation is not reproduced -- anything but None is refused.
+    target_faces: this build's own decimator (simplify_mesh) after the reconstruction, before save_path is written; with return_counts
+    the dict gains faces_reconstructed and simplify_rounds."""
     if simplify_face_num is not None:
-        raise NotImplementedError("recon_one_shape_SPR: mesh decimation (simplify_face_num) is not built; pass None and choose the face "
-                                  "count through depth (6, 7, 8)")
+        raise NotImplementedError("recon_one_shape_SPR: pymeshlab's quadric edge-collapse decimation (simplify_face_num) is not reproduced; "
+                                  "this build's own decimator is the keyword target_faces=")
     if int(depth) not in DEPTHS:
         raise ValueError(f"depth={depth}: the dense grid supports depth 6, 7 or 8 (2^depth cells per axis); the reference's default 12 "
                          "is an octree depth")
@@ -122,6 +162,9 @@ def recon_one_shape_SPR(coords, colors, gt_normals=None, save_path=None, depth=D
     else:
         normals = _to_device(gt_normals, 'gt_normals')
     verts, faces, vcol, rc = poisson_reconstruct(xyz, normals, depth=depth, colors=rgb, return_counts=True)
+    if target_faces is not None:
+        verts, faces, vcol, sc = simplify_mesh(verts, faces, target_faces, colors=vcol, return_counts=True)
+        rc = dict(rc, faces_reconstructed=rc['faces'], vertices=sc['vertices'], faces=sc['faces'], simplify_rounds=sc['rounds'])
     if save_path is not None:
         from . import io_utils
         io_utils.save_obj_mesh(verts.cpu().numpy(), faces.cpu().numpy(), save_path)
