@@ -523,7 +523,7 @@ int pdhip_conv_ht_f16(const void* x, const void* w_packed, const float* bias, co
 int pdhip_conv_ht_plan(int N, int H, int W, int Cin, int Cout, int Cout_pad, long long splitk_ws_floats, int* routed, int* slabs);   /* host-only: would the engine's automatic routing (step 7 of conv_plan, csrc/nn_gemm.hip) send this 3x3 layer to the halo-tile kernel, and in how many K-slabs */
 int pdhip_debug_set_conv_ht(int mode, int slabs);   /* 256 x 64 halo-tile conv: mode 0 never / 1 automatic (batch 1-4 of the 64^2, 128^2 levels) / 2 every eligible layer; slabs 0 automatic, 1 / 2 / 4 forced K-slabs; returns the previous mode */
 int pdhip_debug_set_rr_gn(int max_width);   /* UNet engine: largest image width at which a conv routed to the row-resident kernel also applies the GroupNorm (+ FiLM) + SiLU in front of it (default 0 = never: no gain measured inside the forward; 8 / 16 / 32 = up to that width); returns the previous value */
-int pdhip_debug_set_conv_rr(int mode, int variant, int slabs);   /* row-resident conv: mode 0 never / 1 automatic / 2 every eligible layer; variant 0 auto (1: 8^2, 2: 16^2 whole image, 3: 32^2 bands, 4: 16^2 half image, 5: 8^2 with 128-channel units); slabs 0 auto = K slices of the conv source; returns the previous mode */
+int pdhip_debug_set_conv_rr(int mode, int variant, int slabs);   /* row-resident conv: mode 0 never / 1 automatic / 2 every eligible layer; variant 0 auto (1: 8^2, 2: 16^2 half image, 3: 32^2 bands, 5: 8^2 with 128-channel units, 6 / 7: 32^2 / 16^2 with 16-channel tiles, 8: 64^2 bands; 6 - 8 take raw input only); slabs 0 auto = K slices of the conv source; returns the previous mode */
 int pdhip_attention_f16(const void* qkv /*[N,T,3C]*/, void* out /*[N,T,C]*/, int N, int T, int C, int head_dim,
                         void* vt_ws /*N*T*C halfs, non-NULL selects the 128-query MFMA kernel for T % 128 == 0, head_dim 64, N*heads % 8 == 0 (QKVAttentionLegacy, unet.py:341-373); the buffer is written only in the transposed-V lab form (pdhip_debug_set_attn); NULL: the 64-query kernel*/, void* stream);
 /* out[i] = element i of the N(0,1) stream (seed, stream_id): Philox4x32-10 with counter {i / 4 lo, i / 4 hi, stream_id lo, stream_id hi} and key {seed lo, seed hi};
