@@ -73,6 +73,36 @@ int pdhip_raster_barycentrics(const float* pos /*[V,Vn,4]*/, int V, int Vn, cons
 int pdhip_interpolate(const float* attr /*[Na,C]*/, int C, const int32_t* tri /*[F,3]*/, const int64_t* face_idxs,
                       const float* bary, long long pixels, float* out /*[pixels,C]*/, void* stream);
 
+/* ---- Evaluation renderer, shading stage (utils/camera_utils.py:379-554 render_textured_mesh, :735-828 render_per_vertex_color_mesh): from
+ *      face_idxs [V,R,R] / bary [V,R,R,2] (pdhip_raster_mesh_ws + pdhip_raster_barycentrics, rows as the rasteriser leaves them) to the
+ *      finished views in one pass per pixel, no uv_map in HBM.  a = u*a0 + v*a1 + ((1-u)-v)*a2 over attr [Na,C] / tri [F,3] (the
+ *      contract of pdhip_interpolate).  C = 2: a is a UV, wrapped (uv - floor(uv), the reference's `% 1`) and looked up bilinearly in
+ *      atlas [A,A,3] f32 with x = u*A - 0.5, y = v*A - 0.5 clamped to [0, A-1] (grid_sample align_corners=False, padding_mode='border');
+ *      atlas row 0 is v = 0, the orientation colorize_one_mesh returns (the PNG of save_textured_mesh is that flipped).  C = 3: a is the
+ *      colour (per-vertex colours), atlas must be NULL.  Lighting (light_dirs [L,3], 1 <= L <= 16, with face_normals [F,3] and cam_params
+ *      [V,16]; L = 0 and NULLs: none): n = the face normal, negated where n . R[2] < 0 (cam_params[6:9], the camera's back axis); colour =
+ *      clip(sum_l a * clip(n . l, 0, 1), 0, 1) with |n . l| when double_side, then ** (1 / gamma) when gamma > 0 (0: none).
+ *      images [V,3,R,R] f32 and rgba [V,R,R,4] u8 (either may be NULL) are flipped vertically (row 0 = top, camera_utils.py:553-554);
+ *      rgba = rint(colour * 255) clamped to 0 .. 255, alpha 255 -- the input of the PNG writer.  Uncovered pixels (face index < 0, or a
+ *      face / attribute index outside its table) are exactly 0 in both. */
+int pdhip_shade_views(const int64_t* face_idxs /*[V,R,R]*/, const float* bary /*[V,R,R,2]*/, int V, int R, const float* attr /*[Na,C]*/,
+                      int Na, int C, const int32_t* tri /*[F,3]*/, int F, const float* atlas /*[A,A,3] or NULL*/, int A,
+                      const float* face_normals /*[F,3] or NULL*/, const float* cam_params /*[V,16] or NULL*/,
+                      const float* light_dirs /*[L,3] or NULL*/, int L, int double_side, double gamma, float* images /*[V,3,R,R] or NULL*/,
+                      uint8_t* rgba /*[V,R,R,4] or NULL*/, void* stream);
+
+/* ---- Image metrics of the evaluation (utils/metric_utils/psnr_ssmi.py:44-147): a, b [N,H,W,C] u8 (C <= 4) -> per image sse [N] u64, the
+ *      exact sum of squared differences (PSNR = 10 log10(255^2 H W C / sse) is left to the host), and ssim [N] f64, the mean SSIM with
+ *      C1 = (0.01*255)^2, C2 = (0.03*255)^2 (either may be NULL).  gaussian = 0: skimage.metrics.structural_similarity(data_range=255,
+ *      channel_axis=2) -- 7x7 uniform window, sample covariance (49/48), mean over the windows inside the image (skimage's 3-pixel crop),
+ *      the window sums kept as integers up to the division.  gaussian = 1: psnr_ssmi.py:127-147 -- outer product of the 11-tap Gaussian of
+ *      sigma 1.5 normalised to sum 1, "valid" region, population covariance, mean over pixels and channels.  LDS tiles with halo, separable
+ *      filter, fixed-order reduction in two launches, no floating-point atomics: two calls give equal bits.  An image smaller than the
+ *      window when ssim is asked for: PDHIP_E_ARG.  ws: pdhip_image_metrics_workspace_bytes(N, H, W) bytes.  Does not synchronise. */
+size_t pdhip_image_metrics_workspace_bytes(int N, int H, int W);
+int pdhip_image_metrics(const uint8_t* a, const uint8_t* b, int N, int H, int W, int C, int gaussian, uint64_t* sse /*[N] or NULL*/,
+                        double* ssim /*[N] or NULL*/, void* ws, void* stream);
+
 /* ---- UV unwrapping (the xatlas.parametrize call of xatlas_uvmap_w_face_id, models/get3d/extract_texture_map.py:42-44; the layout is
  *      this library's own): charts of faces sharing a dominant signed normal axis (n.axis >= cos 70 for every face of a chart),
  *      orthographic projection per chart, one world-to-texel scale for all charts, shelf packing with `gutter` texels around every

@@ -125,3 +125,268 @@ def get_cam_Ks_RTs_from_locations(cam_locations):
                                [N[0], N[1], N[2], np.dot(-N, eye)]])
     cam_K = np.array([[560.0, 0, 256], [0, 560, 256], [0, 0, 1]])
     return cam_K, cam_RTs
+
+
+# ----------------------------------------------------------------------------- evaluation renderers (camera_utils.py:251-828)
+def _clip_positions(cams, vertices):
+    """pos [V,Vn,4] = (cam.transform(vertices), 1) for every camera (pdhip_project_points), and the stacked camera parameters."""
+    from . import _lib
+    from ._lib import ptr, stream, check
+    L = _lib.lib()
+    V, Vn, dev = len(cams), vertices.shape[0], vertices.device
+    cp = stack_params(cams)
+    pos = torch.empty((V, Vn, 4), device=dev)
+    vuv = torch.empty((V, Vn, 2), device=dev)
+    ws = torch.empty((4 * V,), dtype=torch.int32, device=dev)
+    check(L.pdhip_project_points(ptr(cp), V, ptr(vertices), Vn, None, 0, 0, 0.0, ptr(pos), ptr(vuv), None, None, None, None,
+                                 ptr(ws), stream()), 'pdhip_project_points')
+    return pos, cp
+
+
+def _normalized(vertices):
+    """camera_utils.py:432-436 on a copy: centre of the bounding box to the origin, largest extent to 1."""
+    vmin, vmax = vertices.min(0)[0], vertices.max(0)[0]
+    return (vertices - (vmax + vmin) / 2.) / (vmax - vmin).max()
+
+
+def face_normals_unit(vertices, faces):
+    """kal.ops.mesh.face_normals(unit=True) (camera_utils.py:392): [F,3] on the device."""
+    fv = vertices[faces.long()]
+    n = torch.cross(fv[:, 1] - fv[:, 0], fv[:, 2] - fv[:, 0], dim=1)
+    return (n / n.norm(dim=1, keepdim=True).clamp_min(1e-30)).float().contiguous()
+
+
+def shade_views(face_idxs, bary, attr, tri, atlas=None, face_normals=None, cam_params=None, light_dirs=None, double_side=False,
+                gamma=None, want_images=True, want_rgba=False):
+    """pdhip_shade_views: face_idxs [V,R,R] i64 / bary [V,R,R,2] as rasterize() returns them, attr [Na,2] UVs with atlas [A,A,3]
+    (row 0 is v = 0) or attr [Na,3] colours, tri [F,3] -> (images [V,3,R,R] f32 or None, rgba [V,R,R,4] u8 or None), both with
+    row 0 at the top.  Lighting only when light_dirs [L,3] is given (then face_normals [F,3] and cam_params [V,16] as well)."""
+    from . import _lib
+    from ._lib import ptr, stream, check
+    L = _lib.lib()
+    dev = face_idxs.device
+    V, R = face_idxs.shape[0], face_idxs.shape[1]
+    if face_idxs.shape[2] != R:
+        raise ValueError(f"shade_views: square views only, got {tuple(face_idxs.shape)}")
+    if tuple(bary.shape) != (V, R, R, 2):
+        raise ValueError(f"shade_views: bary must be [V,R,R,2] = {(V, R, R, 2)}, got {tuple(bary.shape)}")
+    attr = attr.float().contiguous()
+    tri32 = tri.to(torch.int32).contiguous()
+    if attr.dim() != 2 or tri32.dim() != 2 or tri32.shape[1] != 3:
+        raise ValueError(f"shade_views: attr [Na,C] and tri [F,3] expected, got {tuple(attr.shape)} / {tuple(tri32.shape)}")
+    C = attr.shape[1]
+    A = 0
+    if atlas is not None:
+        atlas = atlas.float().contiguous()
+        if atlas.dim() != 3 or atlas.shape[0] != atlas.shape[1] or atlas.shape[2] != 3:
+            raise ValueError(f"shade_views: atlas must be [A,A,3], got {tuple(atlas.shape)}")
+        A = atlas.shape[0]
+    nl = 0
+    if light_dirs is not None:
+        light_dirs = torch.as_tensor(light_dirs, dtype=torch.float32, device=dev).reshape(-1, 3).contiguous()
+        nl = light_dirs.shape[0]
+        if face_normals is None or cam_params is None:
+            raise ValueError("shade_views: light_dirs needs face_normals and cam_params")
+        face_normals = face_normals.float().contiguous()
+        if face_normals.shape[0] != tri32.shape[0]:
+            raise ValueError("shade_views: one face normal per face")
+        cam_params = cam_params.float().contiguous()
+        if tuple(cam_params.shape) != (V, 16):
+            raise ValueError(f"shade_views: cam_params must be [V,16], got {tuple(cam_params.shape)}")
+    else:
+        face_normals = cam_params = None
+    images = torch.empty((V, 3, R, R), device=dev) if want_images else None
+    rgba = torch.empty((V, R, R, 4), dtype=torch.uint8, device=dev) if want_rgba else None
+    check(L.pdhip_shade_views(ptr(face_idxs.contiguous(), torch.int64), ptr(bary.contiguous(), torch.float32), V, R, ptr(attr), attr.shape[0], C,
+                              ptr(tri32), tri32.shape[0], ptr(atlas, allow_none=True), A, ptr(face_normals, allow_none=True),
+                              ptr(cam_params, allow_none=True), ptr(light_dirs, allow_none=True), nl, int(bool(double_side)),
+                              float(gamma) if (gamma is not None and nl) else 0.0, ptr(images, allow_none=True),
+                              ptr(rgba, allow_none=True), stream()), 'pdhip_shade_views')
+    return images, rgba
+
+
+def _save_views(rgba, save_path):
+    """albedo_001.png ... as RGBA (camera_utils.py:534-550); the 8-bit images come from the kernel as they are written."""
+    import os
+    from . import io_utils
+    os.makedirs(save_path, exist_ok=True)
+    for i in range(rgba.shape[0]):
+        arr, wait = io_utils._host_u8(rgba[i])
+        io_utils.save_HWC_u8_img(arr, os.path.join(save_path, 'albedo_{:s}.png'.format(str(i + 1).zfill(3))), wait=wait)
+
+
+def _render(vertices, faces, attr, tri, atlas, cams, res, save_path, save, light_dirs, gamma, double_side, return_mask, pos_hook=None):
+    from .extract_texture_map import rasterize
+    pos, cp = _clip_positions(cams, vertices)
+    if pos_hook is not None:
+        pos_hook(pos)
+    fidx, bary, _, hard = rasterize(pos, faces, res)
+    fn = face_normals_unit(vertices, faces) if light_dirs is not None else None
+    images, rgba = shade_views(fidx, bary, attr, tri, atlas=atlas, face_normals=fn, cam_params=cp, light_dirs=light_dirs,
+                               double_side=double_side, gamma=gamma, want_images=True, want_rgba=bool(save and save_path))
+    if rgba is not None:
+        _save_views(rgba, save_path)
+    return (images, hard.flip(1)) if return_mask else images
+
+
+def render_textured_mesh2(vertices, faces, uvs, face_uvs_idx, atlas_img, cams, rescale=False, uv_centers=0, uv_scales=2, padding=0,
+                          inpaint_scale_factors=None, glctx=None, save_path=None, save=False, normalize_mesh=False, render_height=None,
+                          render_width=None, light_dirs=None, gamma=None, double_side=False, return_mask=False):
+    """Render a textured mesh held in tensors (camera_utils.py:251-377): vertices [Vn,3], faces [F,3], uvs [T,2], face_uvs_idx [F,3],
+    atlas_img [A,A,3] in the orientation colorize_one_mesh returns (row 0 is v = 0; a loader of a saved model_normalized.png flips
+    it back first) -> images [V,3,R,R] with row 0 at the top, uncovered pixels exactly 0 (with return_mask=True also the hard mask
+    [V,R,R], flipped alike).  `rescale=True` applies the crop transform of the texturing path (pdhip_rescale_vertices, as
+    optimize.texture_coordinates does).  `glctx` is ignored.  The caller's `vertices` are never modified.
+
+    This follows render_textured_mesh (camera_utils.py:379-554), not the body of the reference's render_textured_mesh2, for the v
+    flip and the background: that body negates `_texcoords[:, 1]` on a [1,R,R,2] tensor (:338), which negates image row 1 instead of
+    the v channel, and it samples the uncovered pixels at uv = 0 instead of leaving them 0 -- both slips of a function the path
+    never calls.  Lighting follows :489-529 with the normal turned towards each view's own camera."""
+    from . import _lib
+    from ._lib import ptr, stream, check
+    vertices = vertices.detach().float().contiguous()
+    if normalize_mesh:
+        vertices = _normalized(vertices).contiguous()
+    if atlas_img.dim() == 4:
+        atlas_img = atlas_img[0]
+    if atlas_img.shape[-1] != 3 and atlas_img.shape[0] == 3:
+        atlas_img = atlas_img.permute(1, 2, 0)
+    res = int(render_height) if render_height is not None else int(cams[0].height)
+    if render_width is not None and int(render_width) != res:
+        raise NotImplementedError("render_textured_mesh2: square views only (render_height == render_width)")
+    hook = None
+    if rescale:
+        from .ours_utils import crop_params
+
+        def hook(pos):
+            V, dev = pos.shape[0], pos.device
+            uvc, uvs_, pad, sf = crop_params(V, dev, uv_centers, uv_scales, padding, inpaint_scale_factors)
+            check(_lib.lib().pdhip_rescale_vertices(ptr(pos), V, pos.shape[1], ptr(uvc), ptr(uvs_), ptr(sf), float(pad), stream()),
+                  'pdhip_rescale_vertices')
+    return _render(vertices, faces, uvs.reshape(-1, 2), face_uvs_idx, atlas_img, cams, res, save_path, save, light_dirs, gamma, double_side,
+                   return_mask, hook)
+
+
+def _load_mtl(path):
+    """[(name, dict)] of an MTL file: Kd as three floats, map_Kd as a path relative to the file."""
+    mats = []
+    with open(path) as f:
+        for line in f:
+            t = line.split()
+            if not t:
+                continue
+            if t[0] == 'newmtl':
+                mats.append((t[1] if len(t) > 1 else '', {}))
+            elif mats and t[0] == 'Kd':
+                mats[-1][1]['Kd'] = [float(x) for x in t[1:4]]
+            elif mats and t[0] == 'map_Kd':
+                mats[-1][1]['map_Kd'] = t[-1]
+    return mats
+
+
+def load_textured_obj(mesh_file, device):
+    """vertices, faces, uvs, face_uvs_idx and the atlas [A,A,3] f32 (row 0 is v = 0) of an OBJ with ONE material: its `map_Kd` image
+    flipped back from the PNG's orientation, or its `Kd` colour as a 1x1 atlas."""
+    import os
+    import PIL.Image
+    from . import io_utils
+    v, f, vt, ft = io_utils.load_obj_mesh(mesh_file, with_uv=True)
+    mtllib, used = None, []
+    with open(mesh_file) as fh:
+        for line in fh:
+            t = line.split()
+            if t and t[0] == 'mtllib':
+                mtllib = t[1]
+            elif t and t[0] == 'usemtl' and t[1] not in used:
+                used.append(t[1])
+    mats = _load_mtl(os.path.join(os.path.dirname(mesh_file), mtllib)) if mtllib else []
+    if len(mats) > 1 or len(used) > 1:
+        raise NotImplementedError(f"{mesh_file}: {max(len(mats), len(used))} materials -- the device renderer takes a mesh with a single "
+                                  "material (one map_Kd atlas or one Kd colour); multi-material OBJ files are not supported")
+    mat = mats[0][1] if mats else {}
+    if 'map_Kd' in mat:
+        im = PIL.Image.open(os.path.join(os.path.dirname(mesh_file), mat['map_Kd'])).convert('RGB')
+        a = np.asarray(im, np.uint8)
+        if a.shape[0] != a.shape[1]:
+            raise NotImplementedError(f"{mesh_file}: the atlas is {a.shape[1]} x {a.shape[0]}; square atlases only")
+        atlas = torch.from_numpy(np.ascontiguousarray(a[::-1])).to(device).float() / 255.
+    else:
+        atlas = torch.tensor(mat.get('Kd', [0.5, 0.5, 0.5]), dtype=torch.float32, device=device).reshape(1, 1, 3)
+    T = lambda x: torch.from_numpy(x).to(device)
+    if vt is None:                                    # no vt records: every corner looks up uv = 0 (camera_utils.py:397, 415-428)
+        vt, ft = np.zeros((1, 2), np.float32), np.zeros_like(f)
+    return T(v), T(f), T(vt), T(ft), atlas
+
+
+def render_textured_mesh(mesh_file, cams, device, save_path, glctx=None, save=True, vertices=None, normalize_mesh=True, light_dirs=None,
+                         gamma=None, double_side=False, geo_only=False, color=[0.5, 0.5, 0.5]):
+    """camera_utils.py:379-554: render an OBJ + MTL (+ atlas PNG) from every camera -> images [V,3,R,R]; with save=True also
+    <save_path>/albedo_001.png ... as RGBA (alpha = coverage).  One material only: its `map_Kd`, or its `Kd` as a 1x1 atlas; more
+    than one material raises NotImplementedError.  geo_only renders the constant `color`.  `glctx` is ignored."""
+    v, f, vt, ft, atlas = load_textured_obj(mesh_file, device)
+    if vertices is not None:
+        assert vertices.shape[0] == v.shape[0]
+        v = vertices.to(device)
+    if geo_only:
+        atlas = torch.tensor(list(color), dtype=torch.float32, device=device).reshape(1, 1, 3)
+    return render_textured_mesh2(v, f, vt, ft, atlas, cams, save_path=save_path, save=save, normalize_mesh=normalize_mesh,
+                                 light_dirs=light_dirs, gamma=gamma, double_side=double_side)
+
+
+def render_per_vertex_color_mesh(vertices, faces, vertex_colors, cams, save_path=None, light_dirs=None, gamma=None, double_side=False):
+    """camera_utils.py:735-828 on tensors (what spr.recon_one_shape_SPR returns): vertices [Vn,3], faces [F,3], vertex_colors [Vn,3]
+    in [0,1] -> images [V,3,R,R], row 0 at the top; with save_path also albedo_001.png ... as RGBA."""
+    vertices = vertices.detach().float().contiguous()
+    return _render(vertices, faces, vertex_colors, faces, None, cams, int(cams[0].height), save_path, save_path is not None, light_dirs,
+                   gamma, double_side, False)
+
+
+def _find_mesh_file(root_path, cls_id, name):
+    import os
+    for rel in (('models', 'model_normalized.obj'), ('models', f'{name}.obj'), ('meshes', 'model.obj'), ('Scan', 'Scan.obj')):
+        p = os.path.join(root_path, 'meshes', cls_id, name, *rel)
+        if os.path.exists(p):
+            return p
+    return os.path.join(root_path, 'meshes', cls_id, name, 'models', 'model_normalized.obj')
+
+
+def render_textured_meshes_shapenet2(names=None, root_path=None, device=None, save_root_path=None, glctx=None, per_vertex=False):
+    """camera_utils.py:680-730: every <root_path>/meshes/<cls_id>/<name>/models/model_normalized.obj (or the reference's three other
+    layouts) from the 20 'self_defined' views at 1024^2 into <root_path>/rendered_imgs/<cls_id>/<name>/albedo_%03d.png (RGBA).  A shape
+    whose 20 files exist is skipped; a shape that fails is logged and the run goes on.  Returns the number of shapes rendered."""
+    import os
+    import logging
+    import traceback
+    from . import io_utils
+    device = device if device is not None else torch.device('cuda')
+    log = logging.getLogger('pointdreamer_amd.render')
+    cams, _, _, _ = create_cameras(num_views=20, distance=1.6, res=1024, device=device, distribution='self_defined')
+    out_root = save_root_path if save_root_path is not None else root_path
+    done = 0
+    for cls_id in sorted(os.listdir(os.path.join(root_path, 'meshes'))):
+        if cls_id.endswith(('.log', '.yaml', '.py')) or not os.path.isdir(os.path.join(root_path, 'meshes', cls_id)):
+            continue
+        shape_names = sorted(os.listdir(os.path.join(root_path, 'meshes', cls_id)))
+        for i, name in enumerate(shape_names):
+            if names is not None and name not in names:
+                continue
+            save_path = os.path.join(out_root, 'rendered_imgs', cls_id, name)
+            if os.path.isdir(save_path) and len(os.listdir(save_path)) == 20:
+                continue
+            print(cls_id, i, '/', len(shape_names), name)
+            try:
+                mesh_file = _find_mesh_file(root_path, cls_id, name)
+                if per_vertex:
+                    v, f, c = io_utils.load_obj_vertex_colors(mesh_file)
+                    T = lambda x: torch.from_numpy(x).to(device)
+                    render_per_vertex_color_mesh(T(v), T(f), T(c), cams, save_path=save_path)
+                else:
+                    render_textured_mesh(mesh_file, cams, device, save_path, save=True)
+                io_utils.flush()
+                done += 1
+            except KeyboardInterrupt:
+                raise
+            except Exception:                      # noqa: BLE001 -- the reference logs the shape and goes on (:728-730)
+                log.error(f'{i},{name}')
+                log.error(traceback.format_exc())
+    return done

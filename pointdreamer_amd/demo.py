@@ -3,6 +3,7 @@ same YAML keys (configs/*.yaml of the reference) and the same output tree as /ro
 
   <output_path>/<ply stem>_<config stem>/config.yaml, input_pc.ply,
       models/model_normalized.{obj,mtl,png}, others/{k}_{sparse,mask0,mask2,inpainted}.png, others/atlas_wo_background.png
+      and, only with the opt-in key `render_views` (6 or 20; `render_res`, default 512): rendered_imgs/albedo_%03d.png
 
 Geometry: the reference's drop-in hooks -- `<pc>_untextured_mesh.obj` next to the PLY (demo.py:391-399), the cached
 `geo/<name>_untextured/models/model_normalized.obj` (demo.py:401-406) and the cached `geo/xatlas_<res>.pth` dict (demo.py:428-448)
@@ -34,6 +35,9 @@ SUPPORTED_KEYS = ('texture_gen_method', 'camera_distribution', 'cam_res', 'view_
                   'xatlas_texture_res', 'complete_unseen_by', 'output_path')
 # keys of this build's own stages in front of the texturing path (geo_from: 'SPR'): validated like the others, not pipeline arguments
 GEOMETRY_KEYS = ('spr_depth', 'spr_knn', 'spr_faces')
+# opt-in stage behind the texturing path: render_views (6 or 20 'self_defined' views) writes <out>/rendered_imgs/albedo_%03d.png at
+# render_res (default 512); without render_views nothing is rendered and the output tree is unchanged
+RENDER_KEYS = ('render_views', 'render_res')
 
 
 class Cfg(dict):
@@ -73,7 +77,7 @@ def load_config(cfg_file, overrides=None):
     are validated, upstream keys are kept but unused, an unknown key is an error (a typo must not silently fall back)."""
     cfg = Cfg(yaml.safe_load(open(cfg_file)))
     cfg.update(overrides or {})
-    unknown = [k for k in cfg if k not in SUPPORTED_KEYS and k not in UPSTREAM_KEYS and k not in GEOMETRY_KEYS]
+    unknown = [k for k in cfg if k not in SUPPORTED_KEYS and k not in UPSTREAM_KEYS and k not in GEOMETRY_KEYS and k not in RENDER_KEYS]
     if unknown:
         raise KeyError(f"{cfg_file}: unknown config keys {unknown}")
     if 'texture_gen_method' not in cfg:
@@ -91,6 +95,10 @@ def load_config(cfg_file, overrides=None):
         raise ValueError(f"spr_knn={cfg.spr_knn!r}: the normals of the SPR geometry take 3 .. 32 neighbours")
     if 'spr_faces' in cfg and not (isinstance(cfg.spr_faces, int) and not isinstance(cfg.spr_faces, bool) and cfg.spr_faces >= 4):
         raise ValueError(f"spr_faces={cfg.spr_faces!r}: the face count the SPR geometry is decimated to is an integer >= 4")
+    if 'render_views' in cfg and cfg.render_views not in (6, 20):
+        raise ValueError(f"render_views={cfg.render_views!r}: the 'self_defined' evaluation cameras come as 6 or 20 views")
+    if 'render_res' in cfg and not (isinstance(cfg.render_res, int) and not isinstance(cfg.render_res, bool) and 1 <= cfg.render_res <= 16384):
+        raise ValueError(f"render_res={cfg.render_res!r}: the side of the rendered views is an integer in 1 .. 16384")
     if cfg.optimize_from == 'None':                      # YAML `None` is the string 'None' (demo.py:213 treats both alike)
         cfg['optimize_from'] = None
     return cfg
@@ -157,6 +165,21 @@ def save_textured_mesh(vertices, uvs, faces, mesh_tex_idx, atlas_img, mask, outp
     # others/atlas_wo_background.png: the atlas with the chart mask as alpha (demo.py:296-303)
     rgba = torch.cat([atlas_img.float(), mask[0].to(atlas_img.device).float()], dim=-1)
     io_utils.save_CHW_RGBA_img(rgba.flip(0).permute(2, 0, 1), os.path.join(output_root_path, 'others', 'atlas_wo_background.png'))
+
+
+def render_result(cfg, vertices, uvs, faces, mesh_tex_idx, atlas_img, output_root_path, device, logger):
+    """The opt-in `render_views` stage: the in-memory result from the 'self_defined' evaluation cameras (camera_utils.py:165-201, as
+    render_textured_meshes_shapenet2 places them) -> <out>/rendered_imgs/albedo_%03d.png, RGBA.  Nothing without the key."""
+    if 'render_views' not in cfg:
+        return None
+    from .camera_utils import render_textured_mesh2
+    start = time.time()
+    cams, _, _, _ = create_cameras(num_views=cfg.render_views, distribution='self_defined', distance=1.6,
+                                   res=cfg.get('render_res', 512), device=device)
+    save_path = os.path.join(output_root_path, 'rendered_imgs')
+    render_textured_mesh2(vertices, faces, uvs, mesh_tex_idx, atlas_img, cams, save_path=save_path, save=True)
+    logger.info(f'rendered {cfg.render_views} views at {cfg.get("render_res", 512)}^2 -> {save_path} ({time.time() - start} s)')
+    return save_path
 
 
 def _load_shape(cfg, pc_file, name, device, logger):
@@ -244,6 +267,7 @@ def recon_one_textured_mesh(cfg, inpainter, camera_info, pc_file, name, device, 
     torch.cuda.synchronize()
     logger.info(f'generate texture time: {time.time() - start} s')
     save_textured_mesh(vertices, uvs, faces, mesh_tex_idx, atlas_img, mask, sh['out'])
+    render_result(cfg, vertices, uvs, faces, mesh_tex_idx, atlas_img, sh['out'], device, logger)
     logger.info(f'total time: {time.time() - all_start} s')
     return sh['out']
 
@@ -262,6 +286,7 @@ def recon_textured_meshes_batched(cfg, inpainter, camera_info, pc_files, names, 
     logger.info(f'generate texture time: {time.time() - start} s ({(time.time() - start) / len(shapes)} s per shape)')
     for sh, (vertices, uvs, faces, mesh_tex_idx, atlas_img, mask) in zip(shapes, results):
         save_textured_mesh(vertices, uvs, faces, mesh_tex_idx, atlas_img, mask, sh['out'])
+        render_result(cfg, vertices, uvs, faces, mesh_tex_idx, atlas_img, sh['out'], device, logger)
     logger.info(f'total time: {time.time() - all_start} s')
     return [sh['out'] for sh in shapes]
 
@@ -286,6 +311,7 @@ def recon_one_textured_mesh_view_parallel(cfg, inpainter, camera_info, pc_file, 
     logger.info(f'generate texture time: {time.time() - start} s')
     if rank == 0:
         save_textured_mesh(vertices, uvs, faces, mesh_tex_idx, atlas_img, mask, sh['out'])
+        render_result(cfg, vertices, uvs, faces, mesh_tex_idx, atlas_img, sh['out'], device, logger)
     logger.info(f'total time: {time.time() - all_start} s')
     return sh['out']
 

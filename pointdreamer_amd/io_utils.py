@@ -232,6 +232,27 @@ def load_obj_mesh(path, with_uv=False):
     return v, f, None, None
 
 
+def load_obj_vertex_colors(path):
+    """Vertices [Vn,3] f32, triangle faces [F,3] i64 and per-vertex colours [Vn,3] f32 in [0,1] of an OBJ with `v x y z r g b` records
+    (the per-vertex-colour meshes render_per_vertex_color_mesh draws, camera_utils.py:735-748); a vertex without a colour is an error."""
+    vs, cs, fs = [], [], []
+    with open(path) as f:
+        for line in f:
+            t = line.split()
+            if not t:
+                continue
+            if t[0] == 'v':
+                if len(t) < 7:
+                    raise ValueError(f"{path}: `v` record without r g b: not a per-vertex-colour OBJ")
+                vs.append([float(x) for x in t[1:4]])
+                cs.append([float(x) for x in t[4:7]])
+            elif t[0] == 'f':
+                idx = [int(x.split('/')[0]) for x in t[1:]]
+                for k in range(1, len(idx) - 1):
+                    fs.append([idx[0] - 1, idx[k] - 1, idx[k + 1] - 1])
+    return np.array(vs, np.float32), np.array(fs, np.int64), np.array(cs, np.float32)
+
+
 def save_obj_mesh(vertices, faces, path):
     """Untextured OBJ (`v x y z` / `f a b c`, 1-based) through the native writer: the wire format of the geo/<name>_untextured cache
     (what POCO / SPR leave, demo.py:401-406).  Coordinates carry 9 significant digits: load_obj_mesh returns the same float32 values."""
