@@ -165,6 +165,39 @@ int pdhip_simplify_mesh(const float* vertices /*[Vn,3]*/, int Vn, const int64_t*
                         int target_faces, float* out_vertices /*[Vn,3]*/, int64_t* out_faces /*[F,3]*/, float* out_colors /*[Vn,3] or NULL*/,
                         int32_t* counts /*device [4]: vertices, faces, rounds, flags (1 = stalled, 2 = bad input)*/, void* ws, void* stream);
 
+/* ---- Coloured clouds from textured meshes (data/sample_colored_pc_from_mesh.py:50-184: kal.ops.mesh.face_areas + sample_points and one
+ *      grid_sample per material there), csrc/sample_mesh.hip.  A deterministic function of explicit uniforms rand [N,3] f32 in [0,1):
+ *      kaolin's and torch's random streams are not reproduced.  vertices [Vn,3] f32, faces [F,3] i64, uvs [T,2] f32 with face_uvs_idx
+ *      [F,3] i64 (both or neither; -1 at a corner = that corner's UV is (0,0), :102-107), face_material [F] i32 (NULL: material 0),
+ *      face_keep [F] u8 (the reference's face_visibility; NULL: every face).  The material set of M materials: texels, u8 RGB images
+ *      one after the other, each row-major as its file stores it (row 0 at the top), texel_bytes in all; material m's image starts at
+ *      byte mat_offset[m] and is mat_wh[m] = (W, H) texels; mat_wh[m] = (0,0): no image, the colour is mat_kd[m] (mat_kd [M,3] f32).
+ *      Face choice: A_f = 0.5 sqrt(|cross(v1-v0, v2-v0)|^2) in f64 (0 where face_keep is 0), Amax by an integer atomic max on the bit
+ *      pattern, w_f = (uint64) floor(A_f * (2^40 / Amax)), cdf = inclusive uint64 prefix sum (the shared tiled scan), W = cdf[F-1];
+ *      m = (uint32) floor(rand0 * 2^24) (held to [0, 2^24) whatever rand0 is), t = (W * m) >> 24 with the product exact in 128 bits, face =
+ *      the smallest f with cdf[f] > t: exact integer arithmetic, so the choice does not depend on the scan order and a face of weight 0 is
+ *      never drawn.  (u, v) = (rand1, rand2), folded to (1-u, 1-v) where u + v > 1 (kaolin); coords = (v0 + u (v1-v0)) + v (v2-v0) in f32
+ *      op by op, uvs_out the same over the corner UVs, stored BEFORE the wrap (:179); normals = the unit face normal in f32
+ *      (camera_utils.face_normals_unit, norm clamped at 1e-30); colors: mat_kd, or with fr = uv - floor(uv), gx = fr_u*2 - 1,
+ *      gy = -(fr_v*2 - 1), x = ((gx+1) W - 1)/2, y = ((gy+1) H - 1)/2 clamped to [0, W-1] x [0, H-1] the bilinear blend
+ *      top + fy (bot - top), top = t00 + fx (t01 - t00), over texels t/255.0f (:161-170: grid_sample align_corners=False,
+ *      padding_mode='border').  Outputs coords, colors, normals [N,3] f32, uvs_out [N,2] f32, face_idx, material_idx [N] i32.
+ *      face_idx ALWAYS indexes the caller's `faces`: the reference, given face_visibility, returns indices into the FILTERED face list
+ *      next to normals of the unfiltered one (:110-113 against :173); that slip is not reproduced.
+ *      An index outside its table is never dereferenced: a vertex index outside [0, Vn), a uv index outside [-1, T), a material index
+ *      outside [0, M), an image outside the texel_bytes, a non-finite area -- the area pass skips the face and sets an error word; no
+ *      face with positive area; F > 2^22 (refused before any launch): PDHIP_E_ARG with the cause, outputs untouched.  N = 0: the
+ *      checks run, nothing is written, PDHIP_OK.  Synchronises `stream` ONCE (the error word and Amax, one read).  No floating-point
+ *      atomics: two calls give equal bits.  ws: pdhip_sample_mesh_workspace_bytes(F, N) bytes (0 for F outside [1, 2^22]), carved by
+ *      the one layout function both share.  Measured: profiles/sample_pc_bench.txt. */
+size_t pdhip_sample_mesh_workspace_bytes(int F, int N);
+int pdhip_sample_mesh(const float* vertices /*[Vn,3]*/, int Vn, const int64_t* faces /*[F,3]*/, int F, const float* uvs /*[T,2] or NULL*/, int T,
+                      const int64_t* face_uvs_idx /*[F,3] or NULL*/, const int32_t* face_material /*[F] or NULL*/,
+                      const uint8_t* face_keep /*[F] or NULL*/, const uint8_t* texels /*[texel_bytes] or NULL*/, int64_t texel_bytes,
+                      const int64_t* mat_offset /*[M]*/, const int32_t* mat_wh /*[M,2]*/, const float* mat_kd /*[M,3]*/, int M,
+                      const float* rand /*[N,3]*/, int N, float* coords /*[N,3]*/, float* colors /*[N,3]*/, float* normals /*[N,3]*/,
+                      float* uvs_out /*[N,2]*/, int32_t* face_idx /*[N]*/, int32_t* material_idx /*[N]*/, void* ws, void* stream);
+
 /* ---- SURVEY 8(e) configs[4], round 4: S independent shapes of EQUAL sizes (Vn vertices, F faces, N points, atlas A) through the same V
  *      cameras in ONE launch per stage.  Per-shape inputs are stacked ([S, ...]); every per-view array has S*V leading entries, view
  *      g = s * V + v; results equal the per-shape entry points bit for bit (tests/test_gpu_round4.py).  The per-view-independent stages

@@ -1,5 +1,5 @@
-// Radix sort (LSD, 8-bit digits, stable) of 64-bit keys with int32 values, a one-workgroup scan and a tiled exclusive scan over many
-// workgroups: shared by the geometry units that sort or scan on the device (uv_atlas.hip: edge keys, packing order, UV entries;
+// Radix sort (LSD, 8-bit digits, stable) of 64-bit keys with int32 values, a one-workgroup scan and a tiled scan over many
+// workgroups (both templated on the element type): shared by the geometry units that sort or scan on the device (uv_atlas.hip: edge keys, packing order, UV entries;
 // surface_recon.hip: cell keys, vertex / triangle offsets; neighbor_mesh.hip: edge and pair keys; simplify_mesh.hip: directed-edge keys, adjacency / winner / face offsets).  Written
 // here because rocPRIM's sort carries scratch on gfx950.  Every kernel has internal linkage: each including unit gets its own copy.
 #pragma once
@@ -71,71 +71,83 @@ __global__ __launch_bounds__(RS_T) void k_rs_scatter(const uint64_t* __restrict_
     }
 }
 
-// one workgroup: out[i] = sum of in[0..i] (inclusive) or in[0..i) (exclusive)
+// one workgroup: out[i] = sum of in[0..i] (inclusive) or in[0..i) (exclusive).  T: int (every unit above) or uint64_t (sample_mesh.hip:
+// the integer CDF); the launches deduce it from their pointers
 constexpr int SC_T = 1024;
-__global__ __launch_bounds__(SC_T) void k_scan(const int* __restrict__ in, int* __restrict__ out, int n, int exclusive) {
-    __shared__ int part[SC_T];
+template <class T>
+__global__ __launch_bounds__(SC_T) void k_scan(const T* __restrict__ in, T* __restrict__ out, int n, int exclusive) {
+    __shared__ T part[SC_T];
     const int t = threadIdx.x;
     const int chunk = (n + SC_T - 1) / SC_T;
     const int b = min(n, t * chunk), e = min(n, b + chunk);
-    int s = 0;
+    T s = 0;
     for (int i = b; i < e; ++i) s += in[i];
     part[t] = s;
     __syncthreads();
     for (int off = 1; off < SC_T; off <<= 1) {                    // Hillis-Steele inclusive scan of the chunk sums
-        const int add = t >= off ? part[t - off] : 0;
+        const T add = t >= off ? part[t - off] : 0;
         __syncthreads();
         part[t] += add;
         __syncthreads();
     }
-    int run = part[t] - s;
+    T run = part[t] - s;
     for (int i = b; i < e; ++i) {
-        const int x = in[i];
+        const T x = in[i];
         out[i] = exclusive ? run : run + x;
         run += x;
     }
 }
 
-// exclusive scan of n ints over many workgroups: tiles of 2048 (their sums scanned by the one-workgroup k_scan), then the offsets added
+// scan of n elements over many workgroups: tiles of 2048 (their sums scanned by the one-workgroup k_scan), then the offsets added.
+// INCL = false: out[i] = in[0] + ... + in[i - 1]; true: ... + in[i]
 constexpr int SCB_T = 256, SCB_ITEMS = 8, SCB_TILE = SCB_T * SCB_ITEMS;
-__global__ __launch_bounds__(SCB_T) void k_scan_tiles(const int* __restrict__ in, int* __restrict__ out, long long n, int* __restrict__ sums) {
-    __shared__ int part[SCB_T];
+template <class T, bool INCL>
+__global__ __launch_bounds__(SCB_T) void k_scan_tiles(const T* __restrict__ in, T* __restrict__ out, long long n, T* __restrict__ sums) {
+    __shared__ T part[SCB_T];
     const int t = threadIdx.x;
     const long long base = (long long)blockIdx.x * SCB_TILE + (long long)t * SCB_ITEMS;
-    int v[SCB_ITEMS];
-    int s = 0;
+    T v[SCB_ITEMS];
+    T s = 0;
 #pragma unroll
     for (int k = 0; k < SCB_ITEMS; ++k) {
-        v[k] = s;
+        if (!INCL) v[k] = s;
         s += base + k < n ? in[base + k] : 0;
+        if (INCL) v[k] = s;
     }
     part[t] = s;
     __syncthreads();
     for (int off = 1; off < SCB_T; off <<= 1) {
-        const int add = t >= off ? part[t - off] : 0;
+        const T add = t >= off ? part[t - off] : 0;
         __syncthreads();
         part[t] += add;
         __syncthreads();
     }
-    const int excl = part[t] - s;
+    const T excl = part[t] - s;
 #pragma unroll
     for (int k = 0; k < SCB_ITEMS; ++k)
         if (base + k < n) out[base + k] = excl + v[k];
     if (t == SCB_T - 1) sums[blockIdx.x] = part[t];
 }
-__global__ void k_scan_add(int* __restrict__ out, long long n, const int* __restrict__ offs) {
+template <class T>
+__global__ void k_scan_add(T* __restrict__ out, long long n, const T* __restrict__ offs) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] += offs[i / SCB_TILE];
 }
-// ints that tsum and toff must each hold for a scan of n elements (what a carve function takes for them)
+// elements that tsum and toff must each hold for a scan of n elements (what a carve function takes for them)
 constexpr size_t scan_tiles(size_t n) { return n / SCB_TILE + 1; }
-// out[i] = in[0] + ... + in[i - 1] for 0 < n <= 2^31 elements whose sum fits an int
-static void scan_exclusive(const int* in, int* out, long long n, int* tsum, int* toff, hipStream_t s) {
+template <class T, bool INCL>
+static void scan_tiled(const T* in, T* out, long long n, T* tsum, T* toff, hipStream_t s) {
     const int nt = cdiv(n, SCB_TILE);
-    k_scan_tiles<<<nt, SCB_T, 0, s>>>(in, out, n, tsum);
-    k_scan<<<1, SC_T, 0, s>>>(tsum, toff, nt, 1);
-    k_scan_add<<<cdiv(n, 256), 256, 0, s>>>(out, n, toff);
+    k_scan_tiles<T, INCL><<<nt, SCB_T, 0, s>>>(in, out, n, tsum);
+    k_scan<T><<<1, SC_T, 0, s>>>(tsum, toff, nt, 1);
+    k_scan_add<T><<<cdiv(n, 256), 256, 0, s>>>(out, n, toff);
 }
+// out[i] = in[0] + ... + in[i - 1] for 0 < n <= 2^31 elements whose sum fits a T
+template <class T>
+static void scan_exclusive(const T* in, T* out, long long n, T* tsum, T* toff, hipStream_t s) { scan_tiled<T, false>(in, out, n, tsum, toff, s); }
+// out[i] = in[0] + ... + in[i]
+template <class T>
+static void scan_inclusive(const T* in, T* out, long long n, T* tsum, T* toff, hipStream_t s) { scan_tiled<T, true>(in, out, n, tsum, toff, s); }
 
 struct SortBufs {
     uint64_t* k[2];
@@ -159,7 +171,7 @@ static int radix_sort(SortBufs& sb, int n, int bits, hipStream_t s) {
     int cur = 0;
     for (int shift = 0; shift < bits; shift += 8) {
         k_rs_hist<<<nblk, RS_T, 0, s>>>(sb.k[cur], n, shift, sb.hist, nblk);
-        k_scan<<<1, SC_T, 0, s>>>(sb.hist, sb.hist + 256 * nblk, 256 * nblk, 1);
+        k_scan<int><<<1, SC_T, 0, s>>>(sb.hist, sb.hist + 256 * nblk, 256 * nblk, 1);
         k_rs_scatter<<<nblk, RS_T, 0, s>>>(sb.k[cur], sb.v[cur], n, shift, sb.hist + 256 * nblk, nblk, sb.k[cur ^ 1], sb.v[cur ^ 1]);
         cur ^= 1;
     }
