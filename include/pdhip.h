@@ -91,6 +91,35 @@ int pdhip_shade_views(const int64_t* face_idxs /*[V,R,R]*/, const float* bary /*
                       const float* light_dirs /*[L,3] or NULL*/, int L, int double_side, double gamma, float* images /*[V,3,R,R] or NULL*/,
                       uint8_t* rgba /*[V,R,R,4] or NULL*/, void* stream);
 
+/* ---- The same shading stage for meshes with SEVERAL materials (render_textured_mesh, camera_utils.py:379-554: face_material_idx[face_idx]
+ *      per pixel, then one grid_sample per material per view there; one pass per output pixel here -- no uv map, no albedo image and no
+ *      per-material mask in HBM).  face_idxs / bary / V / R, lighting, clip, gamma, the vertical flip, images and rgba: exactly the
+ *      contract of pdhip_shade_views (one __device__ tail serves both kernels).  Per covered pixel of face f: corner UVs
+ *      uvs[face_uvs_idx[f][k]] (uvs [T,2] f32 with face_uvs_idx [F,3] i64, both or neither; an index of -1, or no table: that corner's
+ *      UV is (0,0), :397, :427-428), uv = (u*a0 + v*a1) + ((1-u)-v)*a2 (the contract of pdhip_interpolate), m = face_material[f]
+ *      (face_material [F] i32; NULL: material 0).  The material set is pdhip_sample_mesh's: texels (u8 RGB images one after the other,
+ *      rows as their files store them, row 0 at the top, texel_bytes in all), mat_offset [M] i64, mat_wh [M,2] i32 = (W, H), mat_kd
+ *      [M,3] f32, 1 <= M <= 255.  mat_wh[m] = (0,0): the colour is mat_kd[m] bit for bit.  Otherwise the lookup rule written down under
+ *      pdhip_sample_mesh, operation for operation (csrc/texture_lookup.h, the one definition both kernels call): fr = uv - floor(uv),
+ *      gx = fr_u*2 - 1, gy = -(fr_v*2 - 1), x = ((gx+1) W - 1)/2, y = ((gy+1) H - 1)/2 clamped to [0, W-1] x [0, H-1] (NaN -> 0), the
+ *      blend top + fy (bot - top), top = t00 + fx (t01 - t00), over texels t/255.0f.  (A square image I looked up here is atlas = I
+ *      flipped vertically / 255 looked up by pdhip_shade_views.)  material_idx [V,R,R] i32 (may be NULL): m per pixel, flipped like the
+ *      images, -1 where uncovered.  Nothing outside a table is dereferenced: a face index outside [0, F), a uv index outside [-1, T), a
+ *      material outside [0, M), or an image (mat_offset, mat_wh) that does not lie inside the texel_bytes leaves the pixel UNCOVERED --
+ *      colour exactly 0, alpha 0, material -1.  Refused before any launch (PDHIP_E_ARG): V, R, F not positive or R > 16384, V > 65536;
+ *      M outside 1 .. 255; uvs without face_uvs_idx or the reverse, T <= 0 with them; texels NULL with texel_bytes > 0; images and rgba
+ *      both NULL; L outside 0 .. 16, lights without normals and cameras, gamma without lights.  Does not synchronise.
+ *      Measured: profiles/render_materials_bench.txt. */
+int pdhip_shade_views_materials(const int64_t* face_idxs /*[V,R,R]*/, const float* bary /*[V,R,R,2]*/, int V, int R,
+                                const float* uvs /*[T,2] or NULL*/, int T, const int64_t* face_uvs_idx /*[F,3] or NULL*/,
+                                const int32_t* face_material /*[F] or NULL: material 0*/, int F,
+                                const uint8_t* texels /*[texel_bytes] or NULL*/, int64_t texel_bytes, const int64_t* mat_offset /*[M]*/,
+                                const int32_t* mat_wh /*[M,2]*/, const float* mat_kd /*[M,3]*/, int M,
+                                const float* face_normals /*[F,3] or NULL*/, const float* cam_params /*[V,16] or NULL*/,
+                                const float* light_dirs /*[L,3] or NULL*/, int L, int double_side, double gamma,
+                                float* images /*[V,3,R,R] or NULL*/, uint8_t* rgba /*[V,R,R,4] or NULL*/,
+                                int32_t* material_idx /*[V,R,R] or NULL*/, void* stream);
+
 /* ---- Image metrics of the evaluation (utils/metric_utils/psnr_ssmi.py:44-147): a, b [N,H,W,C] u8 (C <= 4) -> per image sse [N] u64, the
  *      exact sum of squared differences (PSNR = 10 log10(255^2 H W C / sse) is left to the host), and ssim [N] f64, the mean SSIM with
  *      C1 = (0.01*255)^2, C2 = (0.03*255)^2 (either may be NULL).  gaussian = 0: skimage.metrics.structural_similarity(data_range=255,

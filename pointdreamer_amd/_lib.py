@@ -36,6 +36,7 @@ _SIGS = {
     'pdhip_raster_barycentrics': (C.c_int, [vp, i32, i32, vp, i32, vp, vp, vp]),
     'pdhip_interpolate': (C.c_int, [vp, i32, vp, vp, vp, C.c_longlong, vp, vp]),
     'pdhip_shade_views': (C.c_int, [vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, f64, vp, vp, vp]),
+    'pdhip_shade_views_materials': (C.c_int, [vp, vp, i32, i32, vp, i32, vp, vp, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp, i32, i32, f64, vp, vp, vp, vp]),
     'pdhip_image_metrics_workspace_bytes': (sz, [i32, i32, i32]),
     'pdhip_image_metrics': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     'pdhip_uv_atlas_ws_bytes': (sz, [i32, i32]),

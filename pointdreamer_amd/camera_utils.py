@@ -205,6 +205,98 @@ def shade_views(face_idxs, bary, attr, tri, atlas=None, face_normals=None, cam_p
     return images, rgba
 
 
+def check_packed_materials(materials):
+    """Host-side check of a packed material set (texels u8 [B], mat_offset i64 [M], mat_wh i32 [M,2], mat_kd f32 [M,3], the four
+    tensors of sample_colored_pc_from_mesh.pack_materials): 1 <= M <= 255, shapes, dtypes, and every image inside `texels`.
+    ValueError with the cause; returns M.  Reads mat_offset and mat_wh on the host (one synchronisation for device tensors)."""
+    if not isinstance(materials, (tuple, list)) or len(materials) != 4 or not all(torch.is_tensor(t) for t in materials):
+        raise ValueError("packed materials: expected the four tensors (texels, mat_offset, mat_wh, mat_kd) of pack_materials")
+    texels, off, wh, kd = materials
+    if texels.dtype != torch.uint8 or texels.dim() != 1:
+        raise ValueError(f"packed materials: texels must be uint8 [bytes], got {texels.dtype} {tuple(texels.shape)}")
+    M = off.shape[0] if off.dim() == 1 else -1
+    if off.dtype != torch.int64 or wh.dtype != torch.int32 or kd.dtype != torch.float32:
+        raise ValueError(f"packed materials: mat_offset / mat_wh / mat_kd must be int64 / int32 / float32, got {off.dtype} / {wh.dtype} / {kd.dtype}")
+    if M < 0 or tuple(wh.shape) != (M, 2) or tuple(kd.shape) != (M, 3):
+        raise ValueError(f"packed materials: mat_offset [M], mat_wh [M,2], mat_kd [M,3] expected, got {tuple(off.shape)} / "
+                         f"{tuple(wh.shape)} / {tuple(kd.shape)}")
+    if not 1 <= M <= 255:
+        raise ValueError(f"packed materials: {M} materials (1 .. 255)")
+    total = int(texels.numel())
+    for m, (o, (w, h)) in enumerate(zip(off.cpu().tolist(), wh.cpu().tolist())):
+        if w == 0 and h == 0:
+            continue
+        if w <= 0 or h <= 0 or o < 0 or o + 3 * w * h > total:
+            raise ValueError(f"packed materials: image of material {m} ({w} x {h} at byte {o}) does not lie inside the {total} texel bytes")
+    return M
+
+
+def shade_views_materials(face_idxs, bary, uvs, face_uvs_idx, face_material, materials, face_normals=None, cam_params=None,
+                          light_dirs=None, double_side=False, gamma=None, want_images=True, want_rgba=False, want_material_idx=False):
+    """pdhip_shade_views_materials (include/pdhip.h has the contract): face_idxs [V,R,R] i64 / bary [V,R,R,2] as rasterize() returns
+    them, uvs [T,2] with face_uvs_idx [F,3] (-1: that corner's UV is (0,0); both may be None), face_material [F] (None: material 0),
+    materials: the list load_obj_with_materials returns, or the four tensors of pack_materials (checked on the host once per tuple:
+    check_packed_materials) -> (images [V,3,R,R] f32 or None, rgba [V,R,R,4] u8 or None), row 0 at the top, and with
+    want_material_idx a third value, the material per pixel [V,R,R] i32 (-1 where uncovered).  Lighting as in shade_views; the number
+    of faces F is that of face_material, else of face_uvs_idx, else of face_normals."""
+    from . import _lib
+    from ._lib import ptr, stream, check
+    from .sample_colored_pc_from_mesh import pack_materials, _on as move
+    dev = face_idxs.device
+    # (a tensor that is already in place costs nothing: one call is tens of microseconds)
+    _on = lambda x, dev, dtype: x if (torch.is_tensor(x) and x.device == dev and x.dtype == dtype and x.is_contiguous()) else move(x, dev, dtype)
+    if isinstance(materials, tuple):
+        _lib.memo(list(materials), 'check_packed_materials', check_packed_materials)
+        texels, mat_offset, mat_wh, mat_kd = (_on(t, dev, t.dtype) for t in materials)
+    else:
+        texels, mat_offset, mat_wh, mat_kd = pack_materials(materials, dev)
+    L = _lib.lib()
+    V, R = face_idxs.shape[0], face_idxs.shape[1]
+    if face_idxs.shape[2] != R:
+        raise ValueError(f"shade_views_materials: square views only, got {tuple(face_idxs.shape)}")
+    if tuple(bary.shape) != (V, R, R, 2):
+        raise ValueError(f"shade_views_materials: bary must be [V,R,R,2] = {(V, R, R, 2)}, got {tuple(bary.shape)}")
+    uvs, face_uvs_idx = _on(uvs, dev, torch.float32), _on(face_uvs_idx, dev, torch.int64)
+    face_material = _on(face_material, dev, torch.int32)
+    if face_uvs_idx is not None and (face_uvs_idx.dim() != 2 or face_uvs_idx.shape[1] != 3):
+        raise ValueError(f"shade_views_materials: face_uvs_idx must be [F,3], got {tuple(face_uvs_idx.shape)}")
+    if face_material is not None and face_material.dim() != 1:
+        raise ValueError(f"shade_views_materials: face_material must be [F], got {tuple(face_material.shape)}")
+    if uvs is not None and uvs.numel() and (uvs.dim() != 2 or uvs.shape[1] != 2):
+        raise ValueError(f"shade_views_materials: uvs must be [T,2], got {tuple(uvs.shape)}")
+    sizes = [t.shape[0] for t in (face_material, face_uvs_idx, face_normals) if t is not None]
+    if not sizes or any(n != sizes[0] for n in sizes):
+        raise ValueError(f"shade_views_materials: face_material, face_uvs_idx and face_normals must agree on the number of faces (got {sizes})")
+    F = sizes[0]
+    if uvs is None or face_uvs_idx is None or uvs.numel() == 0:
+        if uvs is not None and face_uvs_idx is not None and bool((face_uvs_idx >= 0).any()):
+            raise ValueError("shade_views_materials: face_uvs_idx refers to an empty uv table")
+        uvs = face_uvs_idx = None
+    nl = 0
+    if light_dirs is not None:
+        light_dirs = torch.as_tensor(light_dirs, dtype=torch.float32, device=dev).reshape(-1, 3).contiguous()
+        nl = light_dirs.shape[0]
+        if face_normals is None or cam_params is None:
+            raise ValueError("shade_views_materials: light_dirs needs face_normals and cam_params")
+        face_normals = face_normals.float().contiguous()
+        cam_params = cam_params.float().contiguous()
+        if tuple(cam_params.shape) != (V, 16):
+            raise ValueError(f"shade_views_materials: cam_params must be [V,16], got {tuple(cam_params.shape)}")
+    else:
+        face_normals = cam_params = None
+    images = torch.empty((V, 3, R, R), device=dev) if want_images else None
+    rgba = torch.empty((V, R, R, 4), dtype=torch.uint8, device=dev) if want_rgba else None
+    midx = torch.empty((V, R, R), dtype=torch.int32, device=dev) if want_material_idx else None
+    opt = lambda t, dt=None: ptr(t, dt, allow_none=True) if t is not None and t.numel() else ptr(None, allow_none=True)
+    check(L.pdhip_shade_views_materials(
+        ptr(face_idxs.contiguous(), torch.int64), ptr(bary.contiguous(), torch.float32), V, R, opt(uvs), 0 if uvs is None else uvs.shape[0],
+        opt(face_uvs_idx), opt(face_material), F, opt(texels, torch.uint8), int(texels.numel()), ptr(mat_offset, torch.int64),
+        ptr(mat_wh, torch.int32), ptr(mat_kd, torch.float32), mat_offset.shape[0], opt(face_normals), opt(cam_params), opt(light_dirs), nl,
+        int(bool(double_side)), float(gamma) if (gamma is not None and nl) else 0.0, opt(images), opt(rgba), opt(midx), stream()),
+        'pdhip_shade_views_materials')
+    return (images, rgba, midx) if want_material_idx else (images, rgba)
+
+
 def _save_views(rgba, save_path):
     """albedo_001.png ... as RGBA (camera_utils.py:534-550); the 8-bit images come from the kernel as they are written."""
     import os
@@ -267,6 +359,37 @@ def render_textured_mesh2(vertices, faces, uvs, face_uvs_idx, atlas_img, cams, r
                    return_mask, hook)
 
 
+def render_material_mesh(vertices, faces, uvs, face_uvs_idx, face_material, materials, cams, save_path=None, save=False,
+                         normalize_mesh=False, light_dirs=None, gamma=None, double_side=False, return_mask=False):
+    """The tensor-level renderer of a mesh with per-face materials (camera_utils.py:379-554 after the loading): vertices [Vn,3],
+    faces [F,3], uvs [T,2] with face_uvs_idx [F,3] (-1: (0,0); both may be None), face_material [F] (None: material 0), materials
+    (the loader's list or the four tensors of pack_materials) -> images [V,3,R,R] with row 0 at the top, uncovered pixels exactly 0
+    (with return_mask=True also the hard mask [V,R,R], flipped alike); with save and save_path also albedo_001.png ... as RGBA.
+    _render's stages: clip positions, rasterize, face normals when lit, one shading pass (pdhip_shade_views_materials), _save_views.
+    The caller's `vertices` are never modified."""
+    from .extract_texture_map import rasterize
+    from .sample_colored_pc_from_mesh import _on
+    if not (torch.is_tensor(vertices) and vertices.is_cuda):
+        from . import _lib
+        raise _lib.PdhipError("render_material_mesh: expected vertices on the GPU; pointdreamer_amd has no CPU path")
+    vertices = vertices.detach().float().contiguous()
+    if normalize_mesh:
+        vertices = _normalized(vertices).contiguous()
+    faces = _on(faces, vertices.device, torch.int64)
+    res = int(cams[0].height)
+    pos, cp = _clip_positions(cams, vertices)
+    fidx, bary, _, hard = rasterize(pos, faces, res)
+    fn = face_normals_unit(vertices, faces) if light_dirs is not None else None
+    if face_material is None and face_uvs_idx is None:
+        face_material = torch.zeros((faces.shape[0],), dtype=torch.int32, device=vertices.device)
+    images, rgba = shade_views_materials(fidx, bary, uvs, face_uvs_idx, face_material, materials, face_normals=fn, cam_params=cp,
+                                         light_dirs=light_dirs, double_side=double_side, gamma=gamma, want_images=True,
+                                         want_rgba=bool(save and save_path))
+    if rgba is not None:
+        _save_views(rgba, save_path)
+    return (images, hard.flip(1)) if return_mask else images
+
+
 def _load_mtl(path):
     """[(name, dict)] of an MTL file: Kd as three floats, map_Kd as a path relative to the file."""
     mats = []
@@ -318,19 +441,62 @@ def load_textured_obj(mesh_file, device):
     return T(v), T(f), T(vt), T(ft), atlas
 
 
+def _single_atlas_file(mesh_file):
+    """True when load_textured_obj takes the file: at most one material (MTL entries and `usemtl` names), whose image, if any, is
+    square.  Reads the MTL and the image's header only."""
+    import os
+    import PIL.Image
+    mtllib, used = None, []
+    with open(mesh_file) as fh:
+        for line in fh:
+            t = line.split()
+            if t and t[0] == 'mtllib' and len(t) > 1:
+                mtllib = t[1]
+            elif t and t[0] == 'usemtl' and len(t) > 1 and t[1] not in used:
+                used.append(t[1])
+    mats = _load_mtl(os.path.join(os.path.dirname(mesh_file), mtllib)) if mtllib else []
+    if len(mats) > 1 or len(used) > 1:
+        return False
+    if mats and 'map_Kd' in mats[0][1]:
+        with PIL.Image.open(os.path.join(os.path.dirname(mesh_file), mats[0][1]['map_Kd'])) as im:
+            return im.size[0] == im.size[1]
+    return True
+
+
 def render_textured_mesh(mesh_file, cams, device, save_path, glctx=None, save=True, vertices=None, normalize_mesh=True, light_dirs=None,
                          gamma=None, double_side=False, geo_only=False, color=[0.5, 0.5, 0.5]):
-    """camera_utils.py:379-554: render an OBJ + MTL (+ atlas PNG) from every camera -> images [V,3,R,R]; with save=True also
-    <save_path>/albedo_001.png ... as RGBA (alpha = coverage).  One material only: its `map_Kd`, or its `Kd` as a 1x1 atlas; more
-    than one material raises NotImplementedError.  geo_only renders the constant `color`.  `glctx` is ignored."""
-    v, f, vt, ft, atlas = load_textured_obj(mesh_file, device)
+    """camera_utils.py:379-554: render an OBJ + MTL (+ images) from every camera -> images [V,3,R,R]; with save=True also
+    <save_path>/albedo_001.png ... as RGBA (alpha = coverage).  A file with one material -- its square `map_Kd`, or its `Kd` as a
+    1x1 atlas -- goes through load_textured_obj and render_textured_mesh2 (pdhip_shade_views).  Every other file -- several
+    `newmtl` / `usemtl`, a non-square `map_Kd` -- goes through sample_colored_pc_from_mesh.load_obj_with_materials and
+    render_material_mesh (pdhip_shade_views_materials: the material of the face per pixel, `map_Kd` images of any size next to `Kd`
+    colours).  geo_only renders the constant `color` for every material.  `glctx` is ignored; the caller's `vertices` are not modified."""
+    if _single_atlas_file(mesh_file):
+        v, f, vt, ft, atlas = load_textured_obj(mesh_file, device)
+        if vertices is not None:
+            assert vertices.shape[0] == v.shape[0]
+            v = vertices.to(device)
+        if geo_only:
+            atlas = torch.tensor(list(color), dtype=torch.float32, device=device).reshape(1, 1, 3)
+        return render_textured_mesh2(v, f, vt, ft, atlas, cams, save_path=save_path, save=save, normalize_mesh=normalize_mesh,
+                                     light_dirs=light_dirs, gamma=gamma, double_side=double_side)
+    from .sample_colored_pc_from_mesh import load_obj_with_materials
+    v, f, vt, ft, fm, materials = load_obj_with_materials(mesh_file)
     if vertices is not None:
         assert vertices.shape[0] == v.shape[0]
         v = vertices.to(device)
+    else:
+        v = torch.from_numpy(v).to(device)
     if geo_only:
-        atlas = torch.tensor(list(color), dtype=torch.float32, device=device).reshape(1, 1, 3)
-    return render_textured_mesh2(v, f, vt, ft, atlas, cams, save_path=save_path, save=save, normalize_mesh=normalize_mesh,
-                                 light_dirs=light_dirs, gamma=gamma, double_side=double_side)
+        materials = [{'name': m['name'], 'Kd': np.asarray(list(color), np.float32)} for m in materials]
+    return render_material_mesh(v, f, vt, ft, fm, materials, cams, save_path=save_path, save=save, normalize_mesh=normalize_mesh,
+                                light_dirs=light_dirs, gamma=gamma, double_side=double_side)
+
+
+def render_textured_mesh_w_mask(mesh_file, cams, device, save_path, glctx=None, save=True, vertices=None, normalize_mesh=True):
+    """camera_utils.py:556-676: render_textured_mesh without lighting.  Returns the images [V,3,R,R], as the reference's does
+    despite its name (the coverage is the alpha of the saved files)."""
+    return render_textured_mesh(mesh_file, cams, device, save_path, glctx=glctx, save=save, vertices=vertices, normalize_mesh=normalize_mesh)
 
 
 def render_per_vertex_color_mesh(vertices, faces, vertex_colors, cams, save_path=None, light_dirs=None, gamma=None, double_side=False):
@@ -352,8 +518,9 @@ def _find_mesh_file(root_path, cls_id, name):
 
 def render_textured_meshes_shapenet2(names=None, root_path=None, device=None, save_root_path=None, glctx=None, per_vertex=False):
     """camera_utils.py:680-730: every <root_path>/meshes/<cls_id>/<name>/models/model_normalized.obj (or the reference's three other
-    layouts) from the 20 'self_defined' views at 1024^2 into <root_path>/rendered_imgs/<cls_id>/<name>/albedo_%03d.png (RGBA).  A shape
-    whose 20 files exist is skipped; a shape that fails is logged and the run goes on.  Returns the number of shapes rendered."""
+    layouts) from the 20 'self_defined' views at 1024^2 into <root_path>/rendered_imgs/<cls_id>/<name>/albedo_%03d.png (RGBA).  Files
+    with several materials and `map_Kd` images of any size are rendered (render_textured_mesh routes them to render_material_mesh).
+    A shape whose 20 files exist is skipped; a shape that fails is logged and the run goes on.  Returns the number of shapes rendered."""
     import os
     import logging
     import traceback

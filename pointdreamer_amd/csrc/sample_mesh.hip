@@ -7,6 +7,7 @@
 //   k_smp_draw    one thread per sample: t = (W * m) >> 24 in 128 bits, binary search, fold, position / UV / normal, texture lookup
 // No floating-point atomics; the host reads two words once (error flags, Amax).
 #include "radix_sort.h"
+#include "texture_lookup.h"
 
 namespace pdhip {
 namespace {
@@ -67,10 +68,6 @@ __global__ __launch_bounds__(TB) void k_smp_weight(const double* __restrict__ ar
     w[f] = (uint64_t)floor(area[f] * scale);
 }
 
-__device__ __forceinline__ float texel(const uint8_t* __restrict__ img, int W, int x, int y, int c) {
-    return (float)img[((size_t)y * W + x) * 3 + c] / 255.0f;
-}
-
 __global__ __launch_bounds__(TB) void k_smp_draw(const float* __restrict__ vertices, const int64_t* __restrict__ faces, int F,
                                                  const float* __restrict__ uvs, const int64_t* __restrict__ face_uvs_idx,
                                                  const int32_t* __restrict__ face_material, const uint8_t* __restrict__ texels,
@@ -126,26 +123,7 @@ __global__ __launch_bounds__(TB) void k_smp_draw(const float* __restrict__ verti
     if (W == 0 && H == 0) {
         cr = mat_kd[3 * mat]; cg = mat_kd[3 * mat + 1]; cb = mat_kd[3 * mat + 2];
     } else {
-        // sample_colored_pc_from_mesh.py:161-170: (uv % 1) * 2 - 1, v negated, grid_sample(align_corners=False, padding_mode='border')
-        const float fu = pu - floorf(pu), fv = pv - floorf(pv);
-        const float gx = fu * 2.0f - 1.0f, gy = -(fv * 2.0f - 1.0f);
-        float x = ((gx + 1.0f) * (float)W - 1.0f) / 2.0f, y = ((gy + 1.0f) * (float)H - 1.0f) / 2.0f;
-        x = fminf(fmaxf(x, 0.0f), (float)(W - 1));
-        y = fminf(fmaxf(y, 0.0f), (float)(H - 1));
-        if (!(x == x)) x = 0.0f;
-        if (!(y == y)) y = 0.0f;
-        const int x0 = (int)x, y0 = (int)y, x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-        const float fx = x - (float)x0, fy = y - (float)y0;
-        const uint8_t* img = texels + mat_offset[mat];
-        float out[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float t00 = texel(img, W, x0, y0, c), t01 = texel(img, W, x1, y0, c);
-            const float t10 = texel(img, W, x0, y1, c), t11 = texel(img, W, x1, y1, c);
-            const float top = t00 + fx * (t01 - t00), bot = t10 + fx * (t11 - t10);
-            out[c] = top + fy * (bot - top);
-        }
-        cr = out[0]; cg = out[1]; cb = out[2];
+        material_lookup(texels + mat_offset[mat], W, H, pu, pv, cr, cg, cb);                // texture_lookup.h, shared with the renderer
     }
     colors[3 * i] = cr; colors[3 * i + 1] = cg; colors[3 * i + 2] = cb;
 }

@@ -6,8 +6,9 @@
 
   python -m pointdreamer_amd.render_meshes --rootpath <rootpath> --by kaolin|kaolin_per_vertex
 
-`--by` keeps the reference's two values: 'kaolin' renders textured OBJ files, 'kaolin_per_vertex' OBJ files with `v x y z r g b`
-records; both run on this build's device rasteriser and shading kernel (kaolin and nvdiffrast are not dependencies)."""
+`--by` keeps the reference's two values: 'kaolin' renders textured OBJ files -- one material or several, `map_Kd` images of any size
+next to plain `Kd` colours, the material of the face chosen per pixel -- and 'kaolin_per_vertex' OBJ files with `v x y z r g b`
+records; both run on this build's device rasteriser and shading kernels (kaolin and nvdiffrast are not dependencies)."""
 import argparse
 
 import torch
