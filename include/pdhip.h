@@ -658,6 +658,31 @@ int pdhip_concat_channels_f16(const void* a, int Ca, const void* b, int Cb, long
  * roofline.calibration.copy16_gbs next to torch's copy_: the ceiling the HBM-bound GroupNorm passes are judged against. */
 int pdhip_bench_copy16(const void* src, void* dst, long long bytes, int blocks, int unroll, void* stream);
 
+/* ---- geometry scores of a reconstruction (csrc/cloud_metrics.hip; models/POCO/eval/src/eval.py: distance_p2p, get_threshold_percentage, eval_pointcloud).
+ * pdhip_nearest_points: for every query the EXACT nearest target.  queries [Q,3], targets [M,3] f32 on the device; with the inputs widened to f64,
+ * dx = qx - tx (dy, dz alike) and d2 = (dx*dx + dy*dy) + dz*dz op by op, d2[q] is the minimum over all M targets and idx[q] the SMALLEST target index
+ * that attains it: both equal a brute-force f64 scan bit for bit, and two calls give equal bytes (no floating-point atomics).  counts (device [4]):
+ * queries certified by the LDS phase, queries finished by the ring scan from global memory (or, far from every target or in crowded cells, by the staged
+ * sweep of all targets behind it), grid cells per axis, 0.  The shipped path is the ring scan for every query (counts[0] == 0); the LDS phase, which stages the targets of a workgroup's cell box in chunks of pdhip_nearest_points_stage_chunk()
+ * targets and leaves the ring scan the queries it cannot certify, runs under pdhip_debug_set_nearest_path(1) and gives the same bytes.  ws: pdhip_nearest_points_workspace_bytes(Q, M) device
+ * bytes (0 for sizes the entry refuses).  PDHIP_E_ARG with the cause, and d2 / idx / counts untouched: a non-finite coordinate in either cloud,
+ * M < 1 or > 2^26, Q < 0 or > 2^26, a null pointer.  Q == 0: PDHIP_OK, counts zeroed.  The read of the two bounding boxes and of the two non-finite counts
+ * SYNCHRONISES the stream once (64 bytes); the grid is laid over the part of the targets' box that the queries' box meets.  (The size query is not called ..._ws_bytes: tests/test_ws_bytes_cpu.py fixes the set
+ * of queries with that suffix.) */
+size_t pdhip_nearest_points_workspace_bytes(int Q, int M);
+int pdhip_nearest_points_stage_chunk(void);
+int pdhip_nearest_points(const float* queries, int Q, const float* targets, int M, double* d2, int32_t* idx, int32_t* counts, void* ws, void* stream);
+int pdhip_debug_set_nearest_path(int path);   /* 0 (default): the one-thread-per-query ring scan from global memory for every query, the faster form at 10^5 x 10^5 points (profiles/geometry_metrics_bench.txt); 1: the LDS phase first, then the ring scan for the queries it could not certify (same results); returns the previous value */
+/* pdhip_cloud_metrics: the sums behind completeness / accuracy / Chamfer / normal consistency / F-score over the output of pdhip_nearest_points.
+ * d2 [Q] f64, idx [Q] i32 (into the M targets), normals_src [Q,3] and normals_tgt [M,3] f32 or NULL, thresholds [T] f64 ASCENDING on the device
+ * (not checked), T <= 4096.  sums (device [4]) = sum sqrt(d2), sum d2, sum |n_src . n_tgt[idx]| with both normals normalised in f64 (a zero or
+ * non-finite normal, or an idx outside [0, M), contributes 0; 0 when either normals pointer is NULL), 0.  The f64 sums run over a fixed tree (a
+ * function of Q alone): equal bits on repeats.  within (device [T] i64): within[j] = queries with sqrt(d2) <= thresholds[j], exact (integer histogram
+ * + prefix sum).  ws: pdhip_cloud_metrics_workspace_bytes(T) device bytes.  Q == 0: zeros. */
+size_t pdhip_cloud_metrics_workspace_bytes(int T);
+int pdhip_cloud_metrics(const double* d2, const int32_t* idx, int Q, const float* normals_src, const float* normals_tgt, int M,
+                        const double* thresholds, int T, double* sums, int64_t* within, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,12 @@ _SIGS = {
     'pdhip_simplify_mesh': (C.c_int, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
     'pdhip_sample_mesh_workspace_bytes': (sz, [i32, i32]),
     'pdhip_sample_mesh': (C.c_int, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'pdhip_nearest_points_workspace_bytes': (sz, [i32, i32]),
+    'pdhip_nearest_points_stage_chunk': (C.c_int, []),
+    'pdhip_nearest_points': (C.c_int, [vp, i32, vp, i32, vp, vp, vp, vp, vp]),
+    'pdhip_debug_set_nearest_path': (C.c_int, [i32]),
+    'pdhip_cloud_metrics_workspace_bytes': (sz, [i32]),
+    'pdhip_cloud_metrics': (C.c_int, [vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]),
     'pdhip_rescale_vertices': (C.c_int, [vp, i32, i32, vp, vp, vp, f64, vp]),
     'pdhip_optimize_color_ws_bytes': (sz, [i32, i32, i32]),
     'pdhip_optimize_color': (C.c_int, [vp, i32, vp, vp, i32, i32, vp, i32, vp, f64, i32, vp, vp, vp]),

@@ -1,0 +1,142 @@
+"""Geometry scores of a reconstruction on the device: models/POCO/eval/src/eval.py (MeshEvaluator.eval_pointcloud / eval_mesh,
+distance_p2p, get_threshold_percentage) with the reference's names, keys and argument order.
+
+  nearest_points(queries, targets)  -> (d2 [Q] float64, idx [Q] int32): the exact nearest target of every query (pdhip_nearest_points:
+                                       d2 = (dx dx + dy dy) + dz dz in f64 of the f32 coordinates, the smallest index on a tie)
+  eval_pointcloud(pointcloud, pointcloud_tgt, normals, normals_tgt, thresholds) -> the reference's dict
+  eval_mesh(vertices, faces, pointcloud_tgt, normals_tgt, n_points, seed, rand) -> the same over n_points samples of the mesh
+
+Completeness is target -> prediction, accuracy is prediction -> target, each the mean over the points of its source cloud; the
+normal entries are means of |n_src . n_tgt[nearest]| of the normalised normals; F = 2 P R / (P + R) with P / R the share of
+accuracy / completeness distances <= the threshold.  The kernels (csrc/cloud_metrics.hip) leave per direction three f64 sums and the
+integer counts per threshold; ONE device -> host copy per call brings them back, and the last handful of divisions are host Python.
+Coordinates are float32 on the device (the reference casts the sampled cloud to float32 as well, eval.py:73).
+
+Not built: `iou` (eval_mesh's fifth score needs ground-truth occupancy samples, points_iou / occ_tgt, which nothing in this project
+produces; the key is absent from the result), `remove_wall` (eval.py:48-69, a scene-dataset crop) and `distance_p2m` (unused by the
+reference).  CPU tensors raise PdhipError: there is no CPU path."""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import ptr, stream, check
+
+# eval.py:10-22, the values of an empty prediction (bounding box [-0.5, 0.5]^3)
+EMPTY_PCL_DICT = {'completeness': math.sqrt(3), 'accuracy': math.sqrt(3), 'completeness2': 3, 'accuracy2': 3, 'chamfer': 6}
+EMPTY_PCL_DICT_NORMALS = {'normals completeness': -1., 'normals accuracy': -1., 'normals': -1.}
+DEFAULT_THRESHOLDS = np.linspace(1. / 1000, 1, 1000)
+
+
+def _cloud(x, what, dev=None):
+    """[N,3] float32 contiguous on the GPU (numpy arrays follow `dev`, the device of the call's first GPU tensor)."""
+    if isinstance(x, np.ndarray) and dev is not None:
+        x = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise _lib.PdhipError(f"geometry_metrics: expected {what} on the GPU; pointdreamer_amd has no CPU path")
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"{what} must be [N, 3], got {tuple(x.shape)}")
+    return x.detach().to(torch.float32).contiguous()
+
+
+def nearest_points(queries, targets, return_counts=False):
+    """(d2 [Q] float64, idx [Q] int32) of queries [Q,3] against targets [M,3], both on the GPU (include/pdhip.h has the contract).
+    return_counts: also the int32 [4] tensor (certified by the LDS phase -- 0 on the shipped path --, finished by the ring scan, cells per axis, 0)."""
+    L = _lib.lib()
+    q, t = _cloud(queries, 'queries'), _cloud(targets, 'targets')
+    Q, M, dev = q.shape[0], t.shape[0], q.device
+    d2 = torch.empty((Q,), dtype=torch.float64, device=dev)
+    idx = torch.empty((Q,), dtype=torch.int32, device=dev)
+    counts = torch.zeros((4,), dtype=torch.int32, device=dev)
+    ws = torch.empty((max(int(L.pdhip_nearest_points_workspace_bytes(Q, M)), 8),), dtype=torch.uint8, device=dev)   # (0: the entry refuses the sizes)
+    opt = lambda x: ptr(x) if x.numel() else ptr(None, allow_none=True)
+    check(L.pdhip_nearest_points(opt(q), Q, opt(t), M, opt(d2), opt(idx), ptr(counts), ptr(ws), stream()), 'pdhip_nearest_points')
+    return (d2, idx, counts) if return_counts else (d2, idx)
+
+
+def cloud_sums(d2, idx, normals_src, normals_tgt, M, thresholds, out_sums, out_within):
+    """pdhip_cloud_metrics into out_sums [4] float64 / out_within [T] int64 (views of the caller's result buffer)."""
+    L = _lib.lib()
+    T = thresholds.shape[0]
+    ws = torch.empty((max(int(L.pdhip_cloud_metrics_workspace_bytes(T)), 8),), dtype=torch.uint8, device=d2.device)
+    check(L.pdhip_cloud_metrics(ptr(d2, torch.float64), ptr(idx, torch.int32), d2.shape[0], ptr(normals_src, torch.float32, allow_none=True),
+                                ptr(normals_tgt, torch.float32, allow_none=True), M, ptr(thresholds, torch.float64), T, ptr(out_sums),
+                                ptr(out_within), ptr(ws), stream()), 'pdhip_cloud_metrics')
+
+
+def eval_pointcloud(pointcloud, pointcloud_tgt, normals=None, normals_tgt=None, thresholds=DEFAULT_THRESHOLDS):
+    """eval.py:91-165 -> dict of python floats with the reference's twelve keys (the three normal entries are NaN without normals; an
+    empty prediction returns the reference's constants)."""
+    if pointcloud.shape[0] == 0:
+        out = EMPTY_PCL_DICT.copy()
+        if normals is not None and normals_tgt is not None:
+            out.update(EMPTY_PCL_DICT_NORMALS)
+        return out
+    first = pointcloud if torch.is_tensor(pointcloud) else pointcloud_tgt
+    dev = first.device if torch.is_tensor(first) and first.is_cuda else None
+    pred, tgt = _cloud(pointcloud, 'pointcloud', dev), _cloud(pointcloud_tgt, 'pointcloud_tgt', dev)
+    dev = pred.device
+    with_normals = normals is not None and normals_tgt is not None
+    n_pred = _cloud(normals, 'normals', dev) if with_normals else None
+    n_tgt = _cloud(normals_tgt, 'normals_tgt', dev) if with_normals else None
+    if with_normals and (n_pred.shape[0] != pred.shape[0] or n_tgt.shape[0] != tgt.shape[0]):
+        raise ValueError(f"normals {tuple(n_pred.shape)} / {tuple(n_tgt.shape)} do not match the clouds {tuple(pred.shape)} / {tuple(tgt.shape)}")
+    thr_host = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    if thr_host.shape[0] < 20:
+        raise ValueError("thresholds: the reference reads entries 9, 14 and 19")
+    thr = torch.from_numpy(thr_host).to(dev)
+    T = thr.shape[0]
+    # one result buffer of 8-byte words: [sums (4 f64) | within (T i64)] per direction, completeness first
+    buf = torch.zeros((2 * (4 + T),), dtype=torch.int64, device=dev)
+    for k, (src, dst, ns, nt) in enumerate(((tgt, pred, n_tgt, n_pred), (pred, tgt, n_pred, n_tgt))):
+        d2, idx = nearest_points(src, dst)
+        part = buf[k * (4 + T):(k + 1) * (4 + T)]
+        cloud_sums(d2, idx, ns, nt, dst.shape[0], thr, part[:4].view(torch.float64), part[4:])
+    host = buf.cpu()                                               # the one device -> host copy
+    res = []
+    for k, n in enumerate((tgt.shape[0], pred.shape[0])):
+        part = host[k * (4 + T):(k + 1) * (4 + T)]
+        sums = part[:4].view(torch.float64).tolist()
+        within = part[4:].numpy()
+        res.append((sums[0] / n, sums[1] / n, sums[2] / n if with_normals else float('nan'), within / float(n)))
+    (completeness, completeness2, completeness_normals, recall), (accuracy, accuracy2, accuracy_normals, precision) = res
+    with np.errstate(invalid='ignore', divide='ignore'):
+        F = 2 * precision * recall / (precision + recall)          # (0 / 0 is NaN, as in the reference)
+    return {
+        'completeness': completeness,
+        'accuracy': accuracy,
+        'normals completeness': completeness_normals,
+        'normals accuracy': accuracy_normals,
+        'normals': 0.5 * completeness_normals + 0.5 * accuracy_normals,
+        'completeness2': completeness2,
+        'accuracy2': accuracy2,
+        'chamfer-L2': 0.5 * (completeness2 + accuracy2),
+        'chamfer-L1': 0.5 * (completeness + accuracy),
+        'f-score': float(F[9]),        # threshold = 1.0%
+        'f-score-15': float(F[14]),    # threshold = 1.5%
+        'f-score-20': float(F[19]),    # threshold = 2.0%
+    }
+
+
+def sample_mesh_cloud(vertices, faces, n_points=100000, seed=0, rand=None):
+    """(coords [n,3], face normals [n,3]) of n_points area-uniform samples of the mesh (pdhip_sample_mesh through sample_points).  The
+    uniforms are `rand` [n,3] in [0,1), or torch.rand of a generator on the vertices' device seeded with `seed`."""
+    from .sample_colored_pc_from_mesh import sample_points
+    if not (torch.is_tensor(vertices) and vertices.is_cuda):
+        raise _lib.PdhipError("geometry_metrics: expected vertices on the GPU; pointdreamer_amd has no CPU path")
+    if rand is None:
+        gen = torch.Generator(device=vertices.device)
+        gen.manual_seed(int(seed))
+        rand = torch.rand((int(n_points), 3), device=vertices.device, generator=gen)
+    s = sample_points(vertices, faces, None, None, None, [{'Kd': np.zeros(3, np.float32)}], int(n_points), rand=rand)
+    return s['coords'], s['normals']
+
+
+def eval_mesh(vertices, faces, pointcloud_tgt, normals_tgt, n_points=100000, seed=0, rand=None, thresholds=DEFAULT_THRESHOLDS):
+    """eval.py:37-89 without `iou` and `remove_wall`: the scores of n_points samples of the mesh, their face normals as the prediction's
+    normals.  A mesh without vertices or faces scores as the empty cloud."""
+    if vertices.shape[0] == 0 or faces.shape[0] == 0:
+        return eval_pointcloud(np.empty((0, 3)), pointcloud_tgt, np.empty((0, 3)), normals_tgt, thresholds)
+    coords, nrm = sample_mesh_cloud(vertices, faces, n_points, seed, rand)
+    return eval_pointcloud(coords, pointcloud_tgt, nrm, normals_tgt, thresholds)
