@@ -683,6 +683,31 @@ size_t pdhip_cloud_metrics_workspace_bytes(int T);
 int pdhip_cloud_metrics(const double* d2, const int32_t* idx, int Q, const float* normals_src, const float* normals_tgt, int M,
                         const double* thresholds, int T, double* sums, int64_t* within, void* ws, void* stream);
 
+/* ---- point-in-mesh test and volumetric IoU (csrc/occupancy.hip; models/POCO/eval/src/utils/libmesh/inside_mesh.py: check_mesh_contains,
+ * eval/src/common.py: compute_iou).
+ * pdhip_mesh_contains: occ[q] = 1 when point q is contained in the mesh by the reference's definition.  vertices [Vn,3] f32, faces [F,3] i64, points
+ * [Q,3] f32 on the device, all widened to f64.  With R = resolution (the reference's hash_resolution, 512), over the vertices that a face REFERENCES:
+ * scale = (R - 1) / (max - min) per axis, translate = 0.5 - scale * min, x' = scale * x + translate (two roundings) for triangles and points alike.  A
+ * point outside [0, R]^3 is not contained.  A triangle (t1, t2, t3) is a hit for a point p when, with A = [t1 - t3, t2 - t3] in xy, detA = A00 A11 -
+ * A01 A10 != 0, y = p - t3, u = (A11 y0 - A01 y1) sign(detA), v = (-A10 y0 + A00 y1) sign(detA): 0 < u < |detA|, 0 < v < |detA|, 0 < u + v < |detA| (all
+ * strict).  For a hit, n = cross(t3 - t1, t2 - t1), alpha = n0 (t1x - px) + n1 (t1y - py), depth = t1z |n2| + alpha sign(n2); it counts above when depth
+ * >= pz |n2|, below when depth < pz |n2|, in neither when n2 == 0.  occ = (above odd) and (below odd).  The result equals the all-pairs evaluation of
+ * these formulas in f64, op by op, bit for bit; it depends on the order of neither the points nor the faces, and two calls give equal bytes (integer
+ * atomics only).  resolution enters the result through the rescale alone: the cull is a grid over the POINTS whose size follows Q.  counts (device
+ * [4]): contained, points whose two parities disagree (the reference's "contains1 != contains2" warning; an open mesh), points outside the box, 0.
+ * ws: pdhip_mesh_contains_workspace_bytes(Vn, F, Q, resolution) device bytes (0 for sizes the entry refuses).  PDHIP_E_ARG with the cause, and occ /
+ * counts untouched: a null pointer (named), Vn < 1, F < 1 or > 2^22, Q < 0 or > 2^26, resolution < 2 or > 4096, a face index outside [0, Vn), a
+ * non-finite referenced vertex or point, a mesh without extent on an axis (the reference divides by zero).  Q == 0: PDHIP_OK, counts zeroed, the mesh
+ * still validated.  The read of the bounding box and of the counts of bad inputs SYNCHRONISES the stream once (64 bytes).  (The size query is not called
+ * ..._ws_bytes: tests/test_ws_bytes_cpu.py fixes the set of queries with that suffix.) */
+size_t pdhip_mesh_contains_workspace_bytes(int Vn, int F, int Q, int resolution);
+int pdhip_mesh_contains(const float* vertices, int Vn, const int64_t* faces, int F, const float* points, int Q, int resolution, uint8_t* occ,
+                        int32_t* counts, void* ws, void* stream);
+int pdhip_debug_set_mesh_contains_slabs(int slabs);   /* 0 (default): the column slabs per triangle of the per-triangle pass (each a group of lanes of its own) follow F (64 for a mesh of few faces, whose triangles span many columns of the point grid; 1 from 16 384 faces on); 1 .. 64: that many (same results; profiles/occupancy_bench.txt); returns the previous value */
+/* pdhip_occupancy_iou: out (device [2] i64) = #{a >= 1 and b >= 1}, #{a >= 1 or b >= 1} over two [Q] u8 arrays on the device: integer counts only.
+ * Q == 0: zeros.  PDHIP_E_ARG: Q < 0 or > 2^26, a null pointer (named). */
+int pdhip_occupancy_iou(const uint8_t* a, const uint8_t* b, int Q, int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

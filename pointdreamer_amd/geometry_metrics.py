@@ -5,6 +5,9 @@ distance_p2p, get_threshold_percentage) with the reference's names, keys and arg
                                        d2 = (dx dx + dy dy) + dz dz in f64 of the f32 coordinates, the smallest index on a tie)
   eval_pointcloud(pointcloud, pointcloud_tgt, normals, normals_tgt, thresholds) -> the reference's dict
   eval_mesh(vertices, faces, pointcloud_tgt, normals_tgt, n_points, seed, rand) -> the same over n_points samples of the mesh
+  check_mesh_contains(vertices, faces, points, hash_resolution) -> bool [Q]: the reference's point-in-mesh test
+                                       (eval/src/utils/libmesh/inside_mesh.py; pdhip_mesh_contains, csrc/occupancy.hip)
+  compute_iou(occ1, occ2)           -> the volumetric intersection over union of two occupancy arrays (eval/src/common.py:6-33)
 
 Completeness is target -> prediction, accuracy is prediction -> target, each the mean over the points of its source cloud; the
 normal entries are means of |n_src . n_tgt[nearest]| of the normalised normals; F = 2 P R / (P + R) with P / R the share of
@@ -12,9 +15,12 @@ accuracy / completeness distances <= the threshold.  The kernels (csrc/cloud_met
 integer counts per threshold; ONE device -> host copy per call brings them back, and the last handful of divisions are host Python.
 Coordinates are float32 on the device (the reference casts the sampled cloud to float32 as well, eval.py:73).
 
-Not built: `iou` (eval_mesh's fifth score needs ground-truth occupancy samples, points_iou / occ_tgt, which nothing in this project
-produces; the key is absent from the result), `remove_wall` (eval.py:48-69, a scene-dataset crop) and `distance_p2m` (unused by the
-reference).  CPU tensors raise PdhipError: there is no CPU path."""
+`iou`, eval_mesh's fifth score (eval.py:83-87), is built from the two functions above: with `points_iou` and `occ_tgt` the prediction is tested
+for containment at the points and compared with the ground-truth occupancies, which sample_colored_pc_from_mesh.sample_occupancy_batch
+writes in the reference's .npz layout.  Without them the key is absent from the result.
+
+Not built: `remove_wall` (eval.py:48-69, a scene-dataset crop) and `distance_p2m` (unused by the reference).  CPU tensors raise
+PdhipError: there is no CPU path."""
 import math
 
 import numpy as np
@@ -133,10 +139,94 @@ def sample_mesh_cloud(vertices, faces, n_points=100000, seed=0, rand=None):
     return s['coords'], s['normals']
 
 
-def eval_mesh(vertices, faces, pointcloud_tgt, normals_tgt, n_points=100000, seed=0, rand=None, thresholds=DEFAULT_THRESHOLDS):
-    """eval.py:37-89 without `iou` and `remove_wall`: the scores of n_points samples of the mesh, their face normals as the prediction's
-    normals.  A mesh without vertices or faces scores as the empty cloud."""
+def check_mesh_contains(vertices, faces, points, hash_resolution=512, return_counts=False):
+    """inside_mesh.py:5-8 -> bool [Q] on the device: point q lies inside the mesh (include/pdhip.h has the definition; the result equals the
+    reference's bit for bit).  vertices [Vn,3] on the GPU, faces [F,3] (a numpy array follows the vertices), points [Q,3] on the GPU or a
+    numpy array, which follows the device of `vertices`.  return_counts: also the int32 [4] tensor (contained, points whose two ray
+    parities disagree -- the reference's "contains1 != contains2" warning --, points outside the mesh's box, 0)."""
+    L = _lib.lib()
+    v = _cloud(vertices, 'vertices')
+    dev = v.device
+    p = _cloud(points, 'points', dev)
+    if isinstance(faces, np.ndarray):
+        faces = torch.from_numpy(np.ascontiguousarray(faces)).to(dev)
+    if not (torch.is_tensor(faces) and faces.is_cuda):
+        raise _lib.PdhipError("geometry_metrics: expected faces on the GPU; pointdreamer_amd has no CPU path")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces must be [F, 3], got {tuple(faces.shape)}")
+    f = faces.detach().to(torch.int64).contiguous()
+    Vn, F, Q, R = v.shape[0], f.shape[0], p.shape[0], int(hash_resolution)
+    occ = torch.zeros((Q,), dtype=torch.uint8, device=dev)
+    counts = torch.zeros((4,), dtype=torch.int32, device=dev)
+    ws = torch.empty((max(int(L.pdhip_mesh_contains_workspace_bytes(Vn, F, Q, R)), 8),), dtype=torch.uint8, device=dev)   # (0: the entry refuses the sizes)
+    opt = lambda x: ptr(x) if x.numel() else ptr(None, allow_none=True)
+    check(L.pdhip_mesh_contains(opt(v), Vn, opt(f), F, opt(p), Q, R, opt(occ), ptr(counts), ptr(ws), stream()), 'pdhip_mesh_contains')
+    occ = occ.view(torch.bool)
+    return (occ, counts) if return_counts else occ
+
+
+def iou_from_counts(intersection, union):
+    """common.py:29-31 for one pair of arrays: the float32 quotient of the two counts (exact counts below 2^24); NaN for an empty union."""
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return float(np.float32(intersection) / np.float32(union))
+
+
+def _occupancy(x, what, dev):
+    """[Q] uint8 0 / 1 on the device: bool and integer arrays as they are (nonzero = occupied), floating ones binarised at >= 0.5."""
+    if isinstance(x, np.ndarray):
+        if dev is None:
+            raise _lib.PdhipError(f"geometry_metrics: expected {what} on the GPU; pointdreamer_amd has no CPU path")
+        x = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise _lib.PdhipError(f"geometry_metrics: expected {what} on the GPU; pointdreamer_amd has no CPU path")
+    x = x.detach().reshape(-1)
+    x = (x >= 0.5) if x.dtype != torch.bool else x
+    return x.to(torch.uint8).contiguous()
+
+
+def compute_iou(occ1, occ2):
+    """common.py:6-33 for one pair of occupancy arrays of equal size, binarised at >= 0.5 -> float.  The counts are taken on the device
+    (pdhip_occupancy_iou) and come back in ONE device -> host copy."""
+    L = _lib.lib()
+    first = occ1 if torch.is_tensor(occ1) else occ2
+    dev = first.device if torch.is_tensor(first) and first.is_cuda else None
+    a, b = _occupancy(occ1, 'occ1', dev), _occupancy(occ2, 'occ2', dev)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"occ1 has {a.shape[0]} entries, occ2 {b.shape[0]}")
+    out = torch.zeros((2,), dtype=torch.int64, device=a.device)
+    opt = lambda x: ptr(x) if x.numel() else ptr(None, allow_none=True)
+    check(L.pdhip_occupancy_iou(opt(a), opt(b), a.shape[0], ptr(out), stream()), 'pdhip_occupancy_iou')
+    inter, union = out.cpu().tolist()                              # the one device -> host copy
+    return iou_from_counts(inter, union)
+
+
+def _occ_tgt(occ_tgt, Q, dev):
+    """occ_tgt [Q] unpacked, or the .npz's np.packbits form (uint8 [ceil(Q / 8)], most significant bit first)."""
+    if isinstance(occ_tgt, np.ndarray):
+        occ_tgt = torch.from_numpy(np.ascontiguousarray(occ_tgt)).to(dev)
+    n = occ_tgt.numel()
+    if n != Q and occ_tgt.dtype == torch.uint8 and n == (Q + 7) // 8:
+        shifts = torch.arange(7, -1, -1, dtype=torch.uint8, device=occ_tgt.device)
+        occ_tgt = ((occ_tgt.reshape(-1, 1) >> shifts) & 1).reshape(-1)[:Q]
+    if occ_tgt.numel() != Q:
+        raise ValueError(f"occ_tgt has {n} entries for {Q} points (neither unpacked nor np.packbits of them)")
+    return occ_tgt
+
+
+def eval_mesh(vertices, faces, pointcloud_tgt, normals_tgt, n_points=100000, seed=0, rand=None, thresholds=DEFAULT_THRESHOLDS,
+              points_iou=None, occ_tgt=None):
+    """eval.py:37-89 without `remove_wall`: the scores of n_points samples of the mesh, their face normals as the prediction's normals.  A mesh
+    without vertices or faces scores as the empty cloud.  With points_iou [Q,3] and occ_tgt (their ground-truth occupancies, [Q] or the
+    np.packbits form of the .npz) the result gains 'iou' (0. for an empty mesh, eval.py:86-87); without them the key is absent."""
+    with_iou = points_iou is not None and occ_tgt is not None
     if vertices.shape[0] == 0 or faces.shape[0] == 0:
-        return eval_pointcloud(np.empty((0, 3)), pointcloud_tgt, np.empty((0, 3)), normals_tgt, thresholds)
+        out = eval_pointcloud(np.empty((0, 3)), pointcloud_tgt, np.empty((0, 3)), normals_tgt, thresholds)
+        if with_iou:
+            out['iou'] = 0.
+        return out
     coords, nrm = sample_mesh_cloud(vertices, faces, n_points, seed, rand)
-    return eval_pointcloud(coords, pointcloud_tgt, nrm, normals_tgt, thresholds)
+    out = eval_pointcloud(coords, pointcloud_tgt, nrm, normals_tgt, thresholds)
+    if with_iou:
+        occ = check_mesh_contains(vertices, faces, points_iou)
+        out['iou'] = compute_iou(occ, _occ_tgt(occ_tgt, occ.shape[0], occ.device))
+    return out

@@ -6,7 +6,9 @@ models/POCO/eval/src/eval.py, in the layout of this project's other tools):
 Every <cls_id>/<shape_name>/models/model_normalized.obj under the prediction root is read with io_utils.load_obj_mesh, sampled with
 `--n_points` points (seeded by `--seed`) and scored against <gt_root>/<cls_id>/<shape_name>/coords.npy + normals.npy, the files
 sample_colored_pc_from_mesh writes.  One line per shape, then the mean over the shapes; the result also goes to
-`<parent of pred root>/<time>_geometry_eval_result.txt`.  A shape without ground truth is a FileNotFoundError that names it."""
+`<parent of pred root>/<time>_geometry_eval_result.txt`.  A shape without ground truth is a FileNotFoundError that names it.
+With `--points_root_path <data_root>/point` every shape that has <cls_id>/<shape_name>.npz there (points + packed occupancies, written by
+`sample_colored_pc_from_mesh --occupancy`) is also scored by the volumetric IoU: an `iou` column, its mean over the shapes that have one."""
 import argparse
 import os
 import time
@@ -21,14 +23,17 @@ KEYS = ('chamfer-L1', 'chamfer-L2', 'completeness', 'accuracy', 'normals', 'f-sc
 MESH = os.path.join('models', 'model_normalized.obj')
 
 
-def eval(pred_root_path, gt_root_path, n_points=100000, seed=0, device=None):
-    """Returns dict(per_shape={name: the twelve scores}, mean={key: mean over the shapes}, sample_num, result_file)."""
+def eval(pred_root_path, gt_root_path, n_points=100000, seed=0, device=None, points_root_path=None):
+    """Returns dict(per_shape={name: the twelve scores}, mean={key: mean over the shapes}, sample_num, result_file).  points_root_path
+    (<data_root>/point, what sample_colored_pc_from_mesh --occupancy writes): a shape with <cls_id>/<shape_name>.npz there is also scored
+    by `iou`, and the mean of that column runs over those shapes (NaN when there is none)."""
     device = device if device is not None else torch.device('cuda')
     names = [n for n in shape_names(pred_root_path) if os.path.exists(os.path.join(pred_root_path, n, MESH))]
     if not names:
         raise FileNotFoundError(f'no <cls_id>/<shape_name>/{MESH} under {pred_root_path}')
     per_shape = {}
-    print('shape\t' + '\t'.join(KEYS))
+    shown = KEYS + ('iou',) if points_root_path is not None else KEYS
+    print('shape\t' + '\t'.join(shown))
     for name in names:
         gt = [os.path.join(gt_root_path, name, f) for f in ('coords.npy', 'normals.npy')]
         for p in gt:
@@ -36,18 +41,28 @@ def eval(pred_root_path, gt_root_path, n_points=100000, seed=0, device=None):
                 raise FileNotFoundError(f'{name}: no ground truth {p}')
         vertices, faces = io_utils.load_obj_mesh(os.path.join(pred_root_path, name, MESH))
         coords, normals = (torch.from_numpy(np.load(p).astype(np.float32)).to(device) for p in gt)
+        occ_file = os.path.join(points_root_path, name + '.npz') if points_root_path is not None else None
+        iou_args = {}
+        if occ_file is not None and os.path.exists(occ_file):
+            with np.load(occ_file) as z:
+                iou_args = dict(points_iou=z['points'].astype(np.float32), occ_tgt=z['occupancies'])
         r = geometry_metrics.eval_mesh(torch.from_numpy(vertices).to(device), torch.from_numpy(faces).to(device), coords, normals,
-                                       n_points=n_points, seed=seed)
+                                       n_points=n_points, seed=seed, **iou_args)
         per_shape[name] = r
-        print(name + '\t' + '\t'.join(repr(float(r[k])) for k in KEYS))
+        print(name + '\t' + '\t'.join(repr(float(r.get(k, float('nan')))) for k in shown))
     keys = list(next(iter(per_shape.values())))
-    mean = {k: float(np.mean([float(r[k]) for r in per_shape.values()])) for k in keys}
+    if points_root_path is not None and 'iou' not in keys:
+        keys.append('iou')
+    have = lambda k: [float(r[k]) for r in per_shape.values() if k in r]
+    mean = {k: float(np.mean(have(k))) if have(k) else float('nan') for k in keys}
     print('-----------------------------------------')
     print('pred_root_path', pred_root_path)
     print('gt_root_path', gt_root_path)
+    if points_root_path is not None:
+        print('points_root_path', points_root_path, 'shapes with iou', len(have('iou')))
     print('sample num', len(names))
-    print('\t'.join(KEYS))
-    print('\t'.join(repr(mean[k]) for k in KEYS))
+    print('\t'.join(shown))
+    print('\t'.join(repr(mean[k]) for k in shown))
     print('-----------------------------------------')
     now = time.strftime("%Y_%m_%d %H.%M.%S\n", time.localtime())
     result_file = os.path.join(os.path.dirname(os.path.abspath(pred_root_path).rstrip(os.sep)), f'{now.strip()}_geometry_eval_result.txt')
@@ -63,8 +78,10 @@ def main(argv=None):
     p.add_argument("--gt_root_path", type=str, required=True, help="<data_root>/pc_kaolin: <cls_id>/<shape>/coords.npy + normals.npy")
     p.add_argument("--n_points", type=int, default=100000)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--points_root_path", type=str, default=None,
+                   help="<data_root>/point: <cls_id>/<shape>.npz with points + occupancies (sample_colored_pc_from_mesh --occupancy) -> the iou column")
     args = p.parse_args(argv)
-    return eval(args.pred_root_path, args.gt_root_path, args.n_points, args.seed)
+    return eval(args.pred_root_path, args.gt_root_path, args.n_points, args.seed, points_root_path=args.points_root_path)
 
 
 if __name__ == '__main__':

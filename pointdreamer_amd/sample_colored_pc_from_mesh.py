@@ -12,6 +12,10 @@ Deviations from the reference, all deliberate:
   * the caller's vertices are never modified (the reference normalises them in place).
 
   python -m pointdreamer_amd.sample_colored_pc_from_mesh --rootpath ROOT [--cls_id ...] [--point_num 30000] [--seed 0] [--ply]
+  python -m pointdreamer_amd.sample_colored_pc_from_mesh --rootpath ROOT [--cls_id ...] --occupancy [N] [--padding 0.1] [--seed 0]
+
+The second form (sample_occupancy_batch) writes no clouds: it tests N uniform points against every mesh on the device and stores them
+with their occupancies as <ROOT>/point/<cls_id>/<name>.npz, the ground truth of the volumetric IoU (geometry_metrics.eval_mesh).
 """
 import argparse
 import logging
@@ -355,6 +359,55 @@ def sample_omniobject3d_batch(root_path='datasets/omniobject3d', cls_id='omniobj
     return _sample_batch(root_path, [cls_id], point_num, seed, ply, device)
 
 
+def sample_occupancy_batch(root_path, cls_ids=None, n_points=100000, padding=0.1, seed=0, device=None):
+    """Every <root_path>/meshes/<cls>/<name> -> <root_path>/point/<cls>/<name>.npz with `points` (float32 [n_points,3]) and `occupancies`
+    (np.packbits of the [n_points] inside / outside flags): the two keys the reference's loader reads (models/POCO/datasets/shapenet.py:200-203)
+    as the ground truth of eval_mesh's `iou`.  The mesh is normalised as the point sampler normalises it (camera_utils._normalized); the
+    points are uniform in [-(1 + padding) / 2, (1 + padding) / 2]^3 -- the box is this project's choice, the convention of Occupancy
+    Networks, not something the reference fixes: it reads such files and does not write them --, drawn as float32 from the generator
+    seeded by (seed, crc32 of '<cls>/<name>') that _sample_batch uses, and tested as the float32 values that are stored
+    (geometry_metrics.check_mesh_contains, the reference's check_mesh_contains on the device).  A shape whose file exists is skipped; a
+    shape that fails is logged with its traceback and the run goes on.  Per shape the number of points whose two ray parities disagree is
+    logged: a mesh that is not closed gets the reference's conservative answer there (not contained), which is the reference's
+    behaviour and not an error.  Returns the number of files written."""
+    from .camera_utils import _normalized
+    from .geometry_metrics import check_mesh_contains
+    dev = _lib.resolve_device(device if device is not None else 'cuda')
+    log = logging.getLogger('pointdreamer_amd.sample_pc')
+    save_root = os.path.join(root_path, 'point')
+    mesh_root = os.path.join(root_path, 'meshes')
+    if cls_ids is None:
+        cls_ids = [c for c in sorted(os.listdir(mesh_root)) if os.path.isdir(os.path.join(mesh_root, c))]
+    half = (1.0 + float(padding)) / 2.0
+    done = 0
+    for cls_id in cls_ids:
+        names = sorted(n for n in os.listdir(os.path.join(mesh_root, cls_id)) if os.path.isdir(os.path.join(mesh_root, cls_id, n)))
+        for i, name in enumerate(names):
+            out_file = os.path.join(save_root, cls_id, name + '.npz')
+            if os.path.exists(out_file):
+                log.info(f'skip exist {out_file}')
+                continue
+            log.info(f'{i}/{len(names)}:{cls_id}/{name}')
+            try:
+                gen = torch.Generator().manual_seed((int(seed) << 32) ^ zlib.crc32(f'{cls_id}/{name}'.encode()))
+                mesh = get_other_mesh_data(root_path, name, cls_id=cls_id).data
+                vertices = _normalized(_on(mesh.vertices, dev, torch.float32)).contiguous()
+                points = ((torch.rand((int(n_points), 3), generator=gen) * 2.0 - 1.0) * half).to(torch.float32).contiguous()
+                occ, counts = check_mesh_contains(vertices, _on(mesh.faces, dev, torch.int64), points.to(dev), return_counts=True)
+                contained, disagree, outside, _ = counts.cpu().tolist()
+                log.info(f'{cls_id}/{name}: {contained} of {int(n_points)} points inside, {outside} outside the box of the mesh, '
+                         f'{disagree} with disagreeing parities (taken as outside)')
+                os.makedirs(os.path.dirname(out_file), exist_ok=True)
+                np.savez(out_file, points=points.numpy(), occupancies=np.packbits(occ.cpu().numpy()))
+                done += 1
+            except KeyboardInterrupt:
+                raise
+            except Exception:                      # noqa: BLE001 -- as _sample_batch: log the shape and go on
+                log.error(f'{i},{cls_id}/{name}')
+                log.error(traceback.format_exc())
+    return done
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="Sample coloured point clouds from <rootpath>/meshes/<cls_id>/<name> into <rootpath>/pc_kaolin")
     p.add_argument('--rootpath', required=True)
@@ -362,8 +415,16 @@ def main(argv=None):
     p.add_argument('--point_num', type=int, default=30000)
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--ply', action='store_true', help="also write <cls_id>/<name>.ply (xyz + rgb), the input of demo --pc_file")
+    p.add_argument('--occupancy', type=int, nargs='?', const=100000, default=None, metavar='N',
+                   help="instead of the clouds, write <rootpath>/point/<cls_id>/<name>.npz: N (default 100000) points in the padded unit box "
+                        "and their inside / outside flags, the ground truth of run_geometry_evaluation's iou")
+    p.add_argument('--padding', type=float, default=0.1, help="with --occupancy: the points fill [-(1 + padding) / 2, (1 + padding) / 2]^3")
     args = p.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format='%(asctime)s %(levelname)s %(message)s')
+    if args.occupancy is not None:
+        done = sample_occupancy_batch(args.rootpath, args.cls_id or None, args.occupancy, args.padding, args.seed)
+        print(f'wrote the occupancies of {done} shape(s) into {os.path.join(args.rootpath, "point")}')
+        return 0
     done = _sample_batch(args.rootpath, args.cls_id or None, args.point_num, args.seed, args.ply)
     print(f'sampled {done} shape(s) into {os.path.join(args.rootpath, "pc_kaolin")}')
     return 0
