@@ -5,7 +5,7 @@
 //     a. bounding boxes and a finiteness test of both clouds (integer atomics on order-preserving keys; one small read that synchronises the
 //        stream); a uniform grid of C^3 cells, C ~ sqrt(M / 8): a few targets per occupied cell of a surface, over the cube of the part of the
 //        targets' box that the queries' box meets.  Points outside the grid are clamped into its boundary cells;
-//     b. targets sorted by cell key (radix_sort.h), cstart[c] = first sorted target whose key is >= c, for c = 0 .. C^3 (a binary search per cell): the targets of the
+//     b. targets sorted by cell key (cell_list.h, as is a.'s box kernel), cstart[c] = first sorted target whose key is >= c, for c = 0 .. C^3 (a binary search per cell): the targets of the
 //        cells x0 .. x1 of a grid row are ONE run of the sorted array; queries sorted by the key of the cell they fall (or are clamped) into;
 //     c. phase 1 (k_cm_stage_scan): a workgroup owns CM_T consecutive sorted queries, takes the bounding cell box of their cells plus one ring,
 //        stages the targets of that box into LDS as (x, y, z, index) in chunks of CM_CHUNK, and every thread scans each chunk for its own query
@@ -28,10 +28,9 @@
 //     and within[j] = #{sqrt(d2) <= thresholds[j]}: per-query bin by binary search, an integer histogram in LDS, integer global atomics, prefix sum.
 // No floating-point atomics: two calls give equal bytes.  Compiled with -ffp-contract=off.  Every kernel keeps zero scratch.
 #include "common.h"
-#include "radix_sort.h"
+#include "cell_list.h"
 #include <math.h>
 #include <limits.h>
-#include <string.h>
 #include <algorithm>
 using namespace pdhip;
 
@@ -50,7 +49,7 @@ constexpr int CM_FAR_SLABS = 16;              // ... and the far scan cuts the t
 constexpr int CM_NB = 256;                    // workgroups of the reduction (== CM_T: one finalize workgroup reads them all)
 constexpr int CM_TMAX = 4096;                 // thresholds
 constexpr int CM_NMAX = 1 << 26;
-enum { BOX_MIN = 0, BOX_MAX = 3, BOX_BAD = 6, BOX_WORDS = 8, MISC_UNC = 2 * BOX_WORDS, MISC_FAR = MISC_UNC + 1, MISC_WORDS = 32 };
+enum { MISC_UNC = 2 * BOX_WORDS, MISC_FAR = MISC_UNC + 1, MISC_WORDS = 32 };      // behind the two boxes (cell_list.h)
 
 struct CmGrid {
     double ox, oy, oz, cs;
@@ -76,67 +75,16 @@ __device__ __forceinline__ double cm_face_bound(double q, double o, double cs, i
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// a. box[0..2] / box[3..5] = min / max of the finite coordinates as order-preserving keys, box[6] = points with a non-finite coordinate
-__global__ __launch_bounds__(CM_T) void k_cm_box(const float* __restrict__ P, int N, uint32_t* __restrict__ box) {
-    __shared__ uint32_t sh[BOX_WORDS];
-    const int t = threadIdx.x;
-    if (t < BOX_WORDS) sh[t] = t < BOX_MAX ? 0xffffffffu : 0u;
-    __syncthreads();
-    uint32_t mn0 = 0xffffffffu, mn1 = 0xffffffffu, mn2 = 0xffffffffu, mx0 = 0u, mx1 = 0u, mx2 = 0u, bad = 0u;
-    for (long long i = (long long)blockIdx.x * CM_T + t; i < N; i += (long long)gridDim.x * CM_T) {
-        const float x = P[3 * i], y = P[3 * i + 1], z = P[3 * i + 2];
-        if (!(fabsf(x) <= 3.4028234e38f) || !(fabsf(y) <= 3.4028234e38f) || !(fabsf(z) <= 3.4028234e38f)) { ++bad; continue; }
-        const uint32_t a = f2ord(x), b = f2ord(y), c = f2ord(z);
-        mn0 = min(mn0, a); mn1 = min(mn1, b); mn2 = min(mn2, c);
-        mx0 = max(mx0, a); mx1 = max(mx1, b); mx2 = max(mx2, c);
+// b. the key of the cell that point i of P falls (or is clamped) into
+struct CmKey {
+    const float* P;
+    CmGrid g;
+    __device__ uint64_t operator()(int i) const {
+        const int cx = cm_cell((double)P[3 * (size_t)i], g.ox, g.cs, g.C), cy = cm_cell((double)P[3 * (size_t)i + 1], g.oy, g.cs, g.C),
+                  cz = cm_cell((double)P[3 * (size_t)i + 2], g.oz, g.cs, g.C);
+        return (uint64_t)((cz * g.C + cy) * g.C + cx);
     }
-    for (int off = 32; off > 0; off >>= 1) {                       // one LDS atomic per wave and word, not one per thread
-        mn0 = min(mn0, (uint32_t)__shfl_xor((int)mn0, off)); mn1 = min(mn1, (uint32_t)__shfl_xor((int)mn1, off));
-        mn2 = min(mn2, (uint32_t)__shfl_xor((int)mn2, off)); mx0 = max(mx0, (uint32_t)__shfl_xor((int)mx0, off));
-        mx1 = max(mx1, (uint32_t)__shfl_xor((int)mx1, off)); mx2 = max(mx2, (uint32_t)__shfl_xor((int)mx2, off));
-        bad += (uint32_t)__shfl_xor((int)bad, off);
-    }
-    if ((t & 63) == 0) {
-        atomicMin(&sh[0], mn0); atomicMin(&sh[1], mn1); atomicMin(&sh[2], mn2);
-        atomicMax(&sh[3], mx0); atomicMax(&sh[4], mx1); atomicMax(&sh[5], mx2);
-        if (bad) atomicAdd(&sh[BOX_BAD], bad);
-    }
-    __syncthreads();
-    if (t < BOX_MAX) atomicMin(&box[t], sh[t]);
-    else if (t < BOX_BAD) atomicMax(&box[t], sh[t]);
-    else if (t == BOX_BAD && sh[t]) atomicAdd(&box[t], sh[t]);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// b. cell list
-__global__ void k_cm_keys(const float* __restrict__ P, int N, CmGrid g, uint64_t* __restrict__ key, int* __restrict__ val) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    const int cx = cm_cell((double)P[3 * (size_t)i], g.ox, g.cs, g.C), cy = cm_cell((double)P[3 * (size_t)i + 1], g.oy, g.cs, g.C),
-              cz = cm_cell((double)P[3 * (size_t)i + 2], g.oz, g.cs, g.C);
-    key[i] = (uint64_t)((cz * g.C + cy) * g.C + cx);
-    val[i] = i;
-}
-
-// sorted points as (x, y, z, index)
-__global__ void k_cm_gather(const int* __restrict__ val, const float* __restrict__ P, int N, float4* __restrict__ sp) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= N) return;
-    const int i = val[p];
-    sp[p] = make_float4(P[3 * (size_t)i], P[3 * (size_t)i + 1], P[3 * (size_t)i + 2], __int_as_float(i));
-}
-
-// cstart[c] = first sorted position whose key is >= c, c = 0 .. nc (one thread per cell: a binary search in the sorted keys)
-__global__ void k_cm_cell_starts(const uint64_t* __restrict__ key, int N, int* __restrict__ cstart, int nc) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c > nc) return;
-    int lo = 0, hi = N;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (key[mid] < (uint64_t)c) lo = mid + 1; else hi = mid;
-    }
-    cstart[c] = lo;
-}
+};
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // c. phase 1
@@ -257,12 +205,11 @@ __global__ __launch_bounds__(CM_P2_T) void k_cm_ring_scan(const float4* __restri
     double bd = 1.0e300;
     int bi = INT_MAX, work = 0;
     for (int r = 1;; r *= 2) {
-        const int x0 = max(cx - r, 0), x1 = min(cx + r, C - 1), y0 = max(cy - r, 0), y1 = min(cy + r, C - 1), z0 = max(cz - r, 0),
-                  z1 = min(cz + r, C - 1);
-        for (int z = z0; z <= z1; ++z)
-            for (int y = y0; y <= y1; ++y) {
+        const CellCube q = cube_around(cx, cy, cz, r, C);
+        for (int z = q.z0; z <= q.z1; ++z)
+            for (int y = q.y0; y <= q.y1; ++y) {
                 const int base = (z * C + y) * C;
-                const int b = cstart[base + x0], e = cstart[base + x1 + 1];
+                const int b = cstart[base + q.x0], e = cstart[base + q.x1 + 1];
                 work += e - b;
                 if (work > CM_RING_WORK) {                         // crowded cells: the far scan's staged sweep is the cheaper way
                     far_list[atomicAdd(far_n, 1)] = sp;
@@ -276,10 +223,9 @@ __global__ __launch_bounds__(CM_P2_T) void k_cm_ring_scan(const float4* __restri
                     if (d < bd || (d == bd && k < bi)) { bd = d; bi = k; }
                 }
             }
-        const bool all = x0 == 0 && y0 == 0 && z0 == 0 && x1 == C - 1 && y1 == C - 1 && z1 == C - 1;
-        const double b = fmin(fmin(cm_face_bound(qx, g.ox, g.cs, C, x0, x1), cm_face_bound(qy, g.oy, g.cs, C, y0, y1)),
-                              cm_face_bound(qz, g.oz, g.cs, C, z0, z1));
-        if (all || (bi != INT_MAX && b > 0.0 && bd <= b * b)) break;
+        const double b = fmin(fmin(cm_face_bound(qx, g.ox, g.cs, C, q.x0, q.x1), cm_face_bound(qy, g.oy, g.cs, C, q.y0, q.y1)),
+                              cm_face_bound(qz, g.oz, g.cs, C, q.z0, q.z1));
+        if (q.covers(C) || (bi != INT_MAX && b > 0.0 && bd <= b * b)) break;
         if (r >= CM_RING_MAX) {                                    // far from every target: a thread of its own would scan most of the grid
             far_list[atomicAdd(far_n, 1)] = sp;
             return;
@@ -453,13 +399,6 @@ static size_t carve_metrics(MetricWs& w, void* base, int T) {
     return c.off + 256;
 }
 
-static double host_ord2f(uint32_t u) {
-    const uint32_t b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    float f;
-    memcpy(&f, &b, sizeof(f));
-    return (double)f;
-}
-
 }  // namespace
 
 // tuning / test hook: 0 = the ring scan for every query (shipped: the faster form at 10^5 x 10^5 points, profiles/geometry_metrics_bench.txt);
@@ -487,21 +426,20 @@ extern "C" int pdhip_nearest_points(const float* queries, int Q, const float* ta
     NearWs w;
     carve_nearest(w, ws, Q, M);
     // a. the targets' box, finiteness of both clouds
-    PD_HIP(hipMemsetAsync(w.misc, 0, MISC_WORDS * sizeof(uint32_t), s));
-    PD_HIP(hipMemsetAsync(w.misc, 0xff, 3 * sizeof(uint32_t), s));
-    PD_HIP(hipMemsetAsync(w.misc + BOX_WORDS, 0xff, 3 * sizeof(uint32_t), s));
-    k_cm_box<<<std::min(cdiv(M, CM_T), 1024), CM_T, 0, s>>>(targets, M, w.misc);
-    k_cm_box<<<std::min(cdiv(Q, CM_T), 1024), CM_T, 0, s>>>(queries, Q, w.misc + BOX_WORDS);
+    int rc = clear_boxes(w.misc, 2, MISC_WORDS, s);
+    if (rc) return rc;
+    k_point_box<<<std::min(cdiv(M, CL_T), 1024), CL_T, 0, s>>>(targets, M, nullptr, M, 1, w.misc);
+    k_point_box<<<std::min(cdiv(Q, CL_T), 1024), CL_T, 0, s>>>(queries, Q, nullptr, Q, 1, w.misc + BOX_WORDS);
     PD_LAUNCH_CHECK();
-    uint32_t h[2 * BOX_WORDS];
-    PD_HIP(hipMemcpyAsync(h, w.misc, sizeof(h), hipMemcpyDeviceToHost, s));
-    PD_HIP(hipStreamSynchronize(s));
-    PD_REQUIRE(h[BOX_BAD] == 0, "pdhip_nearest_points: %u target(s) with a non-finite coordinate", h[BOX_BAD]);
-    PD_REQUIRE(h[BOX_WORDS + BOX_BAD] == 0, "pdhip_nearest_points: %u query point(s) with a non-finite coordinate", h[BOX_WORDS + BOX_BAD]);
+    HostBox box[2];                                                // targets, queries
+    rc = read_boxes(w.misc, box, s);
+    if (rc) return rc;
+    PD_REQUIRE(box[0].bad == 0, "pdhip_nearest_points: %u target(s) with a non-finite coordinate", box[0].bad);
+    PD_REQUIRE(box[1].bad == 0, "pdhip_nearest_points: %u query point(s) with a non-finite coordinate", box[1].bad);
     double mn[3], ext = 0.0;
     for (int a = 0; a < 3; ++a) {
-        mn[a] = host_ord2f(h[BOX_MIN + a]);
-        ext = std::max(ext, host_ord2f(h[BOX_MAX + a]) - mn[a]);
+        mn[a] = box[0].mn[a];
+        ext = std::max(ext, box[0].mx[a] - mn[a]);
     }
     // the grid covers the part of the targets' box that the queries' box meets (the whole box if they do not meet): a few outliers among the targets do
     // not coarsen the cells where the queries are.  Points outside the grid are clamped into its boundary cells, which the certificate allows: it
@@ -509,8 +447,8 @@ extern "C" int pdhip_nearest_points(const float* queries, int Q, const float* ta
     double lo[3], hi[3];
     bool meet = true;
     for (int a = 0; a < 3; ++a) {
-        lo[a] = std::max(mn[a], host_ord2f(h[BOX_WORDS + BOX_MIN + a]));
-        hi[a] = std::min(host_ord2f(h[BOX_MAX + a]), host_ord2f(h[BOX_WORDS + BOX_MAX + a]));
+        lo[a] = std::max(mn[a], box[1].mn[a]);
+        hi[a] = std::min(box[0].mx[a], box[1].mx[a]);
         meet = meet && lo[a] <= hi[a];
     }
     if (meet) {
@@ -526,13 +464,10 @@ extern "C" int pdhip_nearest_points(const float* queries, int Q, const float* ta
     g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2];
     const int nc = g.C * g.C * g.C;
     // b. both clouds in cell order
-    k_cm_keys<<<cdiv(M, CM_T), CM_T, 0, s>>>(targets, M, g, w.sb.k[0], w.sb.v[0]);
-    int cur = radix_sort(w.sb, M, bits_for((unsigned long long)nc), s);
-    k_cm_gather<<<cdiv(M, CM_T), CM_T, 0, s>>>(w.sb.v[cur], targets, M, w.st);
-    k_cm_cell_starts<<<cdiv(nc + 1, CM_T), CM_T, 0, s>>>(w.sb.k[cur], M, w.cstart, nc);
-    k_cm_keys<<<cdiv(Q, CM_T), CM_T, 0, s>>>(queries, Q, g, w.sb.k[0], w.sb.v[0]);
-    cur = radix_sort(w.sb, Q, bits_for((unsigned long long)nc), s);
-    k_cm_gather<<<cdiv(Q, CM_T), CM_T, 0, s>>>(w.sb.v[cur], queries, Q, w.sq);
+    int cur = sort_by_cell(w.sb, M, CmKey{targets, g}, (unsigned long long)nc, w.cstart, s);
+    k_gather_xyzi<<<cdiv(M, CL_T), CL_T, 0, s>>>(w.sb.v[cur], targets, M, w.st);
+    cur = sort_by_cell(w.sb, Q, CmKey{queries, g}, (unsigned long long)nc, nullptr, s);      // (the queries need the order only)
+    k_gather_xyzi<<<cdiv(Q, CL_T), CL_T, 0, s>>>(w.sb.v[cur], queries, Q, w.sq);
     PD_LAUNCH_CHECK();
     // c, d.
     int* unc_n = reinterpret_cast<int*>(w.misc + MISC_UNC);

@@ -2,11 +2,11 @@
 // the two counts behind the volumetric IoU (eval/src/common.py: compute_iou).
 //
 //   pdhip_mesh_contains
-//     a. k_occ_box: faces checked against [0, Vn), the bounding box of the REFERENCED vertices (integer atomics on order-preserving keys), the
+//     a. k_point_box (cell_list.h): faces checked against [0, Vn), the bounding box of the REFERENCED vertices (integer atomics on order-preserving keys), the
 //        finiteness of those vertices and of the points; one small read that synchronises the stream.  On the host, in f64 as numpy does:
 //        scale = (R - 1) / (max - min), translate = 0.5 - scale * min.  A mesh without extent on an axis is refused (the reference divides by zero);
 //     b. the POINTS are binned, not the triangles: x' = scale * x + translate (two roundings), a point outside [0, R]^3 takes the key G * G and sorts
-//        behind every cell; the others are sorted (radix_sort.h) by the xy cell key cx * G + cy, y fastest, of a G x G grid with G ~ sqrt(Q / 4).  The
+//        behind every cell; the others are sorted (cell_list.h) by the xy cell key cx * G + cy, y fastest, of a G x G grid with G ~ sqrt(Q / 4).  The
 //        points of the cells y0 .. y1 of one x column are then ONE run of the sorted array (cstart[c] = first sorted point whose key is >= c);
 //     c. k_occ_tri: one group of lanes per (triangle, column slab): a wave, or 16 lanes from 32 768 faces on.  The group rescales its triangle, forms
 //        the constants of check_triangles and of compute_intersection_depth once, takes the cell box of the triangle's xy extent and walks the columns
@@ -34,16 +34,15 @@
 //   * A wave per triangle took k_occ_tri 98 us against 200 000 faces (a triangle there meets one or two columns of a handful of points: most lanes
 //     idle); 16 lanes per triangle 34 us, hence the narrower group from 32 768 faces on.
 //   * Atomics on one address are served one after the other.  k_occ_finish with one global atomicAdd per wave and count: 17.5 us; with an LDS
-//     reduction per workgroup and at most 256 workgroups: 5.5 us.  k_occ_box, which sent the box of the points as well (nobody reads it) from up to
+//     reduction per workgroup and at most 256 workgroups: 5.5 us.  The box kernel, which sent the box of the points as well (nobody reads it) from up to
 //     1 024 workgroups: 2 x 8.7 us; now 2 x 4.2 us.
 //   * What is left is the sort of the points (53 of about 105 us of kernels).  Binning the triangles instead (the reference's layout) needs a pair
 //     list whose size only the data knows; binning the points needs none.  A precomputed per-triangle table was not built: the constants are
 //     uniform over the group and cost it a few dozen f64 instructions.
 // No floating-point atomics: two calls give equal bytes.  Compiled with -ffp-contract=off.  Every kernel keeps zero scratch.
 #include "common.h"
-#include "radix_sort.h"
+#include "cell_list.h"
 #include <math.h>
-#include <string.h>
 #include <algorithm>
 using namespace pdhip;
 
@@ -59,7 +58,7 @@ constexpr int OC_SLAB_WAVES = 16384;          // slabs per triangle = OC_SLAB_WA
 constexpr int OC_SLABS_MAX = 64;
 constexpr int OC_SUBWAVE_F = 32768;           // from this many faces on, 16 lanes per triangle instead of a wave
 constexpr int OC_NB = 256;                    // workgroups of the strided passes: each ends in a few atomics on the same addresses
-enum { BOX_MIN = 0, BOX_MAX = 3, BOX_BAD = 6, BOX_IDX = 7, BOX_WORDS = 8, CNT_IN = 2 * BOX_WORDS, CNT_WARN, CNT_OUT, MISC_WORDS = 32 };
+enum { CNT_IN = 2 * BOX_WORDS, CNT_WARN, CNT_OUT, MISC_WORDS = 32 };      // behind the two boxes (cell_list.h)
 
 struct OcMap {
     double sx, sy, sz, tx, ty, tz;            // x' = s * x + t
@@ -67,59 +66,8 @@ struct OcMap {
     int G;
 };
 
-__device__ __forceinline__ bool oc_finite(float x) { return fabsf(x) <= 3.4028234e38f; }
-
 // cell of a rescaled coordinate, clamped into the grid: monotone in v, which is all the cull needs
 __device__ __forceinline__ int oc_cell(double v, double inv, int G) { return (int)fmin(fmax(floor(v * inv), 0.0), (double)(G - 1)); }
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// a. faces == nullptr: the n points of P.  Otherwise: the n faces over the Vn vertices of P; a face with an index outside [0, Vn) is counted in
-// box[BOX_IDX] and none of its vertices is read.  box[0..2] / box[3..5] = min / max of the finite coordinates as order-preserving keys,
-// box[BOX_BAD] = points / referenced vertices (counted per reference) with a non-finite coordinate
-__global__ __launch_bounds__(OC_T) void k_occ_box(const float* __restrict__ P, int Vn, const int64_t* __restrict__ faces, int n,
-                                                 uint32_t* __restrict__ box) {
-    __shared__ uint32_t sh[BOX_WORDS];
-    const int t = threadIdx.x;
-    if (t < BOX_WORDS) sh[t] = t < BOX_MAX ? 0xffffffffu : 0u;
-    __syncthreads();
-    uint32_t mn0 = 0xffffffffu, mn1 = 0xffffffffu, mn2 = 0xffffffffu, mx0 = 0u, mx1 = 0u, mx2 = 0u, bad = 0u, badidx = 0u;
-    for (long long i = (long long)blockIdx.x * OC_T + t; i < n; i += (long long)gridDim.x * OC_T) {
-        long long v[3] = {i, 0, 0};
-        int nv = 1;
-        if (faces != nullptr) {
-            v[0] = faces[3 * i]; v[1] = faces[3 * i + 1]; v[2] = faces[3 * i + 2];
-            nv = 3;
-            if (v[0] < 0 || v[0] >= Vn || v[1] < 0 || v[1] >= Vn || v[2] < 0 || v[2] >= Vn) { ++badidx; continue; }
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (k >= nv) break;
-            const float x = P[3 * v[k]], y = P[3 * v[k] + 1], z = P[3 * v[k] + 2];
-            if (!oc_finite(x) || !oc_finite(y) || !oc_finite(z)) { ++bad; continue; }
-            const uint32_t a = f2ord(x), b = f2ord(y), c = f2ord(z);
-            mn0 = min(mn0, a); mn1 = min(mn1, b); mn2 = min(mn2, c);
-            mx0 = max(mx0, a); mx1 = max(mx1, b); mx2 = max(mx2, c);
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {                       // one LDS atomic per wave and word, not one per thread
-        mn0 = min(mn0, (uint32_t)__shfl_xor((int)mn0, off)); mn1 = min(mn1, (uint32_t)__shfl_xor((int)mn1, off));
-        mn2 = min(mn2, (uint32_t)__shfl_xor((int)mn2, off)); mx0 = max(mx0, (uint32_t)__shfl_xor((int)mx0, off));
-        mx1 = max(mx1, (uint32_t)__shfl_xor((int)mx1, off)); mx2 = max(mx2, (uint32_t)__shfl_xor((int)mx2, off));
-        bad += (uint32_t)__shfl_xor((int)bad, off);
-        badidx += (uint32_t)__shfl_xor((int)badidx, off);
-    }
-    if ((t & 63) == 0) {
-        atomicMin(&sh[0], mn0); atomicMin(&sh[1], mn1); atomicMin(&sh[2], mn2);
-        atomicMax(&sh[3], mx0); atomicMax(&sh[4], mx1); atomicMax(&sh[5], mx2);
-        if (bad) atomicAdd(&sh[BOX_BAD], bad);
-        if (badidx) atomicAdd(&sh[BOX_IDX], badidx);
-    }
-    __syncthreads();
-    // (atomics on one address are served one after the other: the points' box, which nobody reads, is not sent, and the launches keep the grid small)
-    if (t < BOX_MAX) { if (faces != nullptr) atomicMin(&box[t], sh[t]); }
-    else if (t < BOX_BAD) { if (faces != nullptr) atomicMax(&box[t], sh[t]); }
-    else if (t < BOX_WORDS && sh[t]) atomicAdd(&box[t], sh[t]);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // b. the points in cell order
@@ -129,15 +77,17 @@ __device__ __forceinline__ void oc_rescale(const float* __restrict__ P, size_t i
     z = m.sz * (double)P[3 * i + 2] + m.tz;
 }
 
-__global__ void k_occ_keys(const float* __restrict__ P, int Q, OcMap m, uint64_t* __restrict__ key, int* __restrict__ val) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= Q) return;
-    double x, y, z;
-    oc_rescale(P, (size_t)i, m, x, y, z);
-    const bool in = 0.0 <= x && x <= m.R && 0.0 <= y && y <= m.R && 0.0 <= z && z <= m.R;
-    key[i] = in ? (uint64_t)(oc_cell(x, m.inv, m.G) * m.G + oc_cell(y, m.inv, m.G)) : (uint64_t)(m.G * m.G);
-    val[i] = i;
-}
+// the xy cell key of point i of P; outside the box: G * G, behind every cell
+struct OcKey {
+    const float* P;
+    OcMap m;
+    __device__ uint64_t operator()(int i) const {
+        double x, y, z;
+        oc_rescale(P, (size_t)i, m, x, y, z);
+        const bool in = 0.0 <= x && x <= m.R && 0.0 <= y && y <= m.R && 0.0 <= z && z <= m.R;
+        return in ? (uint64_t)(oc_cell(x, m.inv, m.G) * m.G + oc_cell(y, m.inv, m.G)) : (uint64_t)(m.G * m.G);
+    }
+};
 
 // sorted points as (x', y', z', index); their parity words cleared
 __global__ void k_occ_gather(const int* __restrict__ val, const float* __restrict__ P, int Q, OcMap m, double4* __restrict__ sp,
@@ -149,18 +99,6 @@ __global__ void k_occ_gather(const int* __restrict__ val, const float* __restric
     oc_rescale(P, (size_t)i, m, x, y, z);
     sp[p] = make_double4(x, y, z, __longlong_as_double((long long)i));
     par[p] = 0u;
-}
-
-// cstart[c] = first sorted position whose key is >= c, c = 0 .. nc (cstart[nc] = the points inside the box)
-__global__ void k_occ_cell_starts(const uint64_t* __restrict__ key, int Q, int* __restrict__ cstart, int nc) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c > nc) return;
-    int lo = 0, hi = Q;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (key[mid] < (uint64_t)c) lo = mid + 1; else hi = mid;
-    }
-    cstart[c] = lo;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -294,13 +232,6 @@ static size_t carve_occupancy(OccWs& w, void* base, int Q) {
     return c.off + 256;
 }
 
-static double host_ord2f(uint32_t u) {
-    const uint32_t b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    float f;
-    memcpy(&f, &b, sizeof(f));
-    return (double)f;
-}
-
 }  // namespace
 
 // tuning / test hook: 0 = slabs per triangle from F (shipped), 1 .. 64 = that many.  Same results either way.
@@ -333,22 +264,21 @@ extern "C" int pdhip_mesh_contains(const float* vertices, int Vn, const int64_t*
     OccWs w;
     carve_occupancy(w, ws, Q);
     // a. the box of the referenced vertices, finiteness, the face indices
-    PD_HIP(hipMemsetAsync(w.misc, 0, MISC_WORDS * sizeof(uint32_t), s));
-    PD_HIP(hipMemsetAsync(w.misc, 0xff, 3 * sizeof(uint32_t), s));
-    PD_HIP(hipMemsetAsync(w.misc + BOX_WORDS, 0xff, 3 * sizeof(uint32_t), s));
-    k_occ_box<<<std::min(cdiv(F, OC_T), OC_NB), OC_T, 0, s>>>(vertices, Vn, faces, F, w.misc);
-    if (Q > 0) k_occ_box<<<std::min(cdiv(Q, OC_T), OC_NB), OC_T, 0, s>>>(points, Q, nullptr, Q, w.misc + BOX_WORDS);
+    int rc = clear_boxes(w.misc, 2, MISC_WORDS, s);
+    if (rc) return rc;
+    k_point_box<<<std::min(cdiv(F, CL_T), OC_NB), CL_T, 0, s>>>(vertices, Vn, faces, F, 1, w.misc);
+    if (Q > 0) k_point_box<<<std::min(cdiv(Q, CL_T), OC_NB), CL_T, 0, s>>>(points, Q, nullptr, Q, 0, w.misc + BOX_WORDS);   // (its box: nobody reads it)
     PD_LAUNCH_CHECK();
-    uint32_t h[2 * BOX_WORDS];
-    PD_HIP(hipMemcpyAsync(h, w.misc, sizeof(h), hipMemcpyDeviceToHost, s));
-    PD_HIP(hipStreamSynchronize(s));
-    PD_REQUIRE(h[BOX_IDX] == 0, "pdhip_mesh_contains: %u face(s) with a vertex index outside [0, %d)", h[BOX_IDX], Vn);
-    PD_REQUIRE(h[BOX_BAD] == 0, "pdhip_mesh_contains: %u referenced vertex coordinate triple(s) not finite", h[BOX_BAD]);
-    PD_REQUIRE(h[BOX_WORDS + BOX_BAD] == 0, "pdhip_mesh_contains: %u point(s) with a non-finite coordinate", h[BOX_WORDS + BOX_BAD]);
+    HostBox box[2];                                                // referenced vertices, points (counts only)
+    rc = read_boxes(w.misc, box, s);
+    if (rc) return rc;
+    PD_REQUIRE(box[0].bad_index == 0, "pdhip_mesh_contains: %u face(s) with a vertex index outside [0, %d)", box[0].bad_index, Vn);
+    PD_REQUIRE(box[0].bad == 0, "pdhip_mesh_contains: %u referenced vertex coordinate triple(s) not finite", box[0].bad);
+    PD_REQUIRE(box[1].bad == 0, "pdhip_mesh_contains: %u point(s) with a non-finite coordinate", box[1].bad);
     OcMap m;
     double sc[3], tr[3];
     for (int a = 0; a < 3; ++a) {
-        const double mn = host_ord2f(h[BOX_MIN + a]), mx = host_ord2f(h[BOX_MAX + a]);
+        const double mn = box[0].mn[a], mx = box[0].mx[a];
         PD_REQUIRE(mx > mn, "pdhip_mesh_contains: flat mesh, no extent on axis %d (%g .. %g)", a, mn, mx);
         sc[a] = (double)(resolution - 1) / (mx - mn);
         const double sm = sc[a] * mn;
@@ -364,10 +294,8 @@ extern "C" int pdhip_mesh_contains(const float* vertices, int Vn, const int64_t*
     }
     // b. the points in cell order
     const int nc = m.G * m.G;
-    k_occ_keys<<<cdiv(Q, OC_T), OC_T, 0, s>>>(points, Q, m, w.sb.k[0], w.sb.v[0]);
-    const int cur = radix_sort(w.sb, Q, bits_for((unsigned long long)nc), s);
+    const int cur = sort_by_cell(w.sb, Q, OcKey{points, m}, (unsigned long long)nc, w.cstart, s);      // (cstart[nc] = the points inside the box)
     k_occ_gather<<<cdiv(Q, OC_T), OC_T, 0, s>>>(w.sb.v[cur], points, Q, m, w.sp, w.par);
-    k_occ_cell_starts<<<cdiv(nc + 1, OC_T), OC_T, 0, s>>>(w.sb.k[cur], Q, w.cstart, nc);
     PD_LAUNCH_CHECK();
     // c, d.
     const int slabs = g_contains_slabs > 0 ? g_contains_slabs : tri_slabs(F);

@@ -1,6 +1,7 @@
 // Radix sort (LSD, 8-bit digits, stable) of 64-bit keys with int32 values, a one-workgroup scan and a tiled scan over many
-// workgroups (both templated on the element type): shared by the geometry units that sort or scan on the device (uv_atlas.hip: edge keys, packing order, UV entries;
-// surface_recon.hip: cell keys, vertex / triangle offsets; neighbor_mesh.hip: edge and pair keys; simplify_mesh.hip: directed-edge keys, adjacency / winner / face offsets).  Written
+// workgroups (both templated on the element type): shared by the geometry units that sort or scan on the device (cell_list.h: the cell keys of
+// surface_recon.hip, cloud_metrics.hip and occupancy.hip; uv_atlas.hip: edge keys, packing order, UV entries; surface_recon.hip: vertex / triangle
+// offsets; neighbor_mesh.hip: edge and pair keys; simplify_mesh.hip: directed-edge keys, adjacency / winner / face offsets).  Written
 // here because rocPRIM's sort carries scratch on gfx950.  Every kernel has internal linkage: each including unit gets its own copy.
 #pragma once
 #include "common.h"

@@ -2,7 +2,7 @@
 // normals for a point set + screened Poisson reconstruction), on a dense grid.
 //
 //   pdhip_estimate_normals
-//     a. uniform cell grid over the cloud (cell keys, radix sort, cell start / end), k nearest neighbours by scanning the ring of
+//     a. uniform cell grid over the cloud (cell_list.h: cell keys, radix sort, cell starts), k nearest neighbours by scanning the ring of
 //        cells round each point, the ring growing until the k-th distance is certified by the scanned cube;
 //     b. normal = eigenvector of the smallest eigenvalue of the neighbourhood covariance (f64 about the neighbourhood mean,
 //        closed-form 3 x 3 symmetric solve in registers);
@@ -18,7 +18,7 @@
 //        wound counter-clockwise seen from outside; vertex colours = colour of the nearest cloud point.
 // No float atomics: every sum has a fixed order, two calls give identical bytes.  Compiled with -ffp-contract=off.
 #include "common.h"
-#include "radix_sort.h"
+#include "cell_list.h"
 #include "mc_tables.h"
 #include <math.h>
 #include <string.h>
@@ -85,24 +85,17 @@ __global__ __launch_bounds__(TB) void k_sr_moments(const float* __restrict__ P, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// cell list
-__global__ void k_sr_cell_keys(const float* __restrict__ P, int N, CellGrid g, uint64_t* __restrict__ key, int* __restrict__ val) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    const int cx = cell_of(P[3 * i], g.ox, g.cs, g.C), cy = cell_of(P[3 * i + 1], g.oy, g.cs, g.C), cz = cell_of(P[3 * i + 2], g.oz, g.cs, g.C);
-    key[i] = (uint64_t)((cz * g.C + cy) * g.C + cx);
-    val[i] = i;
-}
-__global__ void k_sr_cell_bounds(const uint64_t* __restrict__ key, const int* __restrict__ val, const float* __restrict__ P, int N,
-                                 int* __restrict__ cstart, int* __restrict__ cend, float4* __restrict__ spos) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= N) return;
-    const uint64_t k = key[p];
-    if (p == 0 || key[p - 1] != k) cstart[(int)k] = p;
-    if (p == N - 1 || key[p + 1] != k) cend[(int)k] = p + 1;
-    const int i = val[p];
-    spos[p] = make_float4(P[3 * i], P[3 * i + 1], P[3 * i + 2], __int_as_float(i));
-}
+// cell list (cell_list.h): the key of the cell of point i of P.  The scans below visit the cells of a cube in the order z, y, x ascending and a
+// cell's points cstart[c] .. cstart[c + 1] ascending: the f32 sums of k_sr_sample_weights and k_sr_rhs and the ties of k_sr_nearest_color
+// rest on that order
+struct SrKey {
+    const float* P;
+    CellGrid g;
+    __device__ uint64_t operator()(int i) const {
+        const int cx = cell_of(P[3 * i], g.ox, g.cs, g.C), cy = cell_of(P[3 * i + 1], g.oy, g.cs, g.C), cz = cell_of(P[3 * i + 2], g.oz, g.cs, g.C);
+        return (uint64_t)((cz * g.C + cy) * g.C + cx);
+    }
+};
 
 // distance^2 from q to the nearest face of the scanned cube of cells [c - r, c + r] that is not a face of the whole grid
 __device__ __forceinline__ float ring_bound(float q, float o, float cs, int C, int c, int r) {
@@ -146,9 +139,8 @@ __device__ __forceinline__ void smallest_eigvec(double a00, double a01, double a
     }
 }
 
-__global__ __launch_bounds__(KNN_T) void k_sr_knn_normals(const float4* __restrict__ spos, const int* __restrict__ cstart,
-                                                          const int* __restrict__ cend, CellGrid g, int N, int k, int* __restrict__ knn,
-                                                          float* __restrict__ nrm) {
+__global__ __launch_bounds__(KNN_T) void k_sr_knn_normals(const float4* __restrict__ spos, const int* __restrict__ cstart, CellGrid g, int N,
+                                                          int k, int* __restrict__ knn, float* __restrict__ nrm) {
     __shared__ float s_d[KMAX][KNN_T];
     __shared__ int s_p[KMAX][KNN_T];
     const int t = threadIdx.x;
@@ -161,13 +153,12 @@ __global__ __launch_bounds__(KNN_T) void k_sr_knn_normals(const float4* __restri
     for (int r = 1;; ++r) {
         int cnt = 0, maxs = 0;
         float maxd = -1.0f;
-        const int x0 = max(cx - r, 0), x1 = min(cx + r, C - 1), y0 = max(cy - r, 0), y1 = min(cy + r, C - 1), z0 = max(cz - r, 0),
-                  z1 = min(cz + r, C - 1);
-        for (int z = z0; z <= z1; ++z)
-            for (int y = y0; y <= y1; ++y)
-                for (int x = x0; x <= x1; ++x) {
+        const CellCube q = cube_around(cx, cy, cz, r, C);
+        for (int z = q.z0; z <= q.z1; ++z)
+            for (int y = q.y0; y <= q.y1; ++y)
+                for (int x = q.x0; x <= q.x1; ++x) {
                     const int c = (z * C + y) * C + x;
-                    const int e = cend[c];
+                    const int e = cstart[c + 1];
                     for (int p = cstart[c]; p < e; ++p) {
                         const float4 s = spos[p];
                         const float dx = s.x - me.x, dy = s.y - me.y, dz = s.z - me.z;
@@ -186,10 +177,9 @@ __global__ __launch_bounds__(KNN_T) void k_sr_knn_normals(const float4* __restri
                         }
                     }
                 }
-        const bool all = x0 == 0 && y0 == 0 && z0 == 0 && x1 == C - 1 && y1 == C - 1 && z1 == C - 1;
         const float b = fminf(fminf(ring_bound(me.x, g.ox, g.cs, C, cx, r), ring_bound(me.y, g.oy, g.cs, C, cy, r)),
                               ring_bound(me.z, g.oz, g.cs, C, cz, r));
-        if (all || (cnt == k && b > 0.0f && maxd <= b * b)) break;
+        if (q.covers(C) || (cnt == k && b > 0.0f && maxd <= b * b)) break;
     }
     double mx = 0.0, my = 0.0, mz = 0.0;
     for (int j = 0; j < k; ++j) {
@@ -298,19 +288,20 @@ __global__ void k_sr_orient_last(const float* __restrict__ P, const int* __restr
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // d. Poisson.  Sample weights: a_p = 1 / sum_q w(|p - q|); snrm (sorted order) = a_p * unit normal
-__global__ void k_sr_sample_weights(const float4* __restrict__ spos, const int* __restrict__ cstart, const int* __restrict__ cend, CellGrid g,
-                                    int N, float invR2, const float* __restrict__ nrm, float4* __restrict__ snrm) {
+__global__ void k_sr_sample_weights(const float4* __restrict__ spos, const int* __restrict__ cstart, CellGrid g, int N, float invR2,
+                                    const float* __restrict__ nrm, float4* __restrict__ snrm) {
     const int sp = blockIdx.x * blockDim.x + threadIdx.x;
     if (sp >= N) return;
     const float4 me = spos[sp];
     const int C = g.C;
     const int cx = cell_of(me.x, g.ox, g.cs, C), cy = cell_of(me.y, g.oy, g.cs, C), cz = cell_of(me.z, g.oz, g.cs, C);
     float rho = 0.f;
-    for (int z = max(cz - 1, 0); z <= min(cz + 1, C - 1); ++z)
-        for (int y = max(cy - 1, 0); y <= min(cy + 1, C - 1); ++y)
-            for (int x = max(cx - 1, 0); x <= min(cx + 1, C - 1); ++x) {
+    const CellCube q = cube_around(cx, cy, cz, 1, C);
+    for (int z = q.z0; z <= q.z1; ++z)
+        for (int y = q.y0; y <= q.y1; ++y)
+            for (int x = q.x0; x <= q.x1; ++x) {
                 const int c = (z * C + y) * C + x;
-                const int e = cend[c];
+                const int e = cstart[c + 1];
                 for (int p = cstart[c]; p < e; ++p) {
                     const float4 s = spos[p];
                     const float dx = s.x - me.x, dy = s.y - me.y, dz = s.z - me.z;
@@ -332,8 +323,8 @@ struct Grid {
 };
 
 // right-hand side of A chi = f, A = 6 I - (sum of the six neighbours), f = -div V (the factor h^2 is dropped: only the level set counts)
-__global__ void k_sr_rhs(const float4* __restrict__ spos, const float4* __restrict__ snrm, const int* __restrict__ cstart,
-                         const int* __restrict__ cend, CellGrid g, Grid G, float R, float* __restrict__ f) {
+__global__ void k_sr_rhs(const float4* __restrict__ spos, const float4* __restrict__ snrm, const int* __restrict__ cstart, CellGrid g, Grid G,
+                         float R, float* __restrict__ f) {
     const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int M = G.M;
     if (n >= (long long)M * M * M) return;
@@ -344,11 +335,12 @@ __global__ void k_sr_rhs(const float4* __restrict__ spos, const float4* __restri
         const int C = g.C;
         const int cx = (int)floorf((x - g.ox) / g.cs), cy = (int)floorf((y - g.oy) / g.cs), cz = (int)floorf((z - g.oz) / g.cs);
         const float invR2 = 1.0f / (R * R);
-        for (int zz = max(cz - 1, 0); zz <= min(cz + 1, C - 1); ++zz)
-            for (int yy = max(cy - 1, 0); yy <= min(cy + 1, C - 1); ++yy)
-                for (int xx = max(cx - 1, 0); xx <= min(cx + 1, C - 1); ++xx) {
+        const CellCube q = cube_around(cx, cy, cz, 1, C);          // (a node outside the cell grid: the cells within one of it, maybe none)
+        for (int zz = q.z0; zz <= q.z1; ++zz)
+            for (int yy = q.y0; yy <= q.y1; ++yy)
+                for (int xx = q.x0; xx <= q.x1; ++xx) {
                     const int c = (zz * C + yy) * C + xx;
-                    const int e = cend[c];
+                    const int e = cstart[c + 1];
                     for (int p = cstart[c]; p < e; ++p) {
                         const float4 s = spos[p];
                         const float dx = x - s.x, dy = y - s.y, dz = z - s.z;
@@ -597,7 +589,7 @@ __global__ void k_sr_mc_faces(const float* __restrict__ chi, int M, const int* _
 
 // colour of the nearest cloud point (ties: the first in cell order)
 __global__ void k_sr_nearest_color(const float* __restrict__ Q, int nq, const float4* __restrict__ spos, const int* __restrict__ cstart,
-                                   const int* __restrict__ cend, CellGrid g, const float* __restrict__ colors, float* __restrict__ out) {
+                                   CellGrid g, const float* __restrict__ colors, float* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nq) return;
     const float qx = Q[3 * i], qy = Q[3 * i + 1], qz = Q[3 * i + 2];
@@ -607,13 +599,12 @@ __global__ void k_sr_nearest_color(const float* __restrict__ Q, int nq, const fl
     float bd = 3.0e38f;
     for (int r = 1;; ++r) {
         best = -1; bd = 3.0e38f;
-        const int x0 = max(cx - r, 0), x1 = min(cx + r, C - 1), y0 = max(cy - r, 0), y1 = min(cy + r, C - 1), z0 = max(cz - r, 0),
-                  z1 = min(cz + r, C - 1);
-        for (int z = z0; z <= z1; ++z)
-            for (int y = y0; y <= y1; ++y)
-                for (int x = x0; x <= x1; ++x) {
+        const CellCube q = cube_around(cx, cy, cz, r, C);
+        for (int z = q.z0; z <= q.z1; ++z)
+            for (int y = q.y0; y <= q.y1; ++y)
+                for (int x = q.x0; x <= q.x1; ++x) {
                     const int c = (z * C + y) * C + x;
-                    const int e = cend[c];
+                    const int e = cstart[c + 1];
                     for (int p = cstart[c]; p < e; ++p) {
                         const float4 s = spos[p];
                         const float dx = s.x - qx, dy = s.y - qy, dz = s.z - qz;
@@ -621,12 +612,11 @@ __global__ void k_sr_nearest_color(const float* __restrict__ Q, int nq, const fl
                         if (d < bd) { bd = d; best = __float_as_int(s.w); }
                     }
                 }
-        const bool all = x0 == 0 && y0 == 0 && z0 == 0 && x1 == C - 1 && y1 == C - 1 && z1 == C - 1;
         // (the bound is measured from the query itself to the faces of the scanned cube that are not faces of the grid: a point that was
         // not scanned lies beyond one of them, also when the query is outside the grid and its cell was clamped)
         const float b = fminf(fminf(ring_bound(qx, g.ox, g.cs, C, cx, r), ring_bound(qy, g.oy, g.cs, C, cy, r)),
                               ring_bound(qz, g.oz, g.cs, C, cz, r));
-        if (all || (best >= 0 && b > 0.0f && bd <= b * b)) break;
+        if (q.covers(C) || (best >= 0 && b > 0.0f && bd <= b * b)) break;
     }
     out[3 * i] = colors[3 * best]; out[3 * i + 1] = colors[3 * best + 1]; out[3 * i + 2] = colors[3 * best + 2];
 }
@@ -636,14 +626,15 @@ constexpr int CELLS_MAX = 128;                                     // cells per 
 
 struct Cells {
     SortBufs sb;
-    int *cstart, *cend;
+    int* cstart;
     float4* spos;
     double* mom;
 };
 static void carve_cells(Carve& c, Cells& w, int N) {
     carve_sort(c, w.sb, N);
-    w.cstart = c.take<int>((size_t)CELLS_MAX * CELLS_MAX * CELLS_MAX);
-    w.cend = c.take<int>((size_t)CELLS_MAX * CELLS_MAX * CELLS_MAX);
+    // cstart[0 .. nc] needs CELLS_MAX^3 + 1 ints.  It takes twice CELLS_MAX^3: this region was a start and an end table of that size, back to
+    // back, and the sizes that pdhip_estimate_normals_ws_bytes / pdhip_surface_recon_ws_bytes report are pinned (tests/test_ws_bytes_cpu.py)
+    w.cstart = c.take<int>(2 * (size_t)CELLS_MAX * CELLS_MAX * CELLS_MAX);
     w.spos = c.take<float4>(N);
     w.mom = c.take<double>(MOM_WORDS);
 }
@@ -683,12 +674,8 @@ static int build_cells(Cells& w, const float* P, int N, const Box& b, double cs_
     g.C = C;
     g.cs = (float)(b.ext / C * (1.0 + 1.0e-6));
     g.ox = (float)b.mn[0]; g.oy = (float)b.mn[1]; g.oz = (float)b.mn[2];
-    const size_t nc = (size_t)C * C * C;
-    PD_HIP(hipMemsetAsync(w.cstart, 0, nc * sizeof(int), s));
-    PD_HIP(hipMemsetAsync(w.cend, 0, nc * sizeof(int), s));
-    k_sr_cell_keys<<<cdiv(N, TB), TB, 0, s>>>(P, N, g, w.sb.k[0], w.sb.v[0]);
-    const int cur = radix_sort(w.sb, N, bits_for((unsigned long long)nc), s);
-    k_sr_cell_bounds<<<cdiv(N, TB), TB, 0, s>>>(w.sb.k[cur], w.sb.v[cur], P, N, w.cstart, w.cend, w.spos);
+    const int cur = sort_by_cell(w.sb, N, SrKey{P, g}, (unsigned long long)C * C * C, w.cstart, s);
+    k_gather_xyzi<<<cdiv(N, TB), TB, 0, s>>>(w.sb.v[cur], P, N, w.spos);
     PD_LAUNCH_CHECK();
     return PDHIP_OK;
 }
@@ -762,7 +749,7 @@ extern "C" int pdhip_estimate_normals(const float* points, int N, int k, int n_e
     CellGrid g;
     rc = build_cells(w.cells, points, N, b, b.ext / std::max(1.0, sqrt((double)N / (k + 2.0))), CELLS_MAX, g, s);
     if (rc) return rc;
-    k_sr_knn_normals<<<cdiv(N, KNN_T), KNN_T, 0, s>>>(w.cells.spos, w.cells.cstart, w.cells.cend, g, N, k, w.knn, normals);
+    k_sr_knn_normals<<<cdiv(N, KNN_T), KNN_T, 0, s>>>(w.cells.spos, w.cells.cstart, g, N, k, w.knn, normals);
     // rule 1
     k_sr_eyes<<<1, 64, 0, s>>>(0.5 * (b.mn[0] + b.mx[0]), 0.5 * (b.mn[1] + b.mx[1]), 0.5 * (b.mn[2] + b.mx[2]), eye_radius * b.ext, n_eyes, w.eyes);
     PD_LAUNCH_CHECK();
@@ -822,8 +809,8 @@ extern "C" int pdhip_surface_recon(const float* points, const float* normals, co
     PD_HIP(hipMemsetAsync(w.misc, 0, M_WORDS * sizeof(int), s));
     PD_HIP(hipMemsetAsync(w.p, 0, (size_t)n3 * sizeof(float), s));
     PD_HIP(hipMemsetAsync(w.q, 0, (size_t)n3 * sizeof(float), s));
-    k_sr_sample_weights<<<cdiv(N, TB), TB, 0, s>>>(w.cells.spos, w.cells.cstart, w.cells.cend, g, N, 1.0f / (R * R), normals, w.snrm);
-    k_sr_rhs<<<gN3, TB, 0, s>>>(w.cells.spos, w.snrm, w.cells.cstart, w.cells.cend, g, G, R, w.f);
+    k_sr_sample_weights<<<cdiv(N, TB), TB, 0, s>>>(w.cells.spos, w.cells.cstart, g, N, 1.0f / (R * R), normals, w.snrm);
+    k_sr_rhs<<<gN3, TB, 0, s>>>(w.cells.spos, w.snrm, w.cells.cstart, g, G, R, w.f);
     k_sr_cg_init<<<CG_NB, CG_T, 0, s>>>(w.f, w.chi, w.r, n3, w.part_ff, w.part_rr[0]);
     PD_LAUNCH_CHECK();
     const int cap = 24 * Gc;
@@ -877,8 +864,7 @@ extern "C" int pdhip_surface_recon(const float* points, const float* normals, co
     PD_REQUIRE(hm[M_NV] <= vertex_capacity && hm[M_NF] <= face_capacity, "pdhip_surface_recon: capacities too small: the mesh has %d "
                "vertices and %d faces, the buffers hold %d and %d", hm[M_NV], hm[M_NF], vertex_capacity, face_capacity);
     if (colors) {
-        k_sr_nearest_color<<<cdiv(hm[M_NV], TB), TB, 0, s>>>(vertices, hm[M_NV], w.cells.spos, w.cells.cstart, w.cells.cend, g, colors,
-                                                             vertex_colors);
+        k_sr_nearest_color<<<cdiv(hm[M_NV], TB), TB, 0, s>>>(vertices, hm[M_NV], w.cells.spos, w.cells.cstart, g, colors, vertex_colors);
         PD_LAUNCH_CHECK();
     }
     return PDHIP_OK;

@@ -131,6 +131,41 @@ def test_determinism_also_with_another_stream_busy():
     assert torch.equal(v1.view(torch.int32), v2.view(torch.int32)) and torch.equal(f1, f2)
 
 
+def test_bytes_equal_the_recorded_ones():
+    """Normals, vertices, faces and vertex colours of three small clouds (tools/surface_recon_eval.py:recon_bytes: 16 points = one cell,
+    257 points, 1 500 points through the reconstruction at depth 6) equal tests/golden/surface_recon_parent.npz, recorded on an MI355X
+    before the cell list moved to csrc/cell_list.h, bit for bit."""
+    from tools import surface_recon_eval as ev
+    want = np.load(ev.BYTES_PATH)
+    got = ev.recon_bytes()
+    assert sorted(got) == sorted(want.files)
+    for k in want.files:
+        a, b = torch.from_numpy(got[k]), torch.from_numpy(want[k])
+        assert a.dtype == b.dtype and a.shape == b.shape, (k, a.dtype, b.dtype, a.shape, b.shape)
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), k
+
+
+def test_vertex_colour_is_the_colour_of_a_nearest_cloud_point():
+    """Every vertex colour is the colour of a cloud point that attains the smallest d = (dx dx + dy dy) + dz dz, dx = s - q, in float32 (the
+    expression and operand order of k_sr_nearest_color): the colours are distinct, so the colour names the point the kernel chose."""
+    from pointdreamer_amd import spr, synthetic
+    xyz, _, _ = synthetic.solid('cup').sample(1500, seed=1)
+    col = np.random.default_rng(5).random((len(xyz), 3), dtype=np.float32)
+    index_of = {row.tobytes(): i for i, row in enumerate(col)}
+    assert len(index_of) == len(col)
+    X = T(xyz)
+    v, f, c = spr.poisson_reconstruct(X, spr.estimate_normals(X), depth=6, colors=T(col))
+    q, c = v.cpu().numpy(), c.cpu().numpy()
+    assert len(q) > 1000 and c.dtype == np.float32
+    chosen = np.array([index_of[row.tobytes()] for row in c])     # (KeyError: a colour that no cloud point has)
+    for b in range(0, len(q), 2048):
+        dx, dy, dz = (xyz[None, :, a] - q[b:b + 2048, None, a] for a in range(3))
+        d = (dx * dx + dy * dy) + dz * dz
+        assert d.dtype == np.float32
+        mine = d[np.arange(d.shape[0]), chosen[b:b + 2048]]
+        assert np.array_equal(mine, d.min(axis=1)), np.flatnonzero(mine != d.min(axis=1))[:8] + b
+
+
 def test_capacity_and_failure_paths():
     """Too small capacities name the sizes needed and write nothing past the buffers; degenerate clouds are refused, no fault."""
     from pointdreamer_amd import spr, _lib

@@ -4,6 +4,8 @@
                                                  #   and the table of profiles/surface_recon_accuracy.txt
   python tools/surface_recon_eval.py texture     # texture quality of the CLI with the reconstructed mesh against the analytic mesh
                                                  #   (torus, rounded box, three cloud seeds) -> appended to the same profile file
+  python tools/surface_recon_eval.py bytes       # normals / mesh / vertex colours of three small clouds -> tests/golden/surface_recon_parent.npz:
+                                                 #   run at the commit whose bytes a refactor of csrc/surface_recon.hip must keep
 
 The helpers (cases, analytic meshes, the atlas-vs-colour-field figure) are imported by the test so that both compute the same thing."""
 import json
@@ -22,6 +24,7 @@ N_POINTS = 25000
 SOLIDS = ('sphere', 'ellipsoid', 'torus', 'rounded_box', 'two_spheres', 'cup')
 JSON_PATH = os.path.join(ROOT, 'tests', 'golden', 'surface_recon_measured.json')
 TXT_PATH = os.path.join(ROOT, 'profiles', 'surface_recon_accuracy.txt')
+BYTES_PATH = os.path.join(ROOT, 'tests', 'golden', 'surface_recon_parent.npz')
 TEXTURE_MARK = "Texture quality"
 
 
@@ -170,6 +173,30 @@ def texture():
     print('\n'.join(L))
 
 
+def recon_bytes():
+    """The arrays that tests/golden/surface_recon_parent.npz pins byte for byte (name -> numpy array; faces as int32):
+      sphere_16    estimate_normals at the smallest N: k = 16 = N, one cell, every scan ends by covering the grid
+      cup_257      estimate_normals with N off the workgroup size and a few cells per axis
+      cup_1500     estimate_normals, then poisson_reconstruct(depth=6, colors=rgb): normals, vertices, faces, vertex colours"""
+    import torch
+    from pointdreamer_amd import synthetic, spr
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    out = {}
+    for name, n in (('sphere', 16), ('cup', 257)):
+        out[f'{name}_{n}_normals'] = spr.estimate_normals(T(synthetic.solid(name).sample(n, seed=1)[0]))
+    xyz, rgb, _ = synthetic.solid('cup').sample(1500, seed=1)
+    nrm = spr.estimate_normals(T(xyz))
+    v, f, c = spr.poisson_reconstruct(T(xyz), nrm, depth=6, colors=T(rgb))
+    out.update(cup_1500_normals=nrm, cup_1500_vertices=v, cup_1500_faces=f.to(torch.int32), cup_1500_colors=c)
+    return {k: a.cpu().numpy() for k, a in out.items()}
+
+
+def write_recon_bytes():
+    got = recon_bytes()
+    np.savez_compressed(BYTES_PATH, **got)
+    print(f"{BYTES_PATH}: {os.path.getsize(BYTES_PATH)} bytes; " + ', '.join(f"{k} {a.shape}" for k, a in got.items()))
+
+
 if __name__ == '__main__':
     logging.getLogger('pointdreamer_amd').setLevel(logging.WARNING)
-    {'accuracy': accuracy, 'texture': texture}[sys.argv[1]]()
+    {'accuracy': accuracy, 'texture': texture, 'bytes': write_recon_bytes}[sys.argv[1]]()
