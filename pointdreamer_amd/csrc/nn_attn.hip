@@ -143,9 +143,6 @@ __global__ __launch_bounds__(256) void k_transpose_v(const half_t* __restrict__ 
     }
 }
 
-thread_local int g_attn_nbuf = 0;      // tuning hook: 2 / 3 LDS chunk buffers of k_attention_t64, 0 = automatic
-thread_local int g_attn_qtn = 0;       // tuning hook: 1 / 2 = 64 / 128 queries per workgroup, 0 = automatic
-thread_local int g_attn_vt = 0;        // tuning hook: 1 = transposed-V workspace form (k_transpose_v + plain reads), 0 = LDS transpose reads
 #define PD_ATT_DSR128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 #define PD_ATT_DSR64T(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 #define PD_ATT_DSR64(dst, addr, off) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
@@ -409,18 +406,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QTN == 2 |
 }
 
 // vt_ws: N*T*C halfs of workspace for the transposed V (only used when T >= 128 and D == 64); may be null -> the 64-query kernel
-int attention(const half_t* qkv, half_t* out, int N, int T, int C, int D, hipStream_t s, half_t* vt_ws) {
+// hook_nbuf / hook_qtn / hook_vt: Tuning::attn_nbuf / attn_qtn / attn_vt
+int attention(const half_t* qkv, half_t* out, int N, int T, int C, int D, hipStream_t s, half_t* vt_ws, int hook_nbuf, int hook_qtn, int hook_vt) {
     PD_REQUIRE(D == 64 || D == 32, "attention: head dim must be 32 or 64 (got %d)", D);
     PD_REQUIRE(C % D == 0 && T % QT == 0, "attention: need C %% D == 0 and T %% 64 == 0 (T=%d C=%d)", T, C);
     const float scale2 = 1.0f / sqrtf((float)D);
     if (vt_ws != nullptr && D == 64 && T % 128 == 0 && (N * (C / D)) % 8 == 0) {
         PD_REQUIRE((N * (C / D)) % 8 == 0, "attention: N * heads must be a multiple of 8");
-        const bool small = g_attn_qtn == 1 || (g_attn_qtn != 2 && (T / 128) * (C / D) * N < 256);
-        const int nbuf = g_attn_nbuf == 2 || g_attn_nbuf == 3 ? g_attn_nbuf : 3;
+        const bool small = hook_qtn == 1 || (hook_qtn != 2 && (T / 128) * (C / D) * N < 256);
+        const int nbuf = hook_nbuf == 2 || hook_nbuf == 3 ? hook_nbuf : 3;
         const int gs = (small ? T / 64 : T / 128) * (C / D) * N;
 #define ATT_LAUNCH(Q, B, R) k_attention_t64<Q, B, R><<<gs, 256, 0, s>>>(qkv, vt_ws, out, T, C, scale2)
 #define ATT_BY_BUF(Q, R) do { if (nbuf == 3) ATT_LAUNCH(Q, 3, R); else ATT_LAUNCH(Q, 2, R); } while (0)
-        if (g_attn_vt != 0) {
+        if (hook_vt != 0) {
             k_transpose_v<<<dim3(T / 64, C / D, N), 256, 0, s>>>(qkv, vt_ws, T, C, D);
             if (small) ATT_BY_BUF(1, false); else ATT_BY_BUF(2, false);
         } else {

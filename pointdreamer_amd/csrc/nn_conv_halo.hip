@@ -18,7 +18,6 @@
 #include "nn_common.h"
 using namespace pdhip;
 namespace pdnn {
-thread_local int g_halo_strips = 0;                                    // tuning / test hook (pdhip_debug_set_conv_halo_strips)
 namespace {
 
 typedef __attribute__((address_space(3))) void lds_void_h;
@@ -522,35 +521,30 @@ int conv3x3_halo_splits(int N, int H, int W, int Cin, int Cout, int Cout_pad, si
     return splits;
 }
 
-// the split factor conv3x3_halo launches with (ws_floats: what the launcher may use, 0 = no workspace)
-int conv3x3_halo_launch_splits(int N, int H, int W, int Cin, int Cout, int Cout_pad, size_t ws_floats) {
+// the split factor to launch conv3x3_halo with (ws_floats: what the launcher may use, 0 = no workspace)
+int conv3x3_halo_launch_splits(const Tuning& t, int N, int H, int W, int Cin, int Cout, int Cout_pad, size_t ws_floats) {
     int splits = conv3x3_halo_splits(N, H, W, Cin, Cout, Cout_pad, ws_floats);
     if (splits < 1) splits = 1;
-    if (g_force_splits >= 1 && ws_floats > 0)                   // tuning / test hook
-        splits = (int)std::min<size_t>(std::min(g_force_splits, Cin / 32), ws_floats / ((size_t)N * H * W * Cout));
+    if (t.force_splits >= 1 && ws_floats > 0)                   // tuning / test hook
+        splits = (int)std::min<size_t>(std::min(t.force_splits, Cin / 32), ws_floats / ((size_t)N * H * W * Cout));
     return splits < 1 ? 1 : splits;
 }
 
-// gn_part (optional): fused GroupNorm octet partials; chunks per image returned through gn_fused (H*W/512 from the direct
-// epilogue, H*W/16 from the split reduce)
 int conv3x3_halo(const half_t* X, const half_t* Wt, const float* bias, const half_t* residual, half_t* Y, int N, int H, int W,
-                 int Cin, int Cout, int Cout_pad, const half_t* zero_page, hipStream_t s, float* gn_part, int* gn_fused,
+                 int Cin, int Cout, int Cout_pad, const half_t* zero_page, hipStream_t s, float* gn_part, int splits, bool full_rows,
                  float* splitk_ws, size_t splitk_ws_floats, const float* apply_table, int res_up, int in_up) {
     PD_REQUIRE(in_up == 0 || (apply_table == nullptr && H % 2 == 0), "conv3x3_halo: an up-sampled input excludes the in-conv GroupNorm");
     PD_REQUIRE(conv3x3_halo_eligible(N, H, W, Cin, Cout_pad), "conv3x3_halo: unsupported geometry (N=%d H=%d W=%d Cin=%d)", N, H, W, Cin);
-    const int splits = conv3x3_halo_launch_splits(N, H, W, Cin, Cout, Cout_pad, splitk_ws ? splitk_ws_floats : 0);
+    PD_REQUIRE(splits >= 1 && splits <= Cin / 32 && (splits == 1 || (splitk_ws != nullptr && (size_t)splits * N * H * W * Cout <= splitk_ws_floats)),
+               "conv3x3_halo: %d splits do not fit the layer / the split-K workspace", splits);
+    PD_REQUIRE(W != 256 || full_rows || H % 4 == 0, "conv3x3_halo: column strips need H %% 4 == 0 at W = 256");
     PD_REQUIRE(!res_up || (splits == 1 && residual != nullptr && H % 2 == 0), "conv3x3_halo: an up-sampled residual needs the direct (unsplit) epilogue");
     float* partial = splits > 1 ? splitk_ws : nullptr;
-    const bool fuse_sk = splits > 1 && gn_part != nullptr && (H * W) % 16 == 0;
-    if (gn_fused) *gn_fused = gn_part ? (splits > 1 ? (fuse_sk ? (H * W) / 16 : 0) : (int)(((long long)H * W) / 512)) : 0;
     float* gnp = splits > 1 ? nullptr : gn_part;
 #define HL_LAUNCH(WL) launch_halo<WL>(X, Wt, bias, residual, Y, N, H, Cin, Cout, Cout_pad, zero_page, s, gnp, splits, partial, apply_table, res_up, in_up)
     int rc;
 #define HL_LAUNCH2(WL, IL) launch_halo<WL, IL>(X, Wt, bias, residual, Y, N, H, Cin, Cout, Cout_pad, zero_page, s, gnp, splits, partial, apply_table, res_up, in_up)
-    // 256-wide images: column strips of 128 (4 rows x 128 per tile: 780 halo pixels per chunk instead of 1 032) measured +2-3 %
-    // over full rows, strips of 64 +1.5-3 % (that instance spilled 8 VGPRs and was never the default: removed in round 5); at 128 wide
-    // strips do not pay.  g_halo_strips: 0 automatic, 1 full rows.
-    if (W == 256 && g_halo_strips != 1 && H % 4 == 0) rc = HL_LAUNCH2(7, 8);
+    if (W == 256 && !full_rows) rc = HL_LAUNCH2(7, 8);       // column strips of 128 (conv3x3_halo_rows)
     else if (W == 256 && apply_table != nullptr) { set_error("conv3x3_halo: APPLY needs H %% 4 == 0 at W = 256"); return PDHIP_E_ARG; }
     else if (W == 256) rc = HL_LAUNCH(8);
     else if (W == 128) rc = HL_LAUNCH(7);
@@ -560,14 +554,8 @@ int conv3x3_halo(const half_t* X, const half_t* Wt, const float* bias, const hal
 #undef HL_LAUNCH2
     if (rc) return rc;
     PD_LAUNCH_CHECK();
-    if (splits > 1) return splitk_reduce(partial, splits, (long long)N * H * W, Cout, bias, residual, Y, fuse_sk ? gn_part : nullptr, H * W, s);
+    if (splits > 1) return splitk_reduce(partial, splits, (long long)N * H * W, Cout, bias, residual, Y, gn_part, H * W, s);
     return PDHIP_OK;
 }
 
 }  // namespace pdnn
-
-extern "C" int pdhip_debug_set_conv_halo_strips(int mode) {
-    const int old = pdnn::g_halo_strips;
-    pdnn::g_halo_strips = mode;
-    return old;
-}

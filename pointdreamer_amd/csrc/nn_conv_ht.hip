@@ -346,18 +346,15 @@ int launch_ht(const half_t* X, const half_t* Wt, const float* bias, const half_t
 
 }  // namespace
 
-thread_local int g_ht_mode = 1;        // tuning / test hook (pdhip_debug_set_conv_ht): 0 = never, 1 = automatic, 2 = every eligible layer
-thread_local int g_ht_slabs = 0;       //   K-slabs forced (0 = automatic)
-
 // K-slabs of a layer: K is cut in two (four) when the tiles alone leave half (three quarters) of the CUs idle and every slab keeps >= 8 chunks
 // (the combine -- 64 KB published write-through per workgroup, ticket, two slices re-read -- costs ~8 us: 64^2 / batch 1 at 256 input channels
 // 19.6 us in two slabs against 17.1 unsplit, at 512 / 768 / 1 024: 26.7 / 34.3 / 41.7 against 28.7 / 44.8 / 54.7); needs the split-K workspace
 // (tickets + tiles x S x 64 KB of f32 slices)
-int conv_ht_slabs(int N, int H, int W, int Cin, int Cout_pad, size_t ws_floats) {
+int conv_ht_slabs(const Tuning& t, int N, int H, int W, int Cin, int Cout_pad, size_t ws_floats) {
     const long long tiles = ((long long)N * H * W / 256) * (Cout_pad / 64);
     const int nct = Cin >> 5;
     auto fits = [&](int S) { return nct % S == 0 && tiles <= 4096 && (size_t)tiles * S * 16384 + PD_SK_TICKET_FLOATS <= ws_floats; };
-    if (g_ht_slabs > 0) return fits(g_ht_slabs) ? g_ht_slabs : 1;
+    if (t.ht_slabs > 0) return fits(t.ht_slabs) ? t.ht_slabs : 1;
     int S = 1;
     while (S < 4 && tiles * S * 2 <= 256 && nct / (S * 2) >= 8 && fits(S * 2)) S *= 2;
     return S;
@@ -369,24 +366,25 @@ int conv_ht_slabs(int N, int H, int W, int Cin, int Cout_pad, size_t ws_floats) 
 // 48 against 45); the 64^2 level once its tiles fill the chip (batch 2-4: 36 / 66 us against 45 / 84 at batch 2) and at batch 1 (half the
 // chip) up to 768 input channels (17 / 29 / 45 against 20 / 32 / 46; 1 024: 56 against 52); never at 32^2 (k_conv_rr's).  Beyond two rounds
 // the 512 x 128 halo tile owns the layer.
-bool conv_ht_routes(int N, int H, int W, int Cin, int Cout, int Cout_pad, size_t ws_floats) {
-    if (g_ht_mode == 0 || H != W || (W != 32 && W != 64 && W != 128) || ((long long)H * W) % 256 != 0 || Cin % 32 != 0 || Cout % 8 != 0 ||
+bool conv_ht_routes(const Tuning& t, int N, int H, int W, int Cin, int Cout, int Cout_pad, size_t ws_floats) {
+    if (t.ht_mode == 0 || H != W || (W != 32 && W != 64 && W != 128) || ((long long)H * W) % 256 != 0 || Cin % 32 != 0 || Cout % 8 != 0 ||
         Cout_pad % 64 != 0 || (long long)N * H * W * Cin * 2 > 0x7ffffff0LL || (long long)Cout_pad * 9 * Cin * 2 > 0x7ffffff0LL) return false;
-    if (g_ht_mode == 2) return true;
+    if (t.ht_mode == 2) return true;
     const long long tiles = ((long long)N * H * W / 256) * (Cout_pad / 64);
     if (tiles > 512) return false;
-    return W == 128 ? (N == 1 || Cin >= 512) : (W == 64 && (tiles >= 256 || Cin <= 768 || conv_ht_slabs(N, H, W, Cin, Cout_pad, ws_floats) > 1));
+    return W == 128 ? (N == 1 || Cin >= 512) : (W == 64 && (tiles >= 256 || Cin <= 768 || conv_ht_slabs(t, N, H, W, Cin, Cout_pad, ws_floats) > 1));
 }
 
 int conv_ht(const half_t* X, const half_t* Wt, const float* bias, const half_t* residual, half_t* Y, int N, int H, int W, int Cin, int Cout,
-            int Cout_pad, const half_t* zero_page, hipStream_t s, float* gn_part, int* gn_chunks, int res_up, float* ws, size_t ws_floats) {
+            int Cout_pad, const half_t* zero_page, hipStream_t s, float* gn_part, int res_up, int S, float* ws, size_t ws_floats) {
     PD_REQUIRE(X && Wt && Y && zero_page, "conv_ht: null argument");
     PD_REQUIRE(H == W && (W == 32 || W == 64 || W == 128) && Cin % 32 == 0 && Cout % 8 == 0 && Cout_pad % 64 == 0 && Cout_pad >= Cout,
                "conv_ht: unsupported geometry (H=%d W=%d Cin=%d Cout=%d)", H, W, Cin, Cout);
     PD_REQUIRE(res_up == 0 || (residual != nullptr && H % 2 == 0), "conv_ht: an up-sampled residual needs even H, W");
     PD_REQUIRE((long long)N * H * W * Cin * 2 <= 0x7ffffff0LL && (long long)Cout_pad * 9 * Cin * 2 <= 0x7ffffff0LL, "conv_ht: operand beyond the 2 GB buffer range");
-    if (gn_chunks) *gn_chunks = gn_part ? H * W / 256 : 0;
-    const int S = conv_ht_slabs(N, H, W, Cin, Cout_pad, ws ? ws_floats : 0);
+    const long long tiles = ((long long)N * H * W / 256) * (Cout_pad / 64);
+    PD_REQUIRE(S == 1 || (S > 1 && (Cin >> 5) % S == 0 && tiles <= 4096 && ws != nullptr && (size_t)tiles * S * 16384 + PD_SK_TICKET_FLOATS <= ws_floats),
+               "conv_ht: %d K-slabs do not fit the layer / the split-K workspace", S);
     if (W == 128) return launch_ht<7>(X, Wt, bias, residual, Y, N, H, Cin, Cout, Cout_pad, zero_page, gn_part, res_up, S, ws, s);
     if (W == 64) return launch_ht<6>(X, Wt, bias, residual, Y, N, H, Cin, Cout, Cout_pad, zero_page, gn_part, res_up, S, ws, s);
     return launch_ht<5>(X, Wt, bias, residual, Y, N, H, Cin, Cout, Cout_pad, zero_page, gn_part, res_up, S, ws, s);
@@ -397,18 +395,16 @@ int conv_ht(const half_t* X, const half_t* Wt, const float* bias, const half_t* 
 extern "C" int pdhip_conv_ht_f16(const void* x, const void* w_packed, const float* bias, const void* residual, int res_up, void* y, int N, int H, int W, int Cin,
                                  int Cout, int Cout_pad, const void* zero_page, float* splitk_ws, long long splitk_ws_floats, float* gn_part, int* gn_chunks,
                                  void* stream) {
+    const size_t wf = splitk_ws ? (size_t)splitk_ws_floats : 0;
+    if (gn_chunks) *gn_chunks = gn_part ? H * W / 256 : 0;      // one chunk per 256-pixel tile (what conv_plan books for CONV_HT)
     return pdnn::conv_ht((const pdnn::half_t*)x, (const pdnn::half_t*)w_packed, bias, (const pdnn::half_t*)residual, (pdnn::half_t*)y, N, H, W, Cin, Cout, Cout_pad,
-                         (const pdnn::half_t*)zero_page, as_stream(stream), gn_part, gn_chunks, res_up, splitk_ws, splitk_ws ? (size_t)splitk_ws_floats : 0);
+                         (const pdnn::half_t*)zero_page, as_stream(stream), gn_part, res_up, pdnn::conv_ht_slabs(pdnn::tuning(), N, H, W, Cin, Cout_pad, wf),
+                         splitk_ws, wf);
 }
 // host-only: the routing decision for a layer (no launch, no GPU needed)
 extern "C" int pdhip_conv_ht_plan(int N, int H, int W, int Cin, int Cout, int Cout_pad, long long splitk_ws_floats, int* routed, int* slabs) {
     const size_t wf = splitk_ws_floats > 0 ? (size_t)splitk_ws_floats : 0;
-    if (routed) *routed = pdnn::conv_ht_routes(N, H, W, Cin, Cout, Cout_pad, wf) ? 1 : 0;
-    if (slabs) *slabs = pdnn::conv_ht_slabs(N, H, W, Cin, Cout_pad, wf);
+    if (routed) *routed = pdnn::conv_ht_routes(pdnn::tuning(), N, H, W, Cin, Cout, Cout_pad, wf) ? 1 : 0;
+    if (slabs) *slabs = pdnn::conv_ht_slabs(pdnn::tuning(), N, H, W, Cin, Cout_pad, wf);
     return PDHIP_OK;
-}
-extern "C" int pdhip_debug_set_conv_ht(int mode, int slabs) {
-    const int old = pdnn::g_ht_mode;
-    pdnn::g_ht_mode = mode; pdnn::g_ht_slabs = slabs;
-    return old;
 }

@@ -571,10 +571,6 @@ __global__ void k_pack_rr(const half_t* __restrict__ src, int K, int Cin, int ta
 
 }  // namespace
 
-thread_local int g_rr_mode = 1;        // tuning / test hook (pdhip_debug_set_conv_rr): 0 = never, 1 = automatic, 2 = every eligible layer
-thread_local int g_rr_variant = 0;     // 0 = automatic, else force a variant id (see conv_rr_plan)
-thread_local int g_rr_slabs = 0;       // 0 = automatic, else force the slab count of the conv source
-
 size_t conv_rr_weight_halfs(int Cin, int taps, int Cs, int Cout) { return (size_t)(Cout / 16) * (taps * (Cin / 32) + Cs / 32) * 512; }
 
 int conv_rr_pack(const half_t* w_packed, int Cin, int taps, int Cs, int Cout, half_t* dst, hipStream_t s) {
@@ -606,16 +602,16 @@ static bool rr_variant(int v, int* w, int* mt, int* nf, int* cs) {
     }
     return false;
 }
-RrPlan conv_rr_plan(int N, int H, int W, int Cin, int Cout, int taps, int Cs, size_t ws_floats, bool want_gn) {
+RrPlan conv_rr_plan(const Tuning& t, int N, int H, int W, int Cin, int Cout, int taps, int Cs, size_t ws_floats, bool want_gn) {
     RrPlan p{0, 0, 0, 0, 0, 0, 0};
-    if (g_rr_mode == 0 || H != W || (taps != 9 && taps != 1)) return p;
+    if (t.rr_mode == 0 || H != W || (taps != 9 && taps != 1)) return p;
     // Candidate tile variants of the image width, smallest channel tile first.  Rule read off tools/bench_rr.py (profiles/r06_rr_bench_standalone.txt):
     // the variant whose tiles come closest to one workgroup per CU with the FEWEST K slabs wins -- every slab beyond the first costs a
     // write-through publish, a ticket round trip and a re-read of the slices by the last arriver (~4 us of a 10 us launch).
     static const int cand8[] = {1, 0}, cand16[] = {7, 2, 0}, cand32[] = {6, 3, 0}, cand64[] = {8, 0};
     const int* cand = W == 8 ? cand8 : W == 16 ? cand16 : W == 32 ? cand32 : W == 64 ? cand64 : nullptr;
     if (cand == nullptr) return p;
-    int v = g_rr_variant, vw = 0, mt = 0, nf = 0, cs = 0;
+    int v = t.rr_variant, vw = 0, mt = 0, nf = 0, cs = 0;
     if (v == 0) {
         for (int k = 0; cand[k] != 0; ++k) {
             int w_, mt_, nf_, cs_;
@@ -635,15 +631,15 @@ RrPlan conv_rr_plan(int N, int H, int W, int Cin, int Cout, int taps, int Cs, si
     // automatic routing: the launches a same-box A/B of the DDNM step favours (profiles/r06_rr_ab.txt): batch 1-2 at 8^2 ... 32^2 (batch 4 at
     // 8^2 only: from batch 4 up k_conv_sk's larger tiles win back what the slabs cost).  The 64^2 level at batch 1 (512+-channel layers: 27-30 /
     // 40 / 51 us at 512 / 768 / 1 024 input channels) went to k_conv_ht's two-slab form when that arrived (27 / 34 / 42 us, profiles/r06_ht_bench.txt)
-    if (g_rr_mode != 2) {
+    if (t.rr_mode != 2) {
         // (with an appended skip 1x1 the slabs of 1x1 units are the long pole: 16-27 us against k_conv_sk<10>'s 15-23 at every level -- not routed)
         const bool ok = Cs == 0 && W <= 32 && (N <= 2 || (N <= 4 && W == 8));
         if (!ok) return p;
     }
     // slabs: enough workgroups to put ~one on every CU, every slab a whole number of units, at most 8 conv slabs (the last arriver re-reads them all)
     const int u0 = Cin / cs, u1 = Cs / cs;
-    int s0 = g_rr_slabs > 0 ? g_rr_slabs : (int)std::max<long long>(1, (256 + tiles / 2) / tiles);
-    s0 = std::min(std::min(s0, u0), g_rr_slabs > 0 ? 64 : (mt * nf >= 16 ? 4 : 8));      // the last arriver re-reads S x (MT x NF) KB at ~65 GB/s: <= 64 KB
+    int s0 = t.rr_slabs > 0 ? t.rr_slabs : (int)std::max<long long>(1, (256 + tiles / 2) / tiles);
+    s0 = std::min(std::min(s0, u0), t.rr_slabs > 0 ? 64 : (mt * nf >= 16 ? 4 : 8));      // the last arriver re-reads S x (MT x NF) KB at ~65 GB/s: <= 64 KB
     while (u0 % s0 != 0) --s0;
     int s1 = 0;
     if (u1 > 0) {
@@ -658,7 +654,7 @@ RrPlan conv_rr_plan(int N, int H, int W, int Cin, int Cout, int taps, int Cs, si
 }
 
 int conv_rr(const RrPlan& pl, const RrIn& in, const RrIn* skip, int taps, const half_t* wf, const float* bias, const half_t* residual, int res_up,
-            half_t* Y, int N, int H, int W, int Cout, float* ws, size_t ws_floats, float* gn_part, int* gn_chunks, hipStream_t s) {
+            half_t* Y, int N, int H, int W, int Cout, float* ws, size_t ws_floats, float* gn_part, hipStream_t s) {
     PD_REQUIRE(pl.variant > 0 && wf != nullptr && Y != nullptr && in.x != nullptr, "conv_rr: no plan / null argument");
     PD_REQUIRE((skip == nullptr) == (pl.S1 == 0), "conv_rr: the plan and the skip source disagree");
     PD_REQUIRE(res_up == 0 || (residual != nullptr && H % 2 == 0 && W % 2 == 0), "conv_rr: an up-sampled residual needs even H, W");
@@ -689,7 +685,6 @@ int conv_rr(const RrPlan& pl, const RrIn& in, const RrIn* skip, int taps, const 
     a.tickets = reinterpret_cast<unsigned*>(ws);
     a.slabs = ws ? ws + PD_SK_TICKET_FLOATS : nullptr;
     a.gn_part = gn_part;
-    if (gn_chunks) *gn_chunks = gn_part ? pl.bands : 0;
     const int grid = (int)(tiles * S);
     int vw = 0, cs = 0, mt = 0, nf = 0;
     PD_REQUIRE(rr_variant(pl.variant, &vw, &mt, &nf, &cs) && vw == W, "conv_rr: variant %d does not serve %d-wide images", pl.variant, W);
@@ -736,11 +731,6 @@ __global__ void k_gn_octet_partials(const pdnn::half_t* __restrict__ X, int HW, 
 #ifdef PD_LAB_RR_STAMP
 extern "C" int pdhip_lab_rr_read_stamps(unsigned long long* host, int n) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(pdnn::g_rr_stamps), sizeof(unsigned long long) * n); }
 #endif
-extern "C" int pdhip_debug_set_conv_rr(int mode, int variant, int slabs) {
-    const int old = pdnn::g_rr_mode;
-    pdnn::g_rr_mode = mode; pdnn::g_rr_variant = variant; pdnn::g_rr_slabs = slabs;
-    return old;
-}
 extern "C" long long pdhip_conv_rr_weight_halfs(int Cin, int taps, int Cs, int Cout) { return (long long)pdnn::conv_rr_weight_halfs(Cin, taps, Cs, Cout); }
 extern "C" int pdhip_conv_rr_pack_f16(const void* w_packed, int Cin, int taps, int Cs, int Cout, void* wf, void* stream) {
     PD_REQUIRE(w_packed && wf, "pdhip_conv_rr_pack_f16: null argument");
@@ -758,7 +748,7 @@ extern "C" int pdhip_gn_apply_parts_f16(const void* x, const void* x2, int Ca, i
     PD_REQUIRE(x && partA && gamma && beta && y, "pdhip_gn_apply_parts_f16: null argument");
     const pdnn::GnPartsArg pa{partA, x2 ? Ca : C, chunksA, partB, x2 ? C - Ca : 0, chunksB, 1e-5f};
     return pdnn::gn_apply((const pdnn::half_t*)x, nullptr, gamma, beta, film, film_stride, N, H, W, C, silu, 0, y, 0, as_stream(stream),
-                          (const pdnn::half_t*)x2, x2 ? Ca : 0, nullptr, &pa);
+                          (const pdnn::half_t*)x2, x2 ? Ca : 0, nullptr, &pa, pdnn::tuning().gn_iters);
 }
 extern "C" int pdhip_conv_rr_f16(const void* x, const void* x2, int C, int Ca, int gn_mode, const float* gamma, const float* beta, const float* film,
                                  long long film_stride, const float* partA, int chunksA, const float* partB, int chunksB, const void* xs,
@@ -766,11 +756,12 @@ extern "C" int pdhip_conv_rr_f16(const void* x, const void* x2, int C, int Ca, i
                                  void* y, int N, int H, int W, int Cout, float* ws, long long ws_floats, float* gn_part, int* gn_chunks,
                                  void* stream) {
     PD_REQUIRE(x && wf && y, "pdhip_conv_rr_f16: null argument");
-    const pdnn::RrPlan pl = pdnn::conv_rr_plan(N, H, W, C, Cout, taps, xs ? Cs : 0, ws ? (size_t)ws_floats : 0, gn_mode != 0);
+    const pdnn::RrPlan pl = pdnn::conv_rr_plan(pdnn::tuning(), N, H, W, C, Cout, taps, xs ? Cs : 0, ws ? (size_t)ws_floats : 0, gn_mode != 0);
     PD_REQUIRE(pl.variant != 0, "pdhip_conv_rr_f16: not a layer for the row-resident kernel (N=%d H=%d W=%d Cin=%d Cout=%d taps=%d Cs=%d)", N, H, W, C, Cout, taps, xs ? Cs : 0);
     pdnn::RrIn in{(const pdnn::half_t*)x, (const pdnn::half_t*)x2, C, x2 ? Ca : C, gn_mode, gamma, beta, film, film_stride, partA, partB, chunksA, chunksB, 1e-5f};
     pdnn::RrIn sk{(const pdnn::half_t*)xs, (const pdnn::half_t*)xs2, Cs, xs2 ? Cs1 : Cs, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 1e-5f};
+    if (gn_chunks) *gn_chunks = gn_part ? pl.bands : 0;
     return pdnn::conv_rr(pl, in, xs ? &sk : nullptr, taps, (const pdnn::half_t*)wf, bias, (const pdnn::half_t*)residual, res_up, (pdnn::half_t*)y, N, H, W,
-                         Cout, ws, ws ? (size_t)ws_floats : 0, gn_part, gn_chunks, as_stream(stream));
+                         Cout, ws, ws ? (size_t)ws_floats : 0, gn_part, as_stream(stream));
 }
 

@@ -569,72 +569,85 @@ extern "C" int pdhip_lab_sk_read_stamps(unsigned long long* host, int n) {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_sk_stamps), sizeof(unsigned long long) * n);
 }
 #endif
-thread_local int g_sk_mode = 1;        // tuning / test hook: 0 = never route to k_conv_sk, 1 = automatic, 2 = every eligible layer
-thread_local int g_sk_tile = 0;        // tuning hook: 0 = automatic, 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 64x32
-thread_local int g_sk_splits = 0;      // tuning hook: >= 1 forces the split factor
-thread_local int g_sk_stages = 0;      // lab hook: LDS stages per K-group (2, 3, 4 where the tile allows); 0 = default
-thread_local int g_sk_kg = 0;          // lab hook: K-groups per workgroup (1, 2, 4; 8 = loader-specialised); 0 = default
-thread_local int g_sk_order = 0;       // lab hook: tile order inside an XCD's run: 0 automatic, 1 pixel tiles fastest, 2 n-tiles fastest
-
 // the plan for one layer; bm == 0: not a layer for this kernel.  Rules read off tools/bench_sk.py tables (profiles/r03_sk_bench.txt):
 //   * a tile shape whose tiles alone fill the chip (>= 224) runs unsplit -- the largest such shape (fewest L2 -> LDS bytes);
 //   * otherwise 3x3 layers are split along K to ~256 workgroups: the largest tile that needs <= 4 slices, else the 64x32 tile with
 //     up to 8 (a tile's slabs are re-read by ONE workgroup: 16 x 8 KB slices cost more than the K loop they shorten);
 //   * 1x1 layers (K loops of 4-32 steps) never split: the combine costs more than their whole loop.
-SkPlan conv_sk_plan(int N, int H, int W, int Cin, int Cout, int Cout_pad, int taps, bool two_source, size_t ws_floats, int k_extra) {
-    SkPlan p{0, 0, 0, 0};
-    if (g_sk_mode == 0 || Cin % 64 != 0 || Cout % 8 != 0 || Cout_pad % 128 != 0 || k_extra % 64 != 0) return p;
+// k_extra > 0: the plan of conv_sk_skip (the default tile configurations only: the lab hooks for stages / K-groups / order belong to conv_sk).
+SkPlan conv_sk_plan(const Tuning& t, int N, int H, int W, int Cin, int Cout, int Cout_pad, int taps, bool two_source, size_t ws_floats, int k_extra) {
+    SkPlan p{0, 0, 0, 0, 0, 0, 0};
+    if (t.sk_mode == 0 || Cin % 64 != 0 || Cout % 8 != 0 || Cout_pad % 128 != 0 || k_extra % 64 != 0) return p;
     const long long M = (long long)N * H * W, hw = (long long)H * W;
     if (M >= (1LL << 31) / 2) return p;
     const int KI = taps * (Cin / 64) + k_extra / 64;      // (k_extra: channels of a skip 1x1 appended to the K loop, conv_sk_skip)
     static const int BMs[4] = {128, 128, 64, 64}, BNs[4] = {128, 64, 64, 32};
     long long tiles[4];
     bool ok[4];
-    for (int t = 0; t < 4; ++t) {
-        tiles[t] = ((M + BMs[t] - 1) / BMs[t]) * (Cout_pad / BNs[t]);
-        ok[t] = hw % BMs[t] == 0 || BMs[t] == 2 * hw;      // a tile is part of one image, or exactly two whole images (fused GroupNorm partials)
+    for (int i = 0; i < 4; ++i) {
+        tiles[i] = ((M + BMs[i] - 1) / BMs[i]) * (Cout_pad / BNs[i]);
+        ok[i] = hw % BMs[i] == 0 || BMs[i] == 2 * hw;      // a tile is part of one image, or exactly two whole images (fused GroupNorm partials)
     }
     int pick = -1, ps = 1;
-    if (g_sk_tile != 0) {
-        pick = g_sk_tile - 1;
+    if (t.sk_tile != 0) {
+        pick = t.sk_tile - 1;
         if (pick < 0 || pick > 3 || !ok[pick]) return p;
-        ps = g_sk_splits >= 1 ? g_sk_splits : 1;
+        ps = t.sk_splits >= 1 ? t.sk_splits : 1;
     } else {
-        if (g_sk_mode != 2 && ok[0] && tiles[0] > 640) return p;   // enough 128x128 tiles: the big-tile kernels own that regime
+        if (t.sk_mode != 2 && ok[0] && tiles[0] > 640) return p;   // enough 128x128 tiles: the big-tile kernels own that regime
         // (long K loops amortise a two-slice combine: 128 tiles of 128x128 x 2 slices beat 256 unsplit 128x64 tiles at K = 9216 --
         // 50 vs 55 us at 16^2 batch 8 -- and lose at K = 4608, 31 vs 29 us at 64^2 batch 1)
         if (taps == 9 && KI >= 128 && ok[0] && tiles[0] >= 112 && tiles[0] < 224) { pick = 0; ps = 2; }
         // (a weight-heavy layer re-reads its 19-38 MB of weights once per PIXEL tile: 64-row tiles double that traffic -- 39 us unsplit
         // on 64x32 tiles against 24 us on 128x64 tiles x 4 slices at the 8^2 level, batch 8)
         const bool heavy = (size_t)Cout_pad * ((size_t)taps * Cin + k_extra) * 2 >= ((size_t)8 << 20) && M >= 256;
-        for (int t = 0; t < 4 && pick < 0; ++t)
-            if (ok[t] && tiles[t] >= 224 && !(heavy && BMs[t] == 64 && (ok[0] || ok[1]))) { pick = t; ps = 1; }
+        for (int i = 0; i < 4 && pick < 0; ++i)
+            if (ok[i] && tiles[i] >= 224 && !(heavy && BMs[i] == 64 && (ok[0] || ok[1]))) { pick = i; ps = 1; }
         if (pick < 0 && taps == 9) {
-            for (int t = 0; t < 4 && pick < 0; ++t) {
-                const int s = (int)((256 + tiles[t] / 2) / std::max<long long>(tiles[t], 1));
-                if (ok[t] && s <= 4) { pick = t; ps = std::max(s, 1); }
+            for (int i = 0; i < 4 && pick < 0; ++i) {
+                const int s = (int)((256 + tiles[i] / 2) / std::max<long long>(tiles[i], 1));
+                if (ok[i] && s <= 4) { pick = i; ps = std::max(s, 1); }
             }
             if (pick < 0 && ok[3]) { pick = 3; ps = (int)std::min<long long>(8, (256 + tiles[3] / 2) / std::max<long long>(tiles[3], 1)); }
         }
         if (pick < 0) {                                    // 1x1: unsplit, the smallest tile the images allow
-            for (int t = 3; t >= 0 && pick < 0; --t) if (ok[t]) pick = t;
+            for (int i = 3; i >= 0 && pick < 0; --i) if (ok[i]) pick = i;
             ps = 1;
         }
         if (pick < 0) return p;
-        if (g_sk_splits >= 1) ps = g_sk_splits;
+        if (t.sk_splits >= 1) ps = t.sk_splits;
     }
     ps = std::max(1, std::min(std::min(ps, std::max(KI / 2, 1)), 64));
     if (ws_floats == 0 || tiles[pick] > 4096) ps = 1;
     while (ps > 1 && (size_t)tiles[pick] * ps * BMs[pick] * BNs[pick] + PD_SK_TICKET_FLOATS > ws_floats) --ps;
     (void)two_source;
     p.bm = BMs[pick]; p.bn = BNs[pick]; p.splits = ps; p.tile_id = pick + 1;
+    // ---- the instance (lab hooks: K-groups t.sk_kg, stages t.sk_stages, order t.sk_order; 0 = the tile's default)
+    const bool skip = k_extra > 0;
+    const long long grid = tiles[pick] * ps;
+    // (lab hook only: sharing the weight slices of the weight-heavy 16^2 / 8^2 layers through one L2 measured no better than the
+    // default order -- the 256 MB Infinity Cache already absorbs the re-reads -- and 18 % worse at 512 tiles; profiles/r03_sk_bench.txt)
+    p.m_fast = !skip && t.sk_order == 1 && (M + p.bm - 1) / p.bm > 1 ? 1 : 0;
+    p.stages = skip ? 0 : t.sk_stages;
+    int kg = skip ? 0 : t.sk_kg;
+    // K-groups: two (four for long unsplit loops of the 64x32 tile) when the launch is ONE round of workgroups -- they are what puts a
+    // second wave on every SIMD; with >= 1.5 rounds co-resident workgroups do that already and the lock-step of the groups only
+    // costs (tools/bench_sk.py, 512 tiles of 128x128: 148 us with one group, 184 with two)
+    // The 128x128 tile takes the loader-specialised form instead (8): 26.2 vs 26.8 us at 128^2 batch 1, 42.4 vs 44.3 at 32^2 batch 8.
+    // (four K-groups exist for the 64x32 tile only: on the 64x64 tile the form needed 138 spilled VGPRs and was never routed)
+    if (kg == 4 && p.tile_id != 4) kg = 2;
+    // (round 5: the 128x128 tile's loader-specialised form runs with EIGHT loader waves -- 12 waves, 133 VGPRs: 26.5 -> 25.7 us at 128^2
+    // batch 1, 43.7 -> 42.2 at 32^2 batch 8, 51.6 -> 50.2 at 16^2 batch 8, profiles/r05_sk_probe.txt)
+    if (kg == 0) kg = grid >= 384 ? 1 : p.tile_id == 1 ? 12 : (p.tile_id == 4 && KI / ps >= 32) ? 4 : 2;
+    if (kg == 12 && p.tile_id > 2) kg = 8;                 // (the 8-loader form exists for the 128-row tiles)
+    p.kg = kg;
     return p;
 }
 
 int conv_sk(const SkPlan& pl, const half_t* X, const half_t* Wt, const float* bias, const half_t* residual, half_t* Y, int N, int H, int W,
             int Cin, int Cout, int Cout_pad, int taps, const half_t* zero_page, hipStream_t s, float* ws, size_t ws_floats, float* gn_part,
-            int* gn_fused, const half_t* X2, int Cin1, int res_up) {
-    PD_REQUIRE(pl.bm > 0 && (taps == 1 || taps == 9), "conv_sk: no plan / bad taps");
+            const half_t* X2, int Cin1, int res_up) {
+    PD_REQUIRE(pl.bm > 0 && pl.kg > 0 && (taps == 1 || taps == 9), "conv_sk: no plan / bad taps");
     PD_REQUIRE(res_up == 0 || (residual != nullptr && H % 2 == 0 && W % 2 == 0), "conv_sk: an up-sampled residual needs even H, W");
     if (X2 == nullptr) Cin1 = Cin;
     PD_REQUIRE(X2 == nullptr || (taps == 1 && Cin1 % 64 == 0 && (Cin - Cin1) % 64 == 0 && Cin1 > 0 && Cin1 < Cin), "conv_sk: bad two-source split");
@@ -645,28 +658,11 @@ int conv_sk(const SkPlan& pl, const half_t* X, const half_t* Wt, const float* bi
     // workspace: [0, 4096) ticket words (zeroed at allocation, self-resetting), then the slabs
     unsigned* tickets = reinterpret_cast<unsigned*>(ws);
     float* slabs = ws ? ws + PD_SK_TICKET_FLOATS : nullptr;
-    if (gn_fused) *gn_fused = gn_part ? std::max((int)(((long long)H * W) / pl.bm), 1) : 0;
-    const int grid = total * pl.splits;
-    // (lab hook only: sharing the weight slices of the weight-heavy 16^2 / 8^2 layers through one L2 measured no better than the
-    // default order -- the 256 MB Infinity Cache already absorbs the re-reads -- and 18 % worse at 512 tiles; profiles/r03_sk_bench.txt)
-    const int m_fast = g_sk_order == 1 && m_tiles > 1 ? 1 : 0;
-#define SK_ARGS grid, s, X, Wt, bias, residual, Y, N, H, W, Cin, Cout, n_tiles, total, zero_page, pl.splits, slabs, tickets, gn_part, X2, Cin1, m_fast, nullptr, nullptr, 0, 0, res_up
-    // (lab hooks: K-groups g_sk_kg, stages g_sk_stages; 0 = the tile's default)
-    int kg = g_sk_kg;
-    const int st = g_sk_stages;
-    // K-groups: two (four for long unsplit loops of the 64x32 tile) when the launch is ONE round of workgroups -- they are what puts a
-    // second wave on every SIMD; with >= 1.5 rounds co-resident workgroups do that already and the lock-step of the groups only
-    // costs (tools/bench_sk.py, 512 tiles of 128x128: 148 us with one group, 184 with two)
-    // The 128x128 tile takes the loader-specialised form instead (8): 26.2 vs 26.8 us at 128^2 batch 1, 42.4 vs 44.3 at 32^2 batch 8.
-    // (four K-groups exist for the 64x32 tile only: on the 64x64 tile the form needed 138 spilled VGPRs and was never routed)
-    if (kg == 4 && pl.tile_id != 4) kg = 2;
-    // (round 5: the 128x128 tile's loader-specialised form runs with EIGHT loader waves -- 12 waves, 133 VGPRs: 26.5 -> 25.7 us at 128^2
-    // batch 1, 43.7 -> 42.2 at 32^2 batch 8, 51.6 -> 50.2 at 16^2 batch 8, profiles/r05_sk_probe.txt)
-    if (kg == 0) kg = grid >= 384 ? 1 : pl.tile_id == 1 ? 12 : (pl.tile_id == 4 && taps * (Cin / 64) / pl.splits >= 32) ? 4 : 2;
+    const int grid = total * pl.splits, kg = pl.kg, st = pl.stages;
+#define SK_ARGS grid, s, X, Wt, bias, residual, Y, N, H, W, Cin, Cout, n_tiles, total, zero_page, pl.splits, slabs, tickets, gn_part, X2, Cin1, pl.m_fast, nullptr, nullptr, 0, 0, res_up
 #define SK_L(T, BM_, BN_, NST_, KG_) launch_sk<T, BM_, BN_, NST_, KG_>(SK_ARGS)
 #define SK_LS(T, BM_, BN_, NST_) launch_sk<T, BM_, BN_, NST_, 1, true>(SK_ARGS)
 #define SK_LS8(T, BM_, BN_, NST_) launch_sk<T, BM_, BN_, NST_, 1, true, 8>(SK_ARGS)
-    if (kg == 12 && pl.tile_id > 2) kg = 8;                // (the 8-loader form exists for the 128-row tiles)
     if (kg == 12) {                                        // loader-specialised, EIGHT loader waves (hook value 12): 128x128 and 128x64 tiles
         if (taps == 9) return pl.tile_id == 1 ? (st == 2 ? SK_LS8(9, 128, 128, 2) : st == 4 ? SK_LS8(9, 128, 128, 4) : SK_LS8(9, 128, 128, 3))
                                               : (st == 3 ? SK_LS8(9, 128, 64, 3) : SK_LS8(9, 128, 64, 4));
@@ -700,11 +696,11 @@ int conv_sk(const SkPlan& pl, const half_t* X, const half_t* Wt, const float* bi
 }
 
 // 3x3 conv (Cin -> Cout) + the ResBlock's skip 1x1 (Cs -> Cout over xs = [XS | XS2]) as ONE K loop; Wt [Cout_pad][9 Cin + Cs], bias summed.
-// The default tile configurations only (the lab hooks for stages / K-groups belong to conv_sk).
+// The default tile configurations only (conv_sk_plan with k_extra = Cs).
 int conv_sk_skip(const SkPlan& pl, const half_t* X, const half_t* Wt, const float* bias, half_t* Y, int N, int H, int W, int Cin, int Cout,
                  int Cout_pad, const half_t* XS, const half_t* XS2, int Cs1, int Cs, const half_t* zero_page, hipStream_t s, float* ws,
-                 size_t ws_floats, float* gn_part, int* gn_fused) {
-    PD_REQUIRE(pl.bm > 0 && XS != nullptr && Cs > 0 && Cs % 64 == 0, "conv_sk_skip: no plan / bad skip source");
+                 size_t ws_floats, float* gn_part) {
+    PD_REQUIRE(pl.bm > 0 && pl.kg > 0 && XS != nullptr && Cs > 0 && Cs % 64 == 0, "conv_sk_skip: no plan / bad skip source");
     if (XS2 == nullptr) Cs1 = Cs;
     PD_REQUIRE(XS2 == nullptr || (Cs1 % 64 == 0 && Cs1 > 0 && Cs1 < Cs), "conv_sk_skip: bad two-source split");
     const long long M = (long long)N * H * W;
@@ -713,11 +709,9 @@ int conv_sk_skip(const SkPlan& pl, const half_t* X, const half_t* Wt, const floa
                "conv_sk_skip: split-K workspace too small");
     unsigned* tickets = reinterpret_cast<unsigned*>(ws);
     float* slabs = ws ? ws + PD_SK_TICKET_FLOATS : nullptr;
-    if (gn_fused) *gn_fused = gn_part ? std::max((int)(((long long)H * W) / pl.bm), 1) : 0;
-    const int grid = total * pl.splits;
-    const int kg = grid >= 384 ? 1 : pl.tile_id == 1 ? 8 : (pl.tile_id == 4 && (9 * (Cin / 64) + Cs / 64) / pl.splits >= 32) ? 4 : 2;
+    const int grid = total * pl.splits, kg = pl.kg;
 #define SKS_ARGS grid, s, X, Wt, bias, nullptr, Y, N, H, W, Cin, Cout, n_tiles, total, zero_page, pl.splits, slabs, tickets, gn_part, nullptr, Cin, 0, XS, XS2, Cs1, Cs
-    if (pl.tile_id == 1) return kg == 8 ? launch_sk<10, 128, 128, 3, 1, true, 8>(SKS_ARGS) : kg == 1 ? launch_sk<10, 128, 128, 2, 1>(SKS_ARGS) : launch_sk<10, 128, 128, 2, 2>(SKS_ARGS);
+    if (pl.tile_id == 1) return kg == 12 ? launch_sk<10, 128, 128, 3, 1, true, 8>(SKS_ARGS) : kg == 1 ? launch_sk<10, 128, 128, 2, 1>(SKS_ARGS) : launch_sk<10, 128, 128, 2, 2>(SKS_ARGS);
     if (pl.tile_id == 2) return kg == 1 ? launch_sk<10, 128, 64, 3, 1>(SKS_ARGS) : launch_sk<10, 128, 64, 3, 2>(SKS_ARGS);
     if (pl.tile_id == 3) return kg == 1 ? launch_sk<10, 64, 64, 4, 1>(SKS_ARGS) : launch_sk<10, 64, 64, 4, 2>(SKS_ARGS);
     return kg == 1 ? launch_sk<10, 64, 32, 4, 1>(SKS_ARGS) : kg == 4 ? launch_sk<10, 64, 32, 3, 4>(SKS_ARGS) : launch_sk<10, 64, 32, 4, 2>(SKS_ARGS);

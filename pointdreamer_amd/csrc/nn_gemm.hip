@@ -556,12 +556,6 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const float* __restrict__
     }
 }
 
-thread_local int g_force_bk = 0;       // tuning hook: 32 / 64 forces the K-step, 0 = automatic
-thread_local int g_force_stages = 0;   // tuning hook: 2 / 3 / 4 LDS stages, 0 = automatic
-thread_local int g_force_splits = 0;   // tuning hook: >= 1 forces the split-K factor, 0 = automatic
-thread_local float* g_dbg_splitk_ws = nullptr; thread_local size_t g_dbg_splitk_floats = 0;   // split-K workspace for the stand-alone conv entry point
-thread_local int g_force_wmw = 0;      // tuning hook, tile geometry: 2 = 128x128/4 waves, 4 = 256x128/8 waves, 8 = 256x256/8 waves, 0 = automatic
-
 template <int TAPS, int BKT, int NSTAGE, int WM, int WN, int TM>
 static int launch_conv(dim3 grid, size_t smem, hipStream_t s, const half_t* X, const half_t* Wt, const float* bias,
                        const half_t* residual, half_t* Y, int N, int H, int W, int Cin, int Cout, int n_tiles, int total,
@@ -583,21 +577,21 @@ const char* conv_kernel_name(ConvKernel k) {
 //   2. rr / sk + skip     the caller wishes the skip 1x1 appended (needs.skip_cs), no halo layer: k_conv_rr, else k_conv_sk
 //   3. rr + in_gn         the caller wishes the in-staging GroupNorm (needs.in_gn) and k_conv_rr has a variant that carries it
 //   4. halo, unsplit      3x3, single source, halo geometry, the tiles alone fill the chip (or tile hook 32 and >= 256 tiles)
-//   5. rr                 fragment-major weights exist, 3x3, single source, no in_up: whatever conv_rr_plan takes (g_rr_* hooks)
-//   6. halo, split        only under the tile hook (g_force_wmw == 32); takes in_up, not res_up
-//   7. ht                 3x3, single source, no forced geometry: conv_ht_routes (g_ht_mode)
-//   8. sk                 no forced geometry: conv_sk_plan (g_sk_* hooks)
-//   9. igemm              everything else; any forced geometry / K-step / stage count / split (g_force_*) other than tile 32 lands here
+//   5. rr                 fragment-major weights exist, 3x3, single source, no in_up: whatever conv_rr_plan takes (t.rr_* hooks)
+//   6. halo, split        only under the tile hook (t.force_wmw == 32); takes in_up, not res_up
+//   7. ht                 3x3, single source, no forced geometry: conv_ht_routes (t.ht_mode)
+//   8. sk                 no forced geometry: conv_sk_plan (t.sk_* hooks)
+//   9. igemm              everything else; any forced geometry / K-step / stage count / split (t.force_*) other than tile 32 lands here
 // A wish the chosen kernel does not absorb (takes_* false) is the caller's to serve with a pass of its own.
-ConvPlan conv_plan(int N, int H, int W, int Cin, int Cout, int Cout_pad, int taps, const ConvNeeds& nd, size_t ws_floats) {
+ConvPlan conv_plan(const Tuning& t, int N, int H, int W, int Cin, int Cout, int Cout_pad, int taps, const ConvNeeds& nd, size_t ws_floats) {
     ConvPlan p;
     p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.Cout_pad = Cout_pad; p.taps = taps;
     const long long hw = (long long)H * W, M = (long long)N * hw;
-    const bool forced = g_force_wmw != 0 || g_force_bk != 0 || g_force_stages != 0 || g_force_splits != 0;
+    const bool forced = t.force_wmw != 0 || t.force_bk != 0 || t.force_stages != 0 || t.force_splits != 0;
     // automatic halo use only when the tiles alone fill the chip: with the chunk split (small-M layers) the halo kernel measures
     // no better than the 128x128 split-K path (tools/bench_splitk.py: 54 vs 51 us at 32x32 / 512 -> 512)
     const bool halo = !nd.two_source && taps == 9 && conv3x3_halo_eligible(N, H, W, Cin, Cout_pad) &&
-                      (g_force_wmw == 32 || (!forced && conv3x3_halo_splits(N, H, W, Cin, Cout, Cout_pad, 0) == 1));
+                      (t.force_wmw == 32 || (!forced && conv3x3_halo_splits(N, H, W, Cin, Cout, Cout_pad, 0) == 1));
     const bool unsplit = halo && conv3x3_halo_splits(N, H, W, Cin, Cout, Cout_pad, ws_floats) == 1;
     const bool strips = W != 256 || H % 4 == 0;
     const bool single3 = taps == 9 && !nd.two_source;
@@ -609,18 +603,19 @@ ConvPlan conv_plan(int N, int H, int W, int Cin, int Cout, int Cout_pad, int tap
         int chunks = 0;
         switch (k) {
         case CONV_HALO:
-            p.splits = conv3x3_halo_launch_splits(N, H, W, Cin, Cout, Cout_pad, part_floats);
+            p.splits = conv3x3_halo_launch_splits(t, N, H, W, Cin, Cout, Cout_pad, part_floats);
+            p.halo_rows = conv3x3_halo_rows(t, H, W);
             chunks = p.splits > 1 ? (hw % 16 == 0 ? (int)(hw / 16) : 0) : (int)(hw / 512);
             p.takes_res_up = unsplit && p.splits == 1 && strips;
             break;
         case CONV_RR: chunks = p.rr.bands; p.takes_res_up = true; break;
-        case CONV_HT: p.slabs = conv_ht_slabs(N, H, W, Cin, Cout_pad, ws_floats); chunks = (int)(hw / 256); p.takes_res_up = true; break;
+        case CONV_HT: p.slabs = conv_ht_slabs(t, N, H, W, Cin, Cout_pad, ws_floats); chunks = (int)(hw / 256); p.takes_res_up = true; break;
         case CONV_SK: chunks = (hw % p.sk.bm == 0 || p.sk.bm == 2 * hw) ? std::max((int)(hw / p.sk.bm), 1) : 0; p.takes_res_up = true; break;
         default: {
-            p.bk = (g_force_bk == 32 || Cin % 64 != 0) ? 32 : 64;
+            p.bk = (t.force_bk == 32 || Cin % 64 != 0) ? 32 : 64;
             // tile geometry: 256x256 (wave tile 128x64: 25 % fewer LDS reads per MFMA, half the L2 traffic) once it still yields
             // at least one workgroup per CU; 128x128 otherwise
-            int geo = g_force_wmw;
+            int geo = t.force_wmw;
             if (geo != 2 && geo != 4 && geo != 8 && geo != 16)
                 geo = (Cout_pad % 256 == 0 && ((M + 255) / 256) * (Cout_pad / 256) >= 256) ? 8 : 2;
             if (geo == 8 && Cout_pad % 256 != 0) geo = 2;
@@ -641,10 +636,17 @@ ConvPlan conv_plan(int N, int H, int W, int Cin, int Cout, int Cout_pad, int tap
                 splits = std::min(std::min((512 + total / 2) / total, KI / 2), cap);
                 while (splits > 1 && (size_t)splits * M * Cout > part_floats) --splits;
             }
-            if (g_force_splits >= 1 && part_floats > 0)
-                splits = (int)std::min<size_t>(std::min(g_force_splits, std::max(KI / 2, 1)), part_floats / ((size_t)M * Cout));
+            if (t.force_splits >= 1 && part_floats > 0)
+                splits = (int)std::min<size_t>(std::min(t.force_splits, std::max(KI / 2, 1)), part_floats / ((size_t)M * Cout));
             if (splits < 1 || nd.two_source) splits = 1;
             p.splits = splits;
+            // 12 = two stages + register-pipelined schedule: the default for the 256x256 tile (+8..16 % over the compiler's schedule)
+            int stages = t.force_stages ? t.force_stages : (p.bk == 64 ? (geo == 8 ? 12 : 2) : 3);
+            const bool pipe = stages == 12 && p.bk == 64 && (geo == 8 || geo == 16);   // written for the 128-row wave tile
+            if (stages == 12) stages = 2;
+            stages = std::min(std::max(stages, 2), 4);
+            while (stages > 2 && (size_t)stages * (bmt + bnt) * p.bk * 2 > 160 * 1024) --stages;
+            p.stages = pipe ? 12 : stages;
             // fused GroupNorm partial statistics: only when a tile never straddles two images (split: from the reduce kernel)
             chunks = splits == 1 ? (hw % bmt == 0 ? (int)(hw / bmt) : 0) : (hw % SK_ROWS == 0 ? (int)(hw / SK_ROWS) : 0);
         }
@@ -658,36 +660,39 @@ ConvPlan conv_plan(int N, int H, int W, int Cin, int Cout, int Cout_pad, int tap
     if (nd.skip_cs > 0 && !halo && taps == 9) {
         p.skip_cs = nd.skip_cs;
         if (nd.have_wf_skip) {
-            p.rr = conv_rr_plan(N, H, W, Cin, Cout, 9, nd.skip_cs, ws_floats);
+            p.rr = conv_rr_plan(t, N, H, W, Cin, Cout, 9, nd.skip_cs, ws_floats);
             if (p.rr.variant != 0) { p.takes_skip = true; return done(CONV_RR); }
         }
-        p.sk = conv_sk_plan(N, H, W, Cin, Cout, Cout_pad, 9, false, ws_floats, nd.skip_cs);
+        p.sk = conv_sk_plan(t, N, H, W, Cin, Cout, Cout_pad, 9, false, ws_floats, nd.skip_cs);
         if (p.sk.bm > 0) { p.takes_skip = true; return done(CONV_SK); }
         p.skip_cs = 0;
     }
     if (nd.in_gn && nd.have_wf && single3) {
-        p.rr = conv_rr_plan(N, H, W, Cin, Cout, 9, 0, ws_floats, true);
+        p.rr = conv_rr_plan(t, N, H, W, Cin, Cout, 9, 0, ws_floats, true);
         if (p.rr.variant != 0) { p.takes_in_gn = true; return done(CONV_RR); }
     }
     p.takes_in_up = nd.in_up && halo && strips;
     if (unsplit) return done(CONV_HALO);
     if (nd.have_wf && single3 && !p.takes_in_up && !unsplit) {
-        p.rr = conv_rr_plan(N, H, W, Cin, Cout, 9, 0, ws_floats);
+        p.rr = conv_rr_plan(t, N, H, W, Cin, Cout, 9, 0, ws_floats);
         if (p.rr.variant != 0) return done(CONV_RR);
     }
     if (halo) return done(CONV_HALO);
-    if (single3 && !forced && conv_ht_routes(N, H, W, Cin, Cout, Cout_pad, ws_floats)) return done(CONV_HT);
+    if (single3 && !forced && conv_ht_routes(t, N, H, W, Cin, Cout, Cout_pad, ws_floats)) return done(CONV_HT);
     if (!forced) {
-        p.sk = conv_sk_plan(N, H, W, Cin, Cout, Cout_pad, taps, nd.two_source, ws_floats);
+        p.sk = conv_sk_plan(t, N, H, W, Cin, Cout, Cout_pad, taps, nd.two_source, ws_floats);
         if (p.sk.bm > 0) return done(CONV_SK);
     }
     return done(CONV_IGEMM);
 }
 
-ConvPlan conv_up2_phase_plan(int N, int H, int W, int Cin, int Cout, int Cout_pad, bool want_gn) {
+ConvPlan conv_up2_phase_plan(const Tuning& t, int N, int H, int W, int Cin, int Cout, int Cout_pad, bool want_gn) {
     ConvPlan p;
     p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.Cout_pad = Cout_pad; p.taps = 9;
     p.kernel = CONV_UP_PHASE; p.want_gn = want_gn;
+    // tile geometry (tuning hook: 8 / 16 force one): 256x256 where the padded Cout allows it, else 256x128 / 4 waves; both run the
+    // register-pipelined schedule
+    p.geo = Cout_pad % 256 != 0 || t.force_wmw == 16 ? 16 : 8;
     p.gn_chunks = want_gn && ((long long)H * W / 4) % 256 == 0 ? (int)((long long)H * W / 256) : 0;   // 4 phases x 256-pixel tiles of the half-resolution image
     return p;
 }
@@ -700,64 +705,49 @@ int splitk_reduce(const float* partial, int splits, long long M, int Cout, const
     return PDHIP_OK;
 }
 
-// the one place a conv kernel is started: p says which, a carries the operands in that kernel's layouts
-int conv_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t s, int* gn_chunks) {
+// the one place a conv kernel is started: p says which and how, a carries the operands in that kernel's layouts
+int conv_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
     const int N = p.N, H = p.H, W = p.W, Cin = p.Cin, Cout = p.Cout, Cout_pad = p.Cout_pad, taps = p.taps;
     const long long hw = (long long)H * W, M = (long long)N * hw;
     float* part_ws = a.ws != nullptr && a.ws_floats > PD_SK_TICKET_FLOATS ? a.ws + PD_SK_TICKET_FLOATS : nullptr;   // behind k_conv_sk's tickets
     const size_t part_floats = part_ws != nullptr ? a.ws_floats - PD_SK_TICKET_FLOATS : 0;
-    int chunks = 0, rc = PDHIP_OK;
+    float* gn_part = p.gn_chunks > 0 ? a.gn_part : nullptr;
     switch (p.kernel) {
     case CONV_HALO:
-        rc = conv3x3_halo(a.X, a.Wt, a.bias, a.residual, a.Y, N, H, W, Cin, Cout, Cout_pad, a.zero_page, s, a.gn_part, &chunks, part_ws, part_floats,
-                          a.apply_table, a.res_up, p.takes_in_up ? 1 : 0);
-        break;
+        return conv3x3_halo(a.X, a.Wt, a.bias, a.residual, a.Y, N, H, W, Cin, Cout, Cout_pad, a.zero_page, s, gn_part, p.splits, p.halo_rows, part_ws, part_floats,
+                            a.apply_table, a.res_up, p.takes_in_up ? 1 : 0);
     case CONV_RR: {
         const RrIn plain{a.X, nullptr, Cin, Cin, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 1e-5f};
         const RrIn skip{a.XS, a.XS2, p.skip_cs, a.XS2 ? a.Cs1 : p.skip_cs, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 1e-5f};
-        rc = conv_rr(p.rr, p.takes_in_gn ? *a.rr_in : plain, p.takes_skip ? &skip : nullptr, 9, a.Wt, a.bias, a.residual, a.res_up, a.Y, N, H, W, Cout,
-                     a.ws, a.ws_floats, a.gn_part, &chunks, s);
-        break;
+        return conv_rr(p.rr, p.takes_in_gn ? *a.rr_in : plain, p.takes_skip ? &skip : nullptr, 9, a.Wt, a.bias, a.residual, a.res_up, a.Y, N, H, W, Cout,
+                       a.ws, a.ws_floats, gn_part, s);
     }
     case CONV_HT:
-        rc = conv_ht(a.X, a.Wt, a.bias, a.residual, a.Y, N, H, W, Cin, Cout, Cout_pad, a.zero_page, s, a.gn_part, &chunks, a.res_up, a.ws, a.ws_floats);
-        break;
-    case CONV_SK: {      // small-M layers (output tiles do not fill the chip): small tiles, deep staging, split-K combined inside the launch
-        float* gnp = (a.gn_part != nullptr && (hw % p.sk.bm == 0 || p.sk.bm == 2 * hw)) ? a.gn_part : nullptr;
-        rc = p.takes_skip ? conv_sk_skip(p.sk, a.X, a.Wt, a.bias, a.Y, N, H, W, Cin, Cout, Cout_pad, a.XS, a.XS2, a.XS2 ? a.Cs1 : p.skip_cs, p.skip_cs,
-                                         a.zero_page, s, a.ws, a.ws_floats, gnp, &chunks)
-                          : conv_sk(p.sk, a.X, a.Wt, a.bias, a.residual, a.Y, N, H, W, Cin, Cout, Cout_pad, taps, a.zero_page, s, a.ws, a.ws_floats, gnp,
-                                    &chunks, a.X2, a.X2 ? a.Cin1 : Cin, a.res_up);
-        break;
-    }
+        return conv_ht(a.X, a.Wt, a.bias, a.residual, a.Y, N, H, W, Cin, Cout, Cout_pad, a.zero_page, s, gn_part, a.res_up, p.slabs, a.ws, a.ws_floats);
+    case CONV_SK:        // small-M layers (output tiles do not fill the chip): small tiles, deep staging, split-K combined inside the launch
+        return p.takes_skip ? conv_sk_skip(p.sk, a.X, a.Wt, a.bias, a.Y, N, H, W, Cin, Cout, Cout_pad, a.XS, a.XS2, a.XS2 ? a.Cs1 : p.skip_cs, p.skip_cs,
+                                           a.zero_page, s, a.ws, a.ws_floats, gn_part)
+                            : conv_sk(p.sk, a.X, a.Wt, a.bias, a.residual, a.Y, N, H, W, Cin, Cout, Cout_pad, taps, a.zero_page, s, a.ws, a.ws_floats, gn_part,
+                                      a.X2, a.X2 ? a.Cin1 : Cin, a.res_up);
     case CONV_UP_PHASE:
-        rc = conv_up2_phase(a.X, a.Wt, a.bias, a.Y, N, H / 2, W / 2, Cin, Cout, Cout_pad, a.zero_page, s, a.gn_part, &chunks);
-        break;
-    case CONV_IGEMM: {
-        const half_t *X = a.X, *Wt = a.Wt, *residual = a.residual, *zero_page = a.zero_page, *X2 = a.X2;
-        const float* bias = a.bias;
-        half_t* Y = a.Y;
-        const int Cin1 = X2 ? a.Cin1 : Cin, bk = p.bk, geo = p.geo, splits = p.splits;
-        PD_REQUIRE(a.res_up == 0, "conv_igemm: an up-sampled residual needs a layer the halo-resident kernel (unsplit), k_conv_rr, k_conv_ht or k_conv_sk takes");
-        const int bmt = geo == 2 ? 128 : 256, bnt = geo == 8 ? 256 : 128;
-        const int m_tiles = (int)((M + bmt - 1) / bmt), n_tiles = Cout_pad / bnt;
-        const int total = m_tiles * n_tiles;
-        float* partial = splits > 1 ? part_ws : nullptr;
-        dim3 grid(total, splits);
-        const bool fuse = a.gn_part != nullptr && splits == 1 && hw % bmt == 0;
-        const bool fuse_sk = a.gn_part != nullptr && splits > 1 && hw % SK_ROWS == 0;   // stats from the reduce kernel
-        chunks = fuse ? (int)(hw / bmt) : fuse_sk ? (int)(hw / SK_ROWS) : 0;
-        float* gnp = fuse ? a.gn_part : nullptr;
-        // 12 = two stages + register-pipelined schedule: the default for the 256x256 tile (+8..16 % over the compiler's schedule)
-        int stages = g_force_stages ? g_force_stages : (bk == 64 ? (geo == 8 ? 12 : 2) : 3);
-        const bool pipe = stages == 12 && bk == 64 && (geo == 8 || geo == 16);   // written for the 128-row wave tile
-        if (stages == 12) stages = 2;
-        if (stages < 2) stages = 2;
-        if (stages > 4) stages = 4;
-        const size_t stage_bytes = (size_t)(bmt + bnt) * bk * 2;
-        while (stages > 2 && stages * stage_bytes > 160 * 1024) --stages;
-        const size_t smem = std::max<size_t>((size_t)stages * stage_bytes, (size_t)bmt * (bnt + 8) * 2);
-        if (pipe) stages = 12;
+        return conv_up2_phase(a.X, a.Wt, a.bias, a.Y, N, H / 2, W / 2, Cin, Cout, Cout_pad, a.zero_page, s, gn_part, p.geo);
+    case CONV_IGEMM: break;
+    }
+    const half_t *X = a.X, *Wt = a.Wt, *residual = a.residual, *zero_page = a.zero_page, *X2 = a.X2;
+    const float* bias = a.bias;
+    half_t* Y = a.Y;
+    const int Cin1 = X2 ? a.Cin1 : Cin, bk = p.bk, geo = p.geo, splits = p.splits, stages = p.stages;
+    PD_REQUIRE(a.res_up == 0, "conv_igemm: an up-sampled residual needs a layer the halo-resident kernel (unsplit), k_conv_rr, k_conv_ht or k_conv_sk takes");
+    PD_REQUIRE((bk == 32 || bk == 64) && (stages == 12 || (stages >= 2 && stages <= 4)) && splits >= 1, "conv_igemm: no plan (bk=%d stages=%d splits=%d)", bk, stages, splits);
+    PD_REQUIRE(splits == 1 || (part_ws != nullptr && (size_t)splits * M * Cout <= part_floats), "conv_igemm: split-K workspace too small");
+    const int bmt = geo == 2 ? 128 : 256, bnt = geo == 8 ? 256 : 128;
+    const int m_tiles = (int)((M + bmt - 1) / bmt), n_tiles = Cout_pad / bnt;
+    const int total = m_tiles * n_tiles;
+    float* partial = splits > 1 ? part_ws : nullptr;
+    dim3 grid(total, splits);
+    float* gnp = splits == 1 ? gn_part : nullptr;          // split: the partials come from the reduce kernel
+    const size_t smem = std::max<size_t>((size_t)(stages == 12 ? 2 : stages) * (bmt + bnt) * bk * 2, (size_t)bmt * (bnt + 8) * 2);
+    int rc;
 #define ARGS grid, smem, s, X, Wt, bias, residual, Y, N, H, W, Cin, Cout, n_tiles, total, zero_page, splits, partial, gnp, X2, Cin1
 #define BY_STAGE(T, B, WM_, WN_, TM_)                                                   \
     (stages == 2 ? launch_conv<T, B, 2, WM_, WN_, TM_>(ARGS) : stages == 3 ? launch_conv<T, B, 3, WM_, WN_, TM_>(ARGS) \
@@ -765,27 +755,23 @@ int conv_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t s, int* gn_chu
 #define BY_STAGE64(T, WM_, WN_, TM_) (stages == 12 ? launch_conv<T, 64, 12, WM_, WN_, TM_>(ARGS) : BY_STAGE(T, 64, WM_, WN_, TM_))
 #define BY_GEO(T, B) (geo == 2 ? BY_STAGE(T, B, 2, 2, 4) : geo == 4 ? BY_STAGE(T, B, 4, 2, 4) : geo == 8 ? BY_STAGE(T, B, 2, 4, 8) : BY_STAGE(T, B, 2, 2, 8))
 #define BY_GEO64(T) (geo == 2 ? BY_STAGE(T, 64, 2, 2, 4) : geo == 4 ? BY_STAGE(T, 64, 4, 2, 4) : geo == 8 ? BY_STAGE64(T, 2, 4, 8) : BY_STAGE64(T, 2, 2, 8))
-        if (taps == 9) rc = (bk == 64) ? BY_GEO64(9) : BY_GEO(9, 32);
-        else rc = (bk == 64) ? BY_GEO64(1) : BY_GEO(1, 32);
+    if (taps == 9) rc = (bk == 64) ? BY_GEO64(9) : BY_GEO(9, 32);
+    else rc = (bk == 64) ? BY_GEO64(1) : BY_GEO(1, 32);
 #undef BY_GEO64
 #undef BY_GEO
 #undef BY_STAGE64
 #undef BY_STAGE
 #undef ARGS
-        if (rc) return rc;
-        if (splits > 1) rc = splitk_reduce(partial, splits, M, Cout, bias, residual, Y, fuse_sk ? a.gn_part : nullptr, H * W, s);
-        else PD_LAUNCH_CHECK();
-        break;
-    }
-    }
-    if (gn_chunks) *gn_chunks = chunks;
-    return rc;
+    if (rc) return rc;
+    if (splits > 1) return splitk_reduce(partial, splits, M, Cout, bias, residual, Y, gn_part, H * W, s);
+    PD_LAUNCH_CHECK();
+    return PDHIP_OK;
 }
 
 // stand-alone form (the C entry points and the kernel tests): plan + launch, a wish the layer's kernel cannot absorb is an error
-int conv_igemm(const half_t* X, const half_t* Wt, const float* bias, const half_t* residual, half_t* Y, int N, int H,
+int conv_igemm(const Tuning& t, const half_t* X, const half_t* Wt, const float* bias, const half_t* residual, half_t* Y, int N, int H,
                int W, int Cin, int Cout, int Cout_pad, int taps, const half_t* zero_page, hipStream_t s, float* splitk_ws,
-               size_t splitk_ws_floats, float* gn_part, int* gn_fused, const half_t* X2, int Cin1, const float* apply_table, int res_up, int in_up) {
+               size_t splitk_ws_floats, float* gn_part, const half_t* X2, int Cin1, const float* apply_table, int res_up, int in_up) {
     PD_REQUIRE(taps == 1 || taps == 9, "conv_igemm: taps must be 1 or 9");
     if (X2 == nullptr) Cin1 = Cin;
     PD_REQUIRE(X2 == nullptr || (taps == 1 && Cin1 > 0 && Cin1 < Cin && Cin1 % 64 == 0 && (Cin - Cin1) % 64 == 0),
@@ -795,12 +781,12 @@ int conv_igemm(const half_t* X, const half_t* Wt, const float* bias, const half_
     if (splitk_ws == nullptr) splitk_ws_floats = 0;
     ConvNeeds nd;
     nd.two_source = X2 != nullptr; nd.in_up = in_up != 0; nd.apply = apply_table != nullptr; nd.want_gn = gn_part != nullptr;
-    const ConvPlan p = conv_plan(N, H, W, Cin, Cout, Cout_pad, taps, nd, splitk_ws_floats);
+    const ConvPlan p = conv_plan(t, N, H, W, Cin, Cout, Cout_pad, taps, nd, splitk_ws_floats);
     PD_REQUIRE(!nd.in_up || p.takes_in_up, "conv_igemm: an up-sampled input needs a layer the halo-resident kernel takes");
     PD_REQUIRE(res_up == 0 || p.takes_res_up, "conv_igemm: an up-sampled residual needs a layer the halo-resident kernel (unsplit), k_conv_ht or k_conv_sk takes");
     PD_REQUIRE(!nd.apply || p.takes_apply, "conv_igemm: an input transform needs a layer the halo-resident kernel takes");
     const ConvArgs a{X, X2, Cin1, Wt, bias, residual, res_up, apply_table, nullptr, nullptr, nullptr, 0, Y, zero_page, splitk_ws, splitk_ws_floats, gn_part};
-    return conv_launch(p, a, s, gn_fused);
+    return conv_launch(p, a, s);
 }
 
 // ---- 3x3 conv of a nearest-x2 up-sampled image as four 2x2 phase convs over the half-resolution image: 4/9 of the MACs.
@@ -832,18 +818,14 @@ bool conv_up2_phase_eligible(int N, int H, int W, int Cin, int Cout, int Cout_pa
            ((long long)N * H * W + 255) / 256 * 4 * (Cout_pad / 128) < (1LL << 30);
 }
 int conv_up2_phase(const half_t* X, const half_t* Wph, const float* bias, half_t* Y, int N, int H, int W, int Cin, int Cout, int Cout_pad,
-                   const half_t* zero_page, hipStream_t s, float* gn_part, int* gn_fused) {
+                   const half_t* zero_page, hipStream_t s, float* gn_part, int geo) {
     PD_REQUIRE(conv_up2_phase_eligible(N, H, W, Cin, Cout, Cout_pad),
                "conv_up2_phase: need Cin %% 64 == 0, Cout %% 8 == 0, padded Cout %% 128 == 0 (Cin=%d Cout=%d pad=%d)", Cin, Cout, Cout_pad);
-    if (((long long)H * W) % 256 != 0) gn_part = nullptr;      // a pixel tile would straddle two images: no fused statistics
-    // tile geometry (tuning hook: 8 / 16 force one): 256x256 where the padded Cout allows it, else 256x128 / 4 waves; both run the
-    // register-pipelined schedule
-    int geo = (g_force_wmw == 8 || g_force_wmw == 16) ? g_force_wmw : 8;
-    if (Cout_pad % 256 != 0) geo = 16;
+    PD_REQUIRE(geo == 16 || (geo == 8 && Cout_pad % 256 == 0), "conv_up2_phase: no plan (geo=%d)", geo);
+    PD_REQUIRE(gn_part == nullptr || ((long long)H * W) % 256 == 0, "conv_up2_phase: a pixel tile would straddle two images: no fused statistics");
     const int bnt = geo == 8 ? 256 : 128;
     const long long M = (long long)N * H * W;
     const int m_tiles = (int)((M + 255) / 256), n_tiles = Cout_pad / bnt, total = m_tiles * 4 * n_tiles;
-    if (gn_fused) *gn_fused = gn_part != nullptr ? 4 * (int)(((long long)H * W) / 256) : 0;
     const size_t smem = std::max<size_t>((size_t)2 * (256 + bnt) * 64 * 2, (size_t)256 * (bnt + 8) * 2);
     dim3 grid(total, 1);
     int rc;

@@ -42,12 +42,14 @@ __global__ __launch_bounds__(256) void k_im2col_in(const float* __restrict__ x, 
     }
 }
 
-int conv_in_3x3(const float* x_nchw, const half_t* Wt, const float* bias, half_t* Y, int N, int H, int W, int Cout, int Cout_pad,
-                half_t* im2col_ws, const half_t* zero_page, hipStream_t s, float* gn_part, int* gn_fused) {
+int conv_in_3x3(const ConvPlan& p, const float* x_nchw, const half_t* Wt, const float* bias, half_t* Y, int N, int H, int W, int Cout, int Cout_pad,
+                half_t* im2col_ws, const half_t* zero_page, hipStream_t s, float* gn_part) {
+    PD_REQUIRE(p.N == N && p.H == H && p.W == W && p.Cin == 32 && p.Cout == Cout && p.Cout_pad == Cout_pad && p.taps == 1, "conv_in_3x3: the plan is of another layer");
     const long long pixels = (long long)N * H * W;
     k_im2col_in<<<(int)std::min<long long>((pixels + 255) / 256, 8192), 256, 0, s>>>(x_nchw, im2col_ws, H, W, pixels);
     PD_LAUNCH_CHECK();
-    return conv_igemm(im2col_ws, Wt, bias, nullptr, Y, N, H, W, 32, Cout, Cout_pad, 1, zero_page, s, nullptr, 0, gn_part, gn_fused);
+    const ConvArgs a{im2col_ws, nullptr, 32, Wt, bias, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, Y, zero_page, nullptr, 0, gn_part};
+    return conv_launch(p, a, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -328,6 +330,9 @@ extern "C" int pdhip_conv_in_f16(const float* x_nchw, const void* Wt, const floa
                                  void* im2col_ws, const void* zero_page, void* stream) {
     PD_REQUIRE(x_nchw && Wt && bias && Y && im2col_ws && zero_page, "pdhip_conv_in_f16: null argument");
     PD_REQUIRE(N >= 1 && H >= 1 && W >= 1 && Cout >= 1, "pdhip_conv_in_f16: N, H, W, Cout must be positive");
-    return pdnn::conv_in_3x3(x_nchw, (const pdnn::half_t*)Wt, bias, (pdnn::half_t*)Y, N, H, W, Cout, Cout_pad, (pdnn::half_t*)im2col_ws, (const pdnn::half_t*)zero_page,
-                             as_stream(stream), nullptr, nullptr);
+    PD_REQUIRE(Cout % 8 == 0 && Cout_pad % 128 == 0 && Cout_pad >= Cout, "conv_igemm: need Cin %% 32 == 0, Cout %% 8 == 0, padded Cout %% 128 == 0 (Cin=%d Cout=%d pad=%d)", 32,
+               Cout, Cout_pad);
+    const pdnn::ConvPlan p = pdnn::conv_plan(pdnn::tuning(), N, H, W, 32, Cout, Cout_pad, 1, pdnn::ConvNeeds(), 0);
+    return pdnn::conv_in_3x3(p, x_nchw, (const pdnn::half_t*)Wt, bias, (pdnn::half_t*)Y, N, H, W, Cout, Cout_pad, (pdnn::half_t*)im2col_ws, (const pdnn::half_t*)zero_page,
+                             as_stream(stream));
 }

@@ -331,10 +331,9 @@ __global__ __launch_bounds__(256) void k_gn_apply(const half_t* __restrict__ X, 
     }
 }
 
-thread_local int g_gn_iters = 0;       // lab hook (pdhip_debug_set_gn_iters): pixels per thread of k_gn_apply, 0 = default
 int gn_apply(const half_t* X, const float* stats, const float* gamma, const float* beta, const float* film,
              long long film_stride, int N, int H, int W, int C, int silu, int resample, void* Y, int out_f32, hipStream_t s,
-             const half_t* XB, int Ca, half_t* Yraw, const GnPartsArg* parts) {
+             const half_t* XB, int Ca, half_t* Yraw, const GnPartsArg* parts, int iters_hook) {
     GnParts gp{nullptr, nullptr, 0, 0, 0, 0, 0.f};
     if (parts != nullptr) {
         PD_REQUIRE(stats == nullptr && parts->partA != nullptr && (C >> 3) <= 256 && ((C / 32) % 8) == 0 && parts->Ca + parts->Cb == C &&
@@ -352,7 +351,7 @@ int gn_apply(const half_t* X, const float* stats, const float* gamma, const floa
     const int opp = C >> 3, pps = max(1, 256 / opp);
     // pixels per thread: GNA_ITERS on the big tensors (constants amortised), fewer on the small ones so that the grid still fills
     // the chip (a 64-pixel 8x8 level with 32 pixels per thread is 8 workgroups walking a serial latency chain)
-    int iters = g_gn_iters > 0 ? g_gn_iters : GNA_ITERS;
+    int iters = iters_hook > 0 ? iters_hook : GNA_ITERS;
     // (with the in-kernel statistics every workgroup pays the re-reduction of its image's partials first: fewer, longer workgroups --
     // 512 against 2 048 is -2.3 % on the batch-1 forward, -1 % at batch 8; tools/time_unet.py)
     const int tgt_blocks = parts != nullptr && N <= 8 ? 512 : 2048;
@@ -604,14 +603,13 @@ __global__ __launch_bounds__(256, 2) void k_gn_skip_w1(const half_t* __restrict_
     __syncthreads();
     gs_epilogue<MI>(acc, gs_smem, bias, SK, m0, tid);
 }
-thread_local int g_gs_variant = 1;     // tuning hook (pdhip_debug_set_gn_skip_variant)
 
 bool gn_skip_eligible(int N, int HW, int Ca, int C, int Cout, int Cout_pad) {
     return Cout == GS_BN && Cout_pad == GS_BN && C % 64 == 0 && Ca % 64 == 0 && Ca > 0 && Ca <= C && ((C / 32) % 8) == 0 && C <= 2048 && HW % GS_BM == 0 && C % 128 == 0;
 }
 
 int gn_skip(const half_t* XA, const half_t* XB, int Ca, int C, const float* stats, const float* gamma, const float* beta, const half_t* Wt,
-            const float* bias, half_t* H0, half_t* SK, int N, int HW, hipStream_t s) {
+            const float* bias, half_t* H0, half_t* SK, int N, int HW, hipStream_t s, int variant) {
     PD_REQUIRE(gn_skip_eligible(N, HW, Ca, C, GS_BN, GS_BN) && (Ca == C || XB != nullptr), "gn_skip: shape not served by the fused kernel");
     static thread_local bool attr_set = false;
     if (!attr_set) {
@@ -620,7 +618,7 @@ int gn_skip(const half_t* XA, const half_t* XB, int Ca, int C, const float* stat
         attr_set = true;
     }
     const long long tiles = (long long)N * HW / GS_BM;
-    if (tiles < 256 && g_gs_variant != 2) k_gn_skip_w1<64><<<(int)(2 * tiles), 256, GS1_SMEM, s>>>(XA, XB, Ca, C, stats, gamma, beta, Wt, bias, H0, SK, HW);
+    if (tiles < 256 && variant != 2) k_gn_skip_w1<64><<<(int)(2 * tiles), 256, GS1_SMEM, s>>>(XA, XB, Ca, C, stats, gamma, beta, Wt, bias, H0, SK, HW);
     else k_gn_skip_w1<128><<<(int)tiles, 256, GS1_SMEM, s>>>(XA, XB, Ca, C, stats, gamma, beta, Wt, bias, H0, SK, HW);
     PD_LAUNCH_CHECK();
     return PDHIP_OK;

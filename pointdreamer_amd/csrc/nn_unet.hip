@@ -32,37 +32,12 @@ struct Act { half_t* p; int C, H, W; const float* gn_part = nullptr; int gn_chun
              int row = -1, rowB = -1; };   // route table only: the rows of the convs that produced p / p2
 
 }  // namespace
-// tuning / test hook (pdhip_debug_set_fuse_gn).  Default 0 = stand-alone GroupNorm-apply passes: MEASURED faster.  The in-conv
-// transform removes 9.4 ms of gn_apply per batch-32 forward but costs the halo conv 23 % (tools/bench_conv.py --apply, lab builds:
-// fetch of the staged pieces -4.5 %, the in-place ds_write_b128 -10 % -- a store occupies the SIMD's LDS path for 13 cycles in
-// front of the fragment reads the MFMAs wait for -- arithmetic -8 %): 76.2 vs 71.4 ms per DDNM step at batch 32.
-namespace pdnn { thread_local int g_fuse_gn = 0; }
-// tuning / test hook (pdhip_debug_set_fold_resample): 1 (default) = the x branch of up / down ResBlocks is never materialised by a
-// k_resample pass: AvgPool2d(2) of the raw input comes out of the GroupNorm-apply kernel that reads the same pixels anyway, the
-// nearest x2 copy is replaced by index arithmetic in the residual read of the consuming conv (unsplit halo layers)
-namespace pdnn { thread_local int g_fold_resample = 1; }
-// tuning / test hook (pdhip_debug_set_fold_skip): 1 (default) = where a channel-changing ResBlock's conv2 runs in k_conv_sk (the small-M
-// layers) the block's skip 1x1 conv is appended to conv2's K loop (one launch, one rounding) instead of a launch of its own + a residual read
-namespace pdnn { thread_local int g_fold_skip = 1; }
-// tuning / test hook (pdhip_debug_set_rr_gn): largest image width at which a ResBlock conv routed to k_conv_rr also applies the GroupNorm (+ FiLM) + SiLU
-// in front of it while staging (no k_gn_apply launch, no normalised tensor; bit-identical).  Default 0 = never -- measured (profiles/r06_rr_gn_ab.txt):
-// stand-alone the 8^2 / 1024-channel conv pays +0.9 us for it (the element map runs under the weight stream) against a ~6 us launch, the 16^2 / 32^2
-// convs +9-10 us (every 16-32-channel tile redoes the map for its whole pixel tile: 100 VALU cycles per element at one wave per SIMD); inside the
-// forward the batch-1 DDNM step is 4.256 ms with it at 8^2 against 4.254-4.268 without, 4.266 at 16^2: no gain, so the two-pass form stays
-namespace pdnn { thread_local int g_rr_gn = 0; }
-// tuning / test hook (pdhip_debug_set_fold_finalize): largest batch at which GroupNorm-apply reduces the conv epilogues' octet
-// partials itself instead of reading the output of a k_gn_finalize_oct launch (0 = never); above that batch the fold is kept for the
-// tensors whose producers left at most g_fold_finalize_chunks chunks per image (the 32^2 ... 8^2 levels: the re-reduction is a few
-// loads per thread against a 5.8 us launch, 2 020 of them per 20 forwards at batch 32)
-namespace pdnn { thread_local int g_fold_finalize = 8; thread_local int g_fold_finalize_chunks = 16; }
-// tuning / test hook (pdhip_debug_set_fuse_skip): 0 = never, 1 (default) = a channel-changing ResBlock whose skip conv is C -> 256 over
-// at least g_fuse_skip_min_tiles pixel tiles (default 1: measured a gain at every batch) runs GroupNorm-apply and the skip 1x1 as ONE
-// pass over its input (k_gn_skip), 2 = always
-namespace pdnn { thread_local int g_fuse_skip = 1; thread_local int g_fuse_skip_min_tiles = 1; }
-// tuning / test hook (pdhip_debug_set_up_phase): the in_layers conv of an up-ResBlock, conv3x3(nearest_x2(h)), as four 2x2 phase convs over the
-// half-resolution h with the coinciding taps summed in the weights (4/9 of the MACs; k_conv_igemm<4>).  0 = never, 1 (default) = where it
-// measured faster than the 9-tap route (wish_up_phase below), 2 = every eligible layer.  Independent of g_fold_resample.
-namespace pdnn { thread_local int g_up_phase = 1; }
+namespace pdnn {
+Tuning& tuning() { static thread_local Tuning t; return t; }
+}
+// the stand-alone conv entry's split-K workspace (pdhip_debug_set_conv_splitk): state, not tuning -- read by the C entry points below only
+static thread_local float* g_dbg_splitk_ws = nullptr;
+static thread_local size_t g_dbg_splitk_floats = 0;
 namespace {
 struct Prof { std::vector<hipEvent_t> ev; std::vector<uint8_t> cls; size_t used = 0; double flops[2] = {0, 0}; bool on = false;
               int period = 1; long long forwards = 0; bool armed = false; };   // cls 0: halo 3x3 conv, 1: attention
@@ -181,6 +156,7 @@ half_t* arena_take(pdhip_unet* u, size_t halfs) {
 struct Act;
 struct Table { std::vector<std::string> name, line; };      // pdhip_unet_route_table: one line per conv of a forward
 struct Ctx { pdhip_unet* u; int N; hipStream_t s; bool dry; const float* film_base; long long film_stride; Table* table;
+             Tuning t;      // the hooks this forward is planned and run under (taken once by the entry point)
              bool go() const { return !dry && table == nullptr; } };   // go: a real forward; dry: the sizing pass; table: planning only (real routing, no launches)
 
 int prof_begin(Ctx& c, double flops, int cls = 0) {
@@ -246,12 +222,13 @@ void table_row(Ctx& c, const std::string& name, const ConvPlan& p, const ConvIn&
     c.table->line.push_back(line);
 }
 
-// one conv, as planned: output (+ partials) from the arena, the launch, and the plan / launcher agreement on the partials left behind
+// one conv, as planned: output (+ partials) from the arena, then the launch
 int run_conv(Ctx& c, const std::string& name, const ConvPlan& p, const ConvW& w, const ConvIn& in, Act* out) {
     *out = Act{nullptr, p.Cout, p.H, p.W};
     out->p = arena_take(c.u, (size_t)c.N * p.H * p.W * p.Cout);
     float* part = p.want_gn ? take_parts(c, p.H, p.W, p.Cout) : nullptr;
-    if (c.table) { table_row(c, name, p, in, out); adopt_parts(out, part, p.gn_chunks); }
+    if (c.table) table_row(c, name, p, in, out);
+    if (!c.dry) adopt_parts(out, part, p.gn_chunks);
     if (!c.go()) return PDHIP_OK;
     PD_REQUIRE(w.have_w && w.have_b, "unet: weights of %s not loaded", name.c_str());
     const ResB* fs = p.takes_skip ? in.skip_w : nullptr;
@@ -264,18 +241,13 @@ int run_conv(Ctx& c, const std::string& name, const ConvPlan& p, const ConvW& w,
     // profile hook (bench.py roofline): the dominant kernel only -- the halo-resident 3x3 conv, unsplit
     const bool booked = p.kernel == CONV_HALO && p.splits == 1;
     if (booked) PD_TRY(prof_begin(c, 2.0 * c.N * p.H * p.W * (double)p.Cout * 9.0 * p.Cin));
-    int chunks = 0;
-    PD_TRY(conv_launch(p, a, c.s, &chunks));
-    if (booked) PD_TRY(prof_end(c));
-    PD_REQUIRE(chunks == p.gn_chunks, "unet: %s: planned for %d partial chunks per image, the %s launcher left %d", name.c_str(), p.gn_chunks,
-               conv_kernel_name(p.kernel), chunks);
-    adopt_parts(out, part, chunks);
-    return PDHIP_OK;
+    PD_TRY(conv_launch(p, a, c.s));
+    return booked ? prof_end(c) : PDHIP_OK;
 }
 ConvPlan plan_conv(const Ctx& c, const Act& x, const ConvW& w, bool want_gn) {      // a conv outside the ResBlocks: nothing to absorb
     ConvNeeds nd;
     nd.two_source = x.p2 != nullptr; nd.want_gn = want_gn; nd.have_wf = w.has_wf;
-    return conv_plan(c.N, x.H, x.W, w.cin, w.cout, w.cout_pad, w.taps, nd, c.u->splitk_floats);
+    return conv_plan(c.t, c.N, x.H, x.W, w.cin, w.cout, w.cout_pad, w.taps, nd, c.u->splitk_floats);
 }
 
 // GroupNorm statistics of x: from the fused conv-epilogue partials when available, else a pass over the tensor
@@ -299,20 +271,20 @@ int run_gn(Ctx& c, const Act& x, const NormW& n, const float* film, long long fi
 #endif
     // small batches: the apply kernel reduces the octet partials itself (no k_gn_finalize_oct launch); large batches: every
     // workgroup re-reducing its image's partials costs more than the 5 us launch it removes
-    if (x.gn_part != nullptr && ((x.C / 32) % 8) == 0 && (x.C >> 3) <= 256 && g_fold_finalize > 0 &&
-        (c.N <= g_fold_finalize || (x.gn_chunks <= g_fold_finalize_chunks && x.gn_chunksB <= g_fold_finalize_chunks))) {
+    if (x.gn_part != nullptr && ((x.C / 32) % 8) == 0 && (x.C >> 3) <= 256 && c.t.fold_finalize > 0 &&
+        (c.N <= c.t.fold_finalize || (x.gn_chunks <= c.t.fold_finalize_chunks && x.gn_chunksB <= c.t.fold_finalize_chunks))) {
         const GnPartsArg pa{x.gn_part, x.Ca, x.gn_chunks, x.gn_partB, x.C - x.Ca, x.gn_chunksB, 1e-5f};
         return gn_apply(x.p, nullptr, n.g, n.b, film, film_stride, c.N, x.H, x.W, x.C, silu, resample, out->p, 0, c.s, x.p2,
-                        x.p2 ? x.Ca : 0, raw_pool, &pa);
+                        x.p2 ? x.Ca : 0, raw_pool, &pa, c.t.gn_iters);
     }
     PD_TRY(run_gn_stats(c, x));
     return gn_apply(x.p, c.u->stats, n.g, n.b, film, film_stride, c.N, x.H, x.W, x.C, silu, resample, out->p, 0, c.s, x.p2, x.p2 ? x.Ca : 0,
-                    raw_pool);
+                    raw_pool, nullptr, c.t.gn_iters);
 }
 
 // GroupNorm (+ FiLM) + SiLU of x, then the conv, in the form the plan took:
 //   takes_apply  statistics -> (A, B) table -> the halo-resident kernel transforms its input tile of the RAW tensor in LDS (nn_conv_halo.hip APPLY)
-//   takes_in_gn  the row-resident kernel normalises the RAW tensor while staging, from the producer's octet partials (nn_conv_rr.hip; see g_rr_gn)
+//   takes_in_gn  the row-resident kernel normalises the RAW tensor while staging, from the producer's octet partials (nn_conv_rr.hip; see Tuning::rr_gn)
 //   neither      a stand-alone GroupNorm-apply pass (with the block's resampling, and AvgPool2d(2) of the raw input into raw_pool), then the conv
 // In the first two the stand-alone pass and its output tensor disappear; all three give the same bits.
 int run_gn_then_conv(Ctx& c, const std::string& name, const ConvPlan& p, const Act& x, const NormW& n, const float* film, long long film_stride,
@@ -348,18 +320,18 @@ struct ResPlan {
     bool skip_conv = false;        // the skip 1x1 runs as a launch of its own (plan: skip)
     ConvPlan c1, c2, skip;         // c1: takes_apply / takes_in_gn / CONV_UP_PHASE / takes_in_up say its form; c2: takes_skip / takes_apply / takes_in_gn
 };
-// the row-resident kernel's in-staging GroupNorm is wished for where it measured a gain (g_rr_gn) and the input carries what it reads
-bool wish_in_gn(const Act& x, const ConvW& w, int W) {
-    if (g_rr_gn <= 0 || W > g_rr_gn || x.p2 != nullptr || x.gn_part == nullptr || x.gn_partB != nullptr || ((x.C / 32) % 8) != 0 || w.cin > 1024 ||
+// the row-resident kernel's in-staging GroupNorm is wished for where it measured a gain (t.rr_gn) and the input carries what it reads
+bool wish_in_gn(const Tuning& t, const Act& x, const ConvW& w, int W) {
+    if (t.rr_gn <= 0 || W > t.rr_gn || x.p2 != nullptr || x.gn_part == nullptr || x.gn_partB != nullptr || ((x.C / 32) % 8) != 0 || w.cin > 1024 ||
         x.C != w.cin) return false;
     const int pps = std::max(1, 256 / (x.C >> 3));
     return (x.gn_chunks + pps - 1) / pps <= PD_RR_MAX_PART_LOADS;
 }
 // the up-ResBlock in_layers conv on the phase kernel?  (H, W: the half-resolution input)
-bool wish_up_phase(int N, const ResB& rb, int H, int W) {
-    if (g_up_phase == 0 || rb.mode != 2 || !rb.c1.has_wph || (H * W) % 256 != 0 ||
+bool wish_up_phase(const Tuning& t, int N, const ResB& rb, int H, int W) {
+    if (t.up_phase == 0 || rb.mode != 2 || !rb.c1.has_wph || (H * W) % 256 != 0 ||
         !conv_up2_phase_eligible(N, H, W, rb.c1.cin, rb.c1.cout, rb.c1.cout_pad)) return false;
-    if (g_up_phase == 2) return true;
+    if (t.up_phase == 2) return true;
     // automatic, by measurement (profiles/up_phase_layers.txt, batch 1 ... 32 x the five up blocks): from 128 tiles (4 phases x 256-pixel tiles x
     // channel tiles) on the phase conv beat the 9-tap route in every case (1.19x at 128 tiles ... 1.94x), at 64 tiles and below it lost (0.23 ... 0.92x:
     // 256 x 256 tiles on a quarter of the CUs)
@@ -368,49 +340,49 @@ bool wish_up_phase(int N, const ResB& rb, int H, int W) {
 }
 // conservative = the sizing pass: every tensor a routing could need is materialised (two-pass GroupNorm, resampled x branch, skip tensor), since
 // the hooks and the batch of a later forward may route differently; it assumes the input carries partials (k_gn_skip's two outputs are the larger form)
-ResPlan plan_res(int N, size_t ws_floats, bool conservative, const Act& x, const ResB& rb) {
+ResPlan plan_res(const Tuning& t, int N, size_t ws_floats, bool conservative, const Act& x, const ResB& rb) {
     ResPlan r;
     const int Ho = rb.mode == 1 ? x.H / 2 : (rb.mode == 2 ? x.H * 2 : x.H), Wo = rb.mode == 1 ? x.W / 2 : (rb.mode == 2 ? x.W * 2 : x.W);
     const bool lean = !conservative;
     // x branch of an up / down block (unet.py:190-195, 237-242: h and x go through the same Upsample / Downsample)
-    const bool fold = g_fold_resample != 0 && lean && x.p2 == nullptr && !rb.has_skip;
+    const bool fold = t.fold_resample != 0 && lean && x.p2 == nullptr && !rb.has_skip;
     r.fold_down = fold && rb.mode == 1;
-    r.fuse_skip = rb.has_skip && rb.mode == 0 && g_fuse_skip != 0 && rb.skip.taps == 1 && x.C == rb.skip.cin &&
+    r.fuse_skip = rb.has_skip && rb.mode == 0 && t.fuse_skip != 0 && rb.skip.taps == 1 && x.C == rb.skip.cin &&
                   gn_skip_eligible(N, x.H * x.W, x.p2 ? x.Ca : x.C, x.C, rb.skip.cout, rb.skip.cout_pad) &&
-                  (g_fuse_skip == 2 || (long long)N * x.H * x.W / 128 >= g_fuse_skip_min_tiles) &&
+                  (t.fuse_skip == 2 || (long long)N * x.H * x.W / 128 >= t.fuse_skip_min_tiles) &&
                   (conservative || (x.gn_part != nullptr && ((x.C / 32) % 8) == 0));
     ConvNeeds n1;
     n1.want_gn = true; n1.have_wf = rb.c1.has_wf;
-    if (lean && !r.fuse_skip && rb.mode == 0 && x.p2 == nullptr) { n1.apply = g_fuse_gn != 0; n1.in_gn = wish_in_gn(x, rb.c1, x.W); }
+    if (lean && !r.fuse_skip && rb.mode == 0 && x.p2 == nullptr) { n1.apply = t.fuse_gn != 0; n1.in_gn = wish_in_gn(t, x, rb.c1, x.W); }
     n1.in_up = fold && rb.mode == 2;       // nearest x2 of the normalised input: index arithmetic in conv1's halo staging, the GroupNorm pass stays at half resolution
-    if (lean && x.p2 == nullptr && !rb.has_skip && wish_up_phase(N, rb, x.H, x.W))
-        r.c1 = conv_up2_phase_plan(N, Ho, Wo, rb.c1.cin, rb.c1.cout, rb.c1.cout_pad, true);   // GroupNorm at half resolution, the x2 lives in the weights
+    if (lean && x.p2 == nullptr && !rb.has_skip && wish_up_phase(t, N, rb, x.H, x.W))
+        r.c1 = conv_up2_phase_plan(t, N, Ho, Wo, rb.c1.cin, rb.c1.cout, rb.c1.cout_pad, true);   // GroupNorm at half resolution, the x2 lives in the weights
     else
-        r.c1 = conv_plan(N, Ho, Wo, rb.c1.cin, rb.c1.cout, rb.c1.cout_pad, 9, n1, ws_floats);
+        r.c1 = conv_plan(t, N, Ho, Wo, rb.c1.cin, rb.c1.cout, rb.c1.cout_pad, 9, n1, ws_floats);
     // conv2 reads h1 = conv1's output; small-M layers: the skip 1x1 rides in its K loop (no launch of its own, no skip tensor, no residual read)
     Act h1{nullptr, rb.cout, Ho, Wo};
     if (r.c1.gn_chunks > 0) { h1.gn_part = x.gn_part ? x.gn_part : reinterpret_cast<const float*>(&r); h1.gn_chunks = r.c1.gn_chunks; h1.Ca = rb.cout; }
     ConvNeeds n2;
     n2.want_gn = true; n2.have_wf = rb.c2.has_wf;
-    if (lean) { n2.apply = g_fuse_gn != 0; n2.in_gn = wish_in_gn(h1, rb.c2, Wo); }
-    if (lean && rb.has_skip && !r.fuse_skip && g_fold_skip != 0 && rb.mode == 0 && rb.has_c2s && rb.skip.taps == 1 &&
+    if (lean) { n2.apply = t.fuse_gn != 0; n2.in_gn = wish_in_gn(t, h1, rb.c2, Wo); }
+    if (lean && rb.has_skip && !r.fuse_skip && t.fold_skip != 0 && rb.mode == 0 && rb.has_c2s && rb.skip.taps == 1 &&
         (x.p2 == nullptr || (x.Ca % 64 == 0 && (x.C - x.Ca) % 64 == 0))) {
         n2.skip_cs = rb.skip.cin;
         n2.have_wf_skip = rb.has_c2s_wf && (x.p2 == nullptr || (x.Ca % 128 == 0 && (x.C - x.Ca) % 128 == 0));
     }
-    r.c2 = conv_plan(N, Ho, Wo, rb.c2.cin, rb.c2.cout, rb.c2.cout_pad, 9, n2, ws_floats);
+    r.c2 = conv_plan(t, N, Ho, Wo, rb.c2.cin, rb.c2.cout, rb.c2.cout_pad, 9, n2, ws_floats);
     r.fold_up = fold && rb.mode == 2 && r.c2.takes_res_up;
     r.skip_conv = rb.has_skip && !r.fuse_skip && !r.c2.takes_skip;
     if (r.skip_conv) {
         ConvNeeds ns;
         ns.two_source = x.p2 != nullptr;
-        r.skip = conv_plan(N, Ho, Wo, rb.skip.cin, rb.skip.cout, rb.skip.cout_pad, rb.skip.taps, ns, ws_floats);
+        r.skip = conv_plan(t, N, Ho, Wo, rb.skip.cin, rb.skip.cout, rb.skip.cout_pad, rb.skip.taps, ns, ws_floats);
     }
     return r;
 }
 
 int run_res(Ctx& c, const Act& x, ResB& rb, Act* out) {
-    const ResPlan r = plan_res(c.N, c.u->splitk_floats, c.dry, x, rb);
+    const ResPlan r = plan_res(c.t, c.N, c.u->splitk_floats, c.dry, x, rb);
     Act h1, xr = x, sk;
     const float* film = c.go() ? c.film_base + rb.emb_off : nullptr;
     if (c.go()) PD_REQUIRE(rb.have_ew && rb.have_eb, "unet: emb_layers of %s not loaded", rb.name.c_str());
@@ -427,7 +399,7 @@ int run_res(Ctx& c, const Act& x, ResB& rb, Act* out) {
         if (c.go()) {
             PD_REQUIRE(rb.n1.have_g && rb.n1.have_b && rb.skip.have_w && rb.skip.have_b, "unet: norm / skip weights of %s not loaded", rb.name.c_str());
             PD_TRY(run_gn_stats(c, x));
-            PD_TRY(gn_skip(x.p, x.p2, x.p2 ? x.Ca : x.C, x.C, c.u->stats, rb.n1.g, rb.n1.b, rb.skip.w, rb.skip.b, h0.p, sk.p, c.N, x.H * x.W, c.s));
+            PD_TRY(gn_skip(x.p, x.p2, x.p2 ? x.Ca : x.C, x.C, c.u->stats, rb.n1.g, rb.n1.b, rb.skip.w, rb.skip.b, h0.p, sk.p, c.N, x.H * x.W, c.s, c.t.gs_variant));
         }
         ConvIn in{&h0};
         in.parts_of = &x; in.note = "gn_skip";
@@ -455,7 +427,7 @@ int run_att(Ctx& c, const Act& x, AttB& ab, Act* out) {
         // profile hook (bench.py roofline.attention): QK^T + PV = 4 T^2 C flop per image (12.18 GFLOP per forward)
         const double T = (double)x.H * x.W;
         PD_TRY(prof_begin(c, 4.0 * c.N * T * T * x.C, 1));
-        PD_TRY(attention(qkv.p, a.p, c.N, x.H * x.W, x.C, c.u->head, c.s, vt));
+        PD_TRY(attention(qkv.p, a.p, c.N, x.H * x.W, x.C, c.u->head, c.s, vt, c.t.attn_nbuf, c.t.attn_qtn, c.t.attn_vt));
         PD_TRY(prof_end(c));
     }
     return run_conv(c, ab.name + ".proj_out", plan_conv(c, a, ab.proj, true), ab.proj, ConvIn{&a, x.p}, out);
@@ -469,17 +441,15 @@ int run_blocks(Ctx& c, std::vector<Block>& blocks, Act* h, const float* x_nchw) 
             const int cpad = ((o.C + 127) / 128) * 128;
             ConvNeeds nd;
             nd.want_gn = true;
-            const ConvPlan p = conv_plan(c.N, o.H, o.W, 32, o.C, cpad, 1, nd, 0);      // the 1x1 conv over the im2col rows conv_in_3x3 launches (no workspace)
+            const ConvPlan p = conv_plan(c.t, c.N, o.H, o.W, 32, o.C, cpad, 1, nd, 0);      // the 1x1 conv over the im2col rows conv_in_3x3 launches (no workspace)
             o.p = arena_take(c.u, (size_t)c.N * o.H * o.W * o.C);
             half_t* col = arena_take(c.u, (size_t)c.N * o.H * o.W * 32);
             float* part = reinterpret_cast<float*>(arena_take(c.u, (size_t)c.N * ((o.H * o.W + 127) / 128) * (o.C / 8) * 2 * 2));
-            if (c.table) { Act in{nullptr, 32, o.H, o.W}; table_row(c, "input_blocks.0.0", p, ConvIn{&in}, &o); adopt_parts(&o, part, p.gn_chunks); }
+            if (c.table) { Act in{nullptr, 32, o.H, o.W}; table_row(c, "input_blocks.0.0", p, ConvIn{&in}, &o); }
+            if (!c.dry) adopt_parts(&o, part, p.gn_chunks);
             if (c.go()) {
                 PD_REQUIRE(c.u->have_win && c.u->have_bin, "unet: input conv not loaded");
-                int chunks = 0;
-                PD_TRY(conv_in_3x3(x_nchw, c.u->w_in, c.u->b_in, o.p, c.N, o.H, o.W, o.C, cpad, col, c.u->zero_page, c.s, part, &chunks));
-                PD_REQUIRE(chunks == p.gn_chunks, "unet: input conv: planned for %d partial chunks per image, the launcher left %d", p.gn_chunks, chunks);
-                adopt_parts(&o, part, chunks);
+                PD_TRY(conv_in_3x3(p, x_nchw, c.u->w_in, c.u->b_in, o.p, c.N, o.H, o.W, o.C, cpad, col, c.u->zero_page, c.s, part));
             }
         } else if (b.kind == 1) {
             PD_TRY(run_res(c, *h, c.u->res[b.idx], &o));
@@ -493,9 +463,10 @@ int run_blocks(Ctx& c, std::vector<Block>& blocks, Act* h, const float* x_nchw) 
 
 // the whole forward; dry = sizing pass (no launches); table != NULL = planning only (real routing, no launches, one line per conv)
 // shared_emb: one precomputed row of ResBlock embeddings [emb_rows] used by every image (t is then ignored), or nullptr
-int forward_impl(pdhip_unet* u, const float* x, const float* t, int N, float* out, hipStream_t s, bool dry,
+// tun: the hooks in force, taken from the calling thread's instance by the entry point
+int forward_impl(const Tuning& tun, pdhip_unet* u, const float* x, const float* t, int N, float* out, hipStream_t s, bool dry,
                  const float* shared_emb = nullptr, int head_ch = 0, Table* table = nullptr) {   // head_ch 3: only eps (out [N,3,H,W]); 0 = all out_ch
-    Ctx c{u, N, s, dry, shared_emb ? shared_emb : u->emb_all, shared_emb ? 0 : u->emb_rows, table};
+    Ctx c{u, N, s, dry, shared_emb ? shared_emb : u->emb_all, shared_emb ? 0 : u->emb_rows, table, tun};
     u->arena_off = 0;
     u->arena_overflow = false;
     if (c.go() && u->prof.on) u->prof.armed = (u->prof.forwards++ % u->prof.period) == 0;      // events around every period-th forward's launches
@@ -677,7 +648,7 @@ extern "C" int pdhip_unet_create(int image_size, int model_channels, int num_res
     if (hipMemset(u->zero_page, 0, 256) != hipSuccess) { set_error("hipMemset failed"); return fail(PDHIP_E_HIP); }
     // ---- workspace (sized by a dry run of the forward at max_batch)
     const size_t S2 = (size_t)image_size * image_size;
-    chk(forward_impl(u, nullptr, nullptr, max_batch, nullptr, nullptr, true));
+    chk(forward_impl(tuning(), u, nullptr, nullptr, max_batch, nullptr, nullptr, true));
     u->arena_bytes = u->arena_off + 4096;
     {
         void* q = nullptr;
@@ -728,7 +699,7 @@ extern "C" int pdhip_unet_route_table(int image_size, int model_channels, int nu
     u.arena = reinterpret_cast<char*>((size_t)1 << 20);      // addresses to tell "has a tensor" from "has none" by; never dereferenced
     u.arena_bytes = ~(size_t)0 >> 1;
     Table table;
-    rc = forward_impl(&u, nullptr, nullptr, N, nullptr, nullptr, false, nullptr, 0, &table);
+    rc = forward_impl(tuning(), &u, nullptr, nullptr, N, nullptr, nullptr, false, nullptr, 0, &table);
     if (rc != PDHIP_OK) return rc;
     std::string all;
     for (const std::string& l : table.line) { all += l; all += '\n'; }
@@ -876,7 +847,7 @@ extern "C" int pdhip_unet_load_tensor(pdhip_unet* u, const char* name_c, const v
 extern "C" int pdhip_unet_forward(pdhip_unet* u, const float* x, const float* t, int N, float* out, void* stream) {
     PD_REQUIRE(u && x && t && out, "pdhip_unet_forward: null argument");
     PD_REQUIRE(N >= 1 && N <= u->max_batch, "pdhip_unet_forward: batch %d outside [1, %d]", N, u->max_batch);
-    return forward_impl(u, x, t, N, out, as_stream(stream), false);
+    return forward_impl(tuning(), u, x, t, N, out, as_stream(stream), false);
 }
 
 // ---- profiling of the dominant kernel (3x3 implicit-GEMM launches) with HIP events on the launch stream
@@ -999,8 +970,9 @@ extern "C" int pdhip_ddnm_sample_keyed(pdhip_unet* u, const float* masked_imgs, 
         PD_TRY(gemv_rows(u->emb_w, u->emb_b, u->steps_silu, u->steps_emb, (int)u->emb_rows, u->ted, n_steps, s));
         u->steps_cached = n_steps;
     }
+    const Tuning tun = tuning();
     for (int k = 0; k < n_steps; ++k) {
-        PD_TRY(forward_impl(u, u->sx, nullptr, N, u->set_, s, false, u->steps_emb + (size_t)k * u->emb_rows, 3));
+        PD_TRY(forward_impl(tun, u, u->sx, nullptr, N, u->set_, s, false, u->steps_emb + (size_t)k * u->emb_rows, 3));
         PD_TRY(ddnm_update(u->sx, u->set_, 3, u->sy, masks, eps_tape ? eps_tape + (size_t)k * n3 : nullptr, seed,
                            (unsigned long long)k + 1, sched.co[k], N, HW, s, quad0));
     }
@@ -1011,13 +983,49 @@ extern "C" int pdhip_ddnm_sample(pdhip_unet* u, const float* masked_imgs, const 
     return pdhip_ddnm_sample_keyed(u, masked_imgs, masks, N, x_T, eps_tape, seed, 0, n_steps, out, stream);
 }
 
+// ---- the tuning / test hooks: every setter writes the calling thread's Tuning (csrc/nn_common.h lists the fields, their values and defaults)
+// and returns the previous value of its (first) field
+static int swap_hook(int& field, int v) { const int old = field; field = v; return old; }
+extern "C" int pdhip_debug_set_conv_tile(int wmw) { return swap_hook(tuning().force_wmw, wmw); }
+extern "C" int pdhip_debug_set_conv_stages(int st) { return swap_hook(tuning().force_stages, st); }
+extern "C" int pdhip_debug_set_conv_bk(int bk) { return swap_hook(tuning().force_bk, bk); }
+extern "C" int pdhip_debug_set_conv_halo_strips(int mode) { return swap_hook(tuning().halo_strips, mode); }
+/* split-K workspace (device floats) for pdhip_conv2d_nhwc_f16 and a forced split factor (0 = automatic) */
+extern "C" int pdhip_debug_set_conv_splitk(void* ws, long long ws_floats, int splits) {
+    g_dbg_splitk_ws = (float*)ws; g_dbg_splitk_floats = ws ? (size_t)ws_floats : 0;
+    if (ws != nullptr && ws_floats >= PD_SK_TICKET_FLOATS) (void)hipMemset(ws, 0, PD_SK_TICKET_FLOATS * sizeof(float));   // k_conv_sk's tickets start at zero
+    return swap_hook(tuning().force_splits, splits);
+}
+extern "C" int pdhip_debug_set_conv_sk(int mode, int tile, int splits) { tuning().sk_tile = tile; tuning().sk_splits = splits; return swap_hook(tuning().sk_mode, mode); }
+extern "C" int pdhip_debug_set_conv_sk_stages(int stages) { return swap_hook(tuning().sk_stages, stages); }
+extern "C" int pdhip_debug_set_conv_sk_kgroups(int kg) { return swap_hook(tuning().sk_kg, kg); }
+extern "C" int pdhip_debug_set_conv_sk_order(int order) { return swap_hook(tuning().sk_order, order); }
+extern "C" int pdhip_debug_set_conv_rr(int mode, int variant, int slabs) { tuning().rr_variant = variant; tuning().rr_slabs = slabs; return swap_hook(tuning().rr_mode, mode); }
+extern "C" int pdhip_debug_set_conv_ht(int mode, int slabs) { tuning().ht_slabs = slabs; return swap_hook(tuning().ht_mode, mode); }
+extern "C" int pdhip_debug_set_fuse_gn(int on) { return swap_hook(tuning().fuse_gn, on); }
+extern "C" int pdhip_debug_set_fold_resample(int on) { return swap_hook(tuning().fold_resample, on); }
+extern "C" int pdhip_debug_set_fold_skip(int on) { return swap_hook(tuning().fold_skip, on); }
+extern "C" int pdhip_debug_set_rr_gn(int max_width) { return swap_hook(tuning().rr_gn, max_width); }
+extern "C" int pdhip_debug_set_fold_finalize(int max_batch) { return swap_hook(tuning().fold_finalize, max_batch); }
+extern "C" int pdhip_debug_set_fold_finalize_chunks(int chunks) { return swap_hook(tuning().fold_finalize_chunks, chunks); }
+extern "C" int pdhip_debug_set_fuse_skip(int mode, int min_tiles) { if (min_tiles > 0) tuning().fuse_skip_min_tiles = min_tiles; return swap_hook(tuning().fuse_skip, mode); }
+extern "C" int pdhip_debug_set_up_phase(int mode) { return swap_hook(tuning().up_phase, mode); }
+extern "C" int pdhip_debug_set_attn(int nbuf, int vt_form, int qtiles) {
+    Tuning& t = tuning();
+    const int old = t.attn_nbuf | (t.attn_vt << 8) | (t.attn_qtn << 16);
+    t.attn_nbuf = nbuf; t.attn_vt = vt_form; t.attn_qtn = qtiles;
+    return old;
+}
+extern "C" int pdhip_debug_set_gn_iters(int iters) { return swap_hook(tuning().gn_iters, iters); }
+extern "C" int pdhip_debug_set_gn_skip_variant(int v) { return swap_hook(tuning().gs_variant, v); }
+
 // ---- stand-alone operators (also the unit-test surface of the kernels)
 extern "C" int pdhip_conv2d_nhwc_f16(const void* x, const void* w_packed, const float* bias, const void* residual, void* y,
                                      int N, int H, int W, int Cin, int Cout, int Cout_pad, int taps, const void* zero_page,
                                      void* stream) {
     PD_REQUIRE(x && w_packed && y && zero_page, "pdhip_conv2d_nhwc_f16: null argument");
-    return conv_igemm((const half_t*)x, (const half_t*)w_packed, bias, (const half_t*)residual, (half_t*)y, N, H, W, Cin, Cout,
-                      Cout_pad, taps, (const half_t*)zero_page, as_stream(stream), pdnn::g_dbg_splitk_ws, pdnn::g_dbg_splitk_floats);
+    return conv_igemm(tuning(), (const half_t*)x, (const half_t*)w_packed, bias, (const half_t*)residual, (half_t*)y, N, H, W, Cin, Cout,
+                      Cout_pad, taps, (const half_t*)zero_page, as_stream(stream), g_dbg_splitk_ws, g_dbg_splitk_floats);
 }
 /* test entry: conv_plan + conv_launch with every operand ConvArgs carries (include/pdhip.h).  What the planned kernel would drop silently is refused. */
 extern "C" int pdhip_debug_conv_launch_nhwc_f16(const void* x, const void* x2, int Cin1, const void* w_packed, const float* bias, const void* residual,
@@ -1040,7 +1048,7 @@ extern "C" int pdhip_debug_conv_launch_nhwc_f16(const void* x, const void* x2, i
     const size_t wsf = ws != nullptr && ws_floats > 0 ? (size_t)ws_floats : 0;
     pdnn::ConvNeeds nd;
     nd.two_source = x2 != nullptr; nd.want_gn = gn_part != nullptr; nd.skip_cs = Cs;
-    const pdnn::ConvPlan p = conv_plan(N, H, W, Cin, Cout, Cout_pad, taps, nd, wsf);
+    const pdnn::ConvPlan p = conv_plan(tuning(), N, H, W, Cin, Cout, Cout_pad, taps, nd, wsf);
     if (kernel) *kernel = (int)p.kernel;
     if (gn_chunks) *gn_chunks = p.gn_chunks;
     PD_REQUIRE(res_up == 0 || p.takes_res_up, "%s: the planned kernel (%s) does not read its residual at half resolution", fn, conv_kernel_name(p.kernel));
@@ -1051,7 +1059,7 @@ extern "C" int pdhip_debug_conv_launch_nhwc_f16(const void* x, const void* x2, i
                "%s: gn_part holds %lld floats, the launch writes %lld", fn, gn_part_floats, (long long)N * p.gn_chunks * (Cout / 8) * 2);
     const pdnn::ConvArgs a{(const half_t*)x, (const half_t*)x2, x2 ? Cin1 : 0, (const half_t*)w_packed, bias, (const half_t*)residual, res_up, nullptr, nullptr,
                            (const half_t*)xs, (const half_t*)xs2, Cs1, (half_t*)y, (const half_t*)zero_page, wsf ? ws : nullptr, wsf, gn_part};
-    return conv_launch(p, a, as_stream(stream), gn_chunks);
+    return conv_launch(p, a, as_stream(stream));
 }
 extern "C" int pdhip_gn_finalize_oct_f32(const float* partA, int Ca, int chunksA, const float* partB, int Cb, int chunksB, int N, int HW, float* stats,
                                          void* stream) {
@@ -1059,33 +1067,6 @@ extern "C" int pdhip_gn_finalize_oct_f32(const float* partA, int Ca, int chunksA
     PD_REQUIRE(partB ? (Cb > 0 && chunksB > 0) : Cb == 0, "pdhip_gn_finalize_oct_f32: partB and Cb / chunksB disagree");
     return gn_finalize_oct(partA, Ca, chunksA, partB, Cb, partB ? chunksB : 0, N, HW, 1e-5f, stats, as_stream(stream));
 }
-/* tuning / test hook: split-K workspace (device floats) for pdhip_conv2d_nhwc_f16 and a forced split factor (0 = automatic) */
-extern "C" int pdhip_debug_set_conv_splitk(void* ws, long long ws_floats, int splits) {
-    int old = pdnn::g_force_splits;
-    pdnn::g_dbg_splitk_ws = (float*)ws; pdnn::g_dbg_splitk_floats = ws ? (size_t)ws_floats : 0; pdnn::g_force_splits = splits;
-    if (ws != nullptr && ws_floats >= PD_SK_TICKET_FLOATS) (void)hipMemset(ws, 0, PD_SK_TICKET_FLOATS * sizeof(float));   // k_conv_sk's tickets start at zero
-    return old;
-}
-/* tuning / test hook of the small-M conv kernel (nn_conv_sk.hip): mode 0 = never, 1 = automatic (default), 2 = every eligible layer;
- * tile 0 = automatic, 1..4 = 128x128 / 128x64 / 64x64 / 64x32; splits 0 = automatic.  Returns the previous mode. */
-extern "C" int pdhip_debug_set_conv_sk(int mode, int tile, int splits) {
-    int old = pdnn::g_sk_mode;
-    pdnn::g_sk_mode = mode; pdnn::g_sk_tile = tile; pdnn::g_sk_splits = splits;
-    return old;
-}
-extern "C" int pdhip_debug_set_conv_sk_stages(int stages) { int old = pdnn::g_sk_stages; pdnn::g_sk_stages = stages; return old; }
-extern "C" int pdhip_debug_set_conv_sk_kgroups(int kg) { int old = pdnn::g_sk_kg; pdnn::g_sk_kg = kg; return old; }
-namespace pdnn { extern thread_local int g_attn_nbuf, g_attn_vt, g_attn_qtn; }
-extern "C" int pdhip_debug_set_attn(int nbuf, int vt_form, int qtiles) {
-    int old = pdnn::g_attn_nbuf | (pdnn::g_attn_vt << 8) | (pdnn::g_attn_qtn << 16);
-    pdnn::g_attn_nbuf = nbuf; pdnn::g_attn_vt = vt_form; pdnn::g_attn_qtn = qtiles;
-    return old;
-}
-extern "C" int pdhip_debug_set_conv_sk_order(int order) { int old = pdnn::g_sk_order; pdnn::g_sk_order = order; return old; }
-/* tuning / test hook: 1 (default) = GroupNorm + SiLU applied inside the consuming halo conv, 0 = stand-alone passes */
-/* tuning / test hook: 1 (default) = up / down ResBlocks never materialise their resampled x branch; 0 = k_resample passes */
-extern "C" int pdhip_debug_set_rr_gn(int max_width) { int old = pdnn::g_rr_gn; pdnn::g_rr_gn = max_width; return old; }
-extern "C" int pdhip_debug_set_up_phase(int mode) { int old = pdnn::g_up_phase; pdnn::g_up_phase = mode; return old; }
 /* stand-alone: the packed 3x3 weights [Cout_pad][9 Cin] f16 -> phase weights [4][Cout_pad][4 Cin] f16 */
 extern "C" int pdhip_pack_conv_up2_phase_f16(const void* w_packed, int Cin, int Cout_pad, void* w_phase, void* stream) {
     PD_REQUIRE(w_packed && w_phase && Cin > 0 && Cout_pad > 0, "pdhip_pack_conv_up2_phase_f16: bad arguments");
@@ -1096,8 +1077,9 @@ extern "C" int pdhip_pack_conv_up2_phase_f16(const void* w_packed, int Cin, int 
 extern "C" int pdhip_conv3x3_up2_phase_nhwc_f16(const void* x, const void* w_phase, const float* bias, void* y, int N, int H, int W, int Cin, int Cout,
                                                 int Cout_pad, const void* zero_page, float* gn_part, void* stream) {
     PD_REQUIRE(x && w_phase && y && zero_page, "pdhip_conv3x3_up2_phase_nhwc_f16: null argument");
+    const pdnn::ConvPlan p = conv_up2_phase_plan(tuning(), N, 2 * H, 2 * W, Cin, Cout, Cout_pad, gn_part != nullptr);
     return conv_up2_phase((const half_t*)x, (const half_t*)w_phase, bias, (half_t*)y, N, H, W, Cin, Cout, Cout_pad, (const half_t*)zero_page,
-                          as_stream(stream), gn_part, nullptr);
+                          as_stream(stream), p.gn_chunks > 0 ? gn_part : nullptr, p.geo);
 }
 /* stand-alone: the same layer on the 9-tap halo-resident kernel reading the half-resolution x with index arithmetic (the route the phase conv
  * replaces; layers that kernel takes unsplit only: 2W in {32 .. 256}) */
@@ -1106,23 +1088,10 @@ extern "C" int pdhip_conv3x3_up2_halo_nhwc_f16(const void* x, const void* w_pack
     PD_REQUIRE(x && w_packed && y && zero_page, "pdhip_conv3x3_up2_halo_nhwc_f16: null argument");
     pdnn::ConvNeeds nd;
     nd.in_up = true;
-    PD_REQUIRE(conv_plan(N, 2 * H, 2 * W, Cin, Cout, Cout_pad, 9, nd, 0).takes_in_up,
+    PD_REQUIRE(conv_plan(tuning(), N, 2 * H, 2 * W, Cin, Cout, Cout_pad, 9, nd, 0).takes_in_up,
                "pdhip_conv3x3_up2_halo_nhwc_f16: not a layer the halo-resident kernel takes unsplit");
-    return conv_igemm((const half_t*)x, (const half_t*)w_packed, bias, nullptr, (half_t*)y, N, 2 * H, 2 * W, Cin, Cout, Cout_pad, 9,
-                      (const half_t*)zero_page, as_stream(stream), nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, 1);
-}
-extern "C" int pdhip_debug_set_fold_skip(int on) { int old = pdnn::g_fold_skip; pdnn::g_fold_skip = on; return old; }
-extern "C" int pdhip_debug_set_fold_resample(int on) { int old = pdnn::g_fold_resample; pdnn::g_fold_resample = on; return old; }
-extern "C" int pdhip_debug_set_fold_finalize_chunks(int chunks) { int old = pdnn::g_fold_finalize_chunks; pdnn::g_fold_finalize_chunks = chunks; return old; }
-extern "C" int pdhip_debug_set_fold_finalize(int max_batch) { int old = pdnn::g_fold_finalize; pdnn::g_fold_finalize = max_batch; return old; }
-namespace pdnn { extern thread_local int g_gs_variant; }
-/* lab hook: 0 = two workgroups per CU, loads one MFMA phase ahead; 1 (default) = one workgroup per CU, activation chunks three K-steps ahead */
-extern "C" int pdhip_debug_set_gn_skip_variant(int v) { int old = pdnn::g_gs_variant; pdnn::g_gs_variant = v; return old; }
-extern "C" int pdhip_debug_set_fuse_skip(int mode, int min_tiles) {
-    int old = pdnn::g_fuse_skip;
-    pdnn::g_fuse_skip = mode;
-    if (min_tiles > 0) pdnn::g_fuse_skip_min_tiles = min_tiles;
-    return old;
+    return conv_igemm(tuning(), (const half_t*)x, (const half_t*)w_packed, bias, nullptr, (half_t*)y, N, 2 * H, 2 * W, Cin, Cout, Cout_pad, 9,
+                      (const half_t*)zero_page, as_stream(stream), nullptr, 0, nullptr, nullptr, 0, nullptr, 0, 1);
 }
 /* stand-alone: h0 = silu(GroupNorm32(x)) and sk = conv1x1(x) (C -> 256) in one pass over x = [xa | xb] (xb NULL: single tensor, Ca == C);
  * stats [N][32][2] (mean, rstd) of x finished by the caller.  C % 256 == 0, Ca % 64 == 0, H * W % 128 == 0. */
@@ -1131,9 +1100,8 @@ extern "C" int pdhip_gn_silu_skip1x1_nhwc_f16(const void* xa, const void* xb, in
                                               int W, void* stream) {
     PD_REQUIRE(xa && stats && gamma && beta && w_packed && h0 && sk, "pdhip_gn_silu_skip1x1_nhwc_f16: null argument");
     return gn_skip((const half_t*)xa, (const half_t*)xb, Ca, C, stats, gamma, beta, (const half_t*)w_packed, bias, (half_t*)h0, (half_t*)sk,
-                   N, H * W, as_stream(stream));
+                   N, H * W, as_stream(stream), tuning().gs_variant);
 }
-extern "C" int pdhip_debug_set_fuse_gn(int on) { int old = pdnn::g_fuse_gn; pdnn::g_fuse_gn = on; return old; }
 /* stand-alone: y = conv3x3( silu( GroupNorm32(x) [* (1 + scale) + shift] ) ) (+ residual) with the transform applied inside the
  * conv (halo-resident kernel; W in {32, 64, 128, 256}, H * W % 512 == 0, Cin % 32 == 0).  ws: N*64 + N*64*ceil(HW/256) + N*Cin*2 floats. */
 extern "C" int pdhip_gn_silu_conv3x3_nhwc_f16(const void* x, const float* gamma, const float* beta, const float* film,
@@ -1149,21 +1117,20 @@ extern "C" int pdhip_gn_silu_conv3x3_nhwc_f16(const void* x, const float* gamma,
     PD_TRY(gn_stats((const half_t*)x, N, H * W, Cin, 1e-5f, stats, ws + (size_t)N * 64, gws, s));
     PD_TRY(gn_table(stats, gamma, beta, film, film_stride, N, Cin, table, s));
     // (the debug split-K workspace is shared with pdhip_conv2d_nhwc_f16, whose k_conv_sk route keeps its tickets in the first words)
-    float* hws = pdnn::g_dbg_splitk_ws != nullptr && pdnn::g_dbg_splitk_floats > PD_SK_TICKET_FLOATS ? pdnn::g_dbg_splitk_ws + PD_SK_TICKET_FLOATS : nullptr;
+    float* hws = g_dbg_splitk_ws != nullptr && g_dbg_splitk_floats > PD_SK_TICKET_FLOATS ? g_dbg_splitk_ws + PD_SK_TICKET_FLOATS : nullptr;
+    const size_t hws_floats = hws ? g_dbg_splitk_floats - PD_SK_TICKET_FLOATS : 0;
+    PD_REQUIRE(conv3x3_halo_eligible(N, H, W, Cin, Cout_pad) && N > 0 && Cout > 0 && Cout_pad > 0, "conv3x3_halo: unsupported geometry (N=%d H=%d W=%d Cin=%d)", N, H, W, Cin);
     return conv3x3_halo((const half_t*)x, (const half_t*)w_packed, bias, (const half_t*)residual, (half_t*)y, N, H, W, Cin, Cout,
-                        Cout_pad, (const half_t*)zero_page, s, nullptr, nullptr, hws, hws ? pdnn::g_dbg_splitk_floats - PD_SK_TICKET_FLOATS : 0, table);
+                        Cout_pad, (const half_t*)zero_page, s, nullptr, conv3x3_halo_launch_splits(tuning(), N, H, W, Cin, Cout, Cout_pad, hws_floats),
+                        conv3x3_halo_rows(tuning(), H, W), hws, hws_floats, table);
 }
 /* tuning hook: the APPLY conv on a ready-made (A, B) table [N][Cin/8][16] (tools/bench_conv.py --apply) */
 extern "C" int pdhip_debug_conv3x3_apply(const void* x, const float* table, const void* w_packed, const float* bias, const void* residual,
                                          void* y, int N, int H, int W, int Cin, int Cout, int Cout_pad, const void* zero_page, void* stream) {
     PD_REQUIRE(x && table && w_packed && y && zero_page, "pdhip_debug_conv3x3_apply: null argument");
     return conv3x3_halo((const half_t*)x, (const half_t*)w_packed, bias, (const half_t*)residual, (half_t*)y, N, H, W, Cin, Cout,
-                        Cout_pad, (const half_t*)zero_page, as_stream(stream), nullptr, nullptr, nullptr, 0, table);
+                        Cout_pad, (const half_t*)zero_page, as_stream(stream), nullptr, 1, conv3x3_halo_rows(tuning(), H, W), nullptr, 0, table);
 }
-extern "C" int pdhip_debug_set_conv_tile(int wmw) { int old = pdnn::g_force_wmw; pdnn::g_force_wmw = wmw; return old; }
-extern "C" int pdhip_debug_set_conv_stages(int st) { int old = pdnn::g_force_stages; pdnn::g_force_stages = st; return old; }
-/* tuning / test hook: force the conv K-step (32 or 64; 0 = automatic). Returns the previous value. */
-extern "C" int pdhip_debug_set_conv_bk(int bk) { int old = pdnn::g_force_bk; pdnn::g_force_bk = bk; return old; }
 extern "C" int pdhip_pack_conv_weight_f16(const float* w_oihw, int Cout, int Cin, int taps, void* w_packed, void* stream) {
     PD_REQUIRE(w_oihw && w_packed, "pdhip_pack_conv_weight_f16: null argument");
     k_pack_conv<<<grid_for((long long)Cout * Cin * taps), 256, 0, as_stream(stream)>>>(w_oihw, 0, Cout, Cin, taps, (half_t*)w_packed);
@@ -1175,7 +1142,8 @@ extern "C" int pdhip_groupnorm_nhwc_f16(const void* x, const float* gamma, const
                                         float* ws, long long ws_floats, void* stream) {
     PD_REQUIRE(x && gamma && beta && y && stats_ws && ws, "pdhip_groupnorm_nhwc_f16: null argument");
     PD_TRY(gn_stats((const half_t*)x, N, H * W, C, 1e-5f, stats_ws, ws, (size_t)ws_floats, as_stream(stream)));
-    return gn_apply((const half_t*)x, stats_ws, gamma, beta, film, 2LL * C, N, H, W, C, silu, resample, y, 0, as_stream(stream));
+    return gn_apply((const half_t*)x, stats_ws, gamma, beta, film, 2LL * C, N, H, W, C, silu, resample, y, 0, as_stream(stream), nullptr, 0, nullptr, nullptr,
+                    tuning().gn_iters);
 }
 // output head on its own: GroupNorm(32) statistics + the fused GN -> SiLU -> conv3x3 kernel (f32-equivalent arithmetic)
 extern "C" size_t pdhip_unet_head_ws_floats(int N, int H, int W, int C, int Cout) {
@@ -1199,7 +1167,8 @@ extern "C" int pdhip_unet_head_f32(const void* x, const float* gamma, const floa
 }
 extern "C" int pdhip_attention_f16(const void* qkv, void* out, int N, int T, int C, int head_dim, void* vt_ws, void* stream) {
     PD_REQUIRE(qkv && out, "pdhip_attention_f16: null argument");
-    return attention((const half_t*)qkv, (half_t*)out, N, T, C, head_dim, as_stream(stream), (half_t*)vt_ws);
+    const Tuning& t = tuning();
+    return attention((const half_t*)qkv, (half_t*)out, N, T, C, head_dim, as_stream(stream), (half_t*)vt_ws, t.attn_nbuf, t.attn_qtn, t.attn_vt);
 }
 extern "C" int pdhip_philox_normal(float* out, long long n, uint64_t seed, uint64_t stream_id, void* stream) {
     PD_REQUIRE(out && n > 0, "pdhip_philox_normal: bad arguments");
@@ -1208,7 +1177,6 @@ extern "C" int pdhip_philox_normal(float* out, long long n, uint64_t seed, uint6
 extern "C" int pdhip_bench_copy16(const void* src, void* dst, long long bytes, int blocks, int unroll, void* stream) {
     return copy16(src, dst, bytes, blocks, unroll, as_stream(stream));
 }
-extern "C" int pdhip_debug_set_gn_iters(int iters) { const int old = g_gn_iters; g_gn_iters = iters; return old; }
 // ---- the GroupNorm-apply pass and its neighbours on their own (csrc/nn_norm.hip): unit-test surface, nothing the product calls
 extern "C" int pdhip_gn_apply_f16(const void* x, const void* x2, int Ca, int C, const float* stats, const float* partA, int chunksA,
                                   const float* partB, int chunksB, const float* gamma, const float* beta, const float* film,
@@ -1223,10 +1191,10 @@ extern "C" int pdhip_gn_apply_f16(const void* x, const void* x2, int Ca, int C, 
     if (partA != nullptr) {
         const GnPartsArg pa{partA, x2 ? Ca : C, chunksA, partB, x2 ? C - Ca : 0, chunksB, 1e-5f};
         return gn_apply((const half_t*)x, nullptr, gamma, beta, film, film_stride, N, H, W, C, silu, resample, y, 0, as_stream(stream),
-                        (const half_t*)x2, x2 ? Ca : 0, (half_t*)y_raw, &pa);
+                        (const half_t*)x2, x2 ? Ca : 0, (half_t*)y_raw, &pa, tuning().gn_iters);
     }
     return gn_apply((const half_t*)x, stats, gamma, beta, film, film_stride, N, H, W, C, silu, resample, y, 0, as_stream(stream),
-                    (const half_t*)x2, x2 ? Ca : 0, (half_t*)y_raw, nullptr);
+                    (const half_t*)x2, x2 ? Ca : 0, (half_t*)y_raw, nullptr, tuning().gn_iters);
 }
 extern "C" int pdhip_gn_table_f32(const float* stats, const float* gamma, const float* beta, const float* film, long long film_stride, int N, int C,
                                   float* table, void* stream) {

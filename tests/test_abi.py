@@ -204,3 +204,25 @@ def test_unet_route_table_follows_the_hooks():
             changed = {block(r) for r in base if hit(r)}     # the blocks whose rows the hook touches
             assert [r for r in off if block(r) not in changed] == [r for r in base if block(r) not in changed]
             assert _routes(N) == base                        # restored
+
+
+def test_unet_route_table_under_every_hook_matches_the_recorded_digests():
+    """Production config at batch 1, 2, 8, 32 with every routing / fold hook flipped alone to each of its documented non-default values
+    (nn_hooks_common.ROUTE_SETTINGS): row count and SHA-256 of each table equal tests/golden/unet_route_table_hooks.txt, recorded from the build
+    before the hooks became one Tuning struct handed to the planners (tools/gen_route_table_hooks.py writes the file and prints a full table).
+    Every hook is restored in a finally (nn_hooks_common.hook); the last step is the default table again."""
+    import __graft_entry__ as ge
+    ge.build()
+    import nn_hooks_common as nh
+    want = {}
+    for line in open(os.path.join(ROOT, 'tests', 'golden', 'unet_route_table_hooks.txt')):
+        label, n, rows, sha = line.split()
+        want[(label, int(n[2:]))] = (int(rows[5:]), sha[7:])
+    settings = [('default', None, ())] + nh.ROUTE_SETTINGS
+    assert set(want) == {(label, N) for label, _, _ in settings for N in nh.ROUTE_BATCHES} and len(settings) == 29
+    default = {N: nh.route_table_lines('default', None, (), N) for N in nh.ROUTE_BATCHES}
+    for label, setter, args in settings:
+        for N in nh.ROUTE_BATCHES:
+            assert nh.route_table_digest(nh.route_table_lines(label, setter, args, N)) == want[(label, N)], (label, N)
+    for N in nh.ROUTE_BATCHES:
+        assert nh.route_table_lines('default', None, (), N) == default[N], N      # every hook is back at its default

@@ -14,6 +14,7 @@ import torch
 import torch.nn.functional as F
 
 import nn_ops_common as oc
+from nn_hooks_common import hook
 from conftest import load_golden, note_measured, U1_FP32_LINF, U1_FP32_L2, U1_SMALL_FP32_LINF, U1_SMALL_FP32_L2
 from oracle import unet as ounet, ddnm as oddnm
 
@@ -179,10 +180,10 @@ def test_attention_vs_torch(nn, N, T, Cc, D):
     # K / V chunks requested one or two iterations ahead; V read with the LDS transpose read or from a transposed workspace:
     # the same operands in the same order -> the same bits
     for nbuf, vt_form, qt in ((2, 0, 0), (3, 0, 1), (2, 1, 2), (3, 1, 0), (3, 0, 2), (0, 0, 0)):
-        L.pdhip_debug_set_attn(nbuf, vt_form, qt)
-        out2.zero_()
-        assert L.pdhip_attention_f16(_ptr(qd), _ptr(out2), N, T, Cc, D, _ptr(vt), _stream()) == 0, L.pdhip_last_error()
-        outs.append(out2.clone())
+        with hook('attn', nbuf, vt_form, qt):
+            out2.zero_()
+            assert L.pdhip_attention_f16(_ptr(qd), _ptr(out2), N, T, Cc, D, _ptr(vt), _stream()) == 0, L.pdhip_last_error()
+            outs.append(out2.clone())
     for o_ in outs[1:]:
         assert torch.equal(outs[0], o_)
     o = out.float().cpu().permute(0, 2, 1)
@@ -377,8 +378,8 @@ def test_conv3x3_halo_kernel_vs_torch_fp32(nn, N, H, W, Cin, Cout, res, splits):
     inside an image, several images, odd / single channel-chunk counts, residual, and the split over channel chunks (f32
     partials + fixed-order reduce) used by small-M layers."""
     L = nn['L']
-    old = L.pdhip_debug_set_conv_tile(32)
     ws = torch.empty((max(splits, 1) * N * H * W * Cout,), device=DEV)
+    old = L.pdhip_debug_set_conv_tile(32)
     L.pdhip_debug_set_conv_splitk(_ptr(ws), ws.numel(), splits)
     try:
         g = torch.Generator().manual_seed(N * 1000 + H * W + Cin + Cout)

@@ -151,9 +151,9 @@ def test_conv_sk_small_m_kernel_vs_torch_fp32(nn, N, H, W, Cin, Cout, k, res, ti
     b = torch.randn((Cout,), generator=g).half().float()
     r = torch.randn((N, Cout, H, W), generator=g).half().float() if res else None
     ws = torch.empty((4096 + 64 * 4096 * 16,), dtype=torch.float32, device=DEV)
+    ref = F.conv2d(x, w, b, padding=k // 2) + (r if res else 0)
     L.pdhip_debug_set_conv_splitk(_ptr(ws), ws.numel(), 0)
     old = L.pdhip_debug_set_conv_sk(2 if tile else 1, tile, splits)
-    ref = F.conv2d(x, w, b, padding=k // 2) + (r if res else 0)
     try:
         for kg in (0, 1, 2, 4, 8, 12):              # K-groups per workgroup (4-wave groups on alternate K-steps of one tile); 8 = loader-specialised, 12 = with eight loader waves
             L.pdhip_debug_set_conv_sk_kgroups(kg)

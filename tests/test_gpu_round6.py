@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import load_golden, note_measured, U1_FP32_LINF, U1_FP32_L2
+from nn_hooks_common import hook
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -379,18 +380,17 @@ def test_conv_ht_vs_torch_fp32(nn, N, HW, Cin, Cout, res, slabs):
     rd = r.to(DEV) if r is not None else None
     ws = torch.zeros((4096 + 4 * 1024 * 1024,), dtype=torch.float32, device=DEV)
     ws[4096:] = float('nan')
-    old = L.pdhip_debug_set_conv_ht(2, slabs)
     outs = []
-    for _ in range(2):
-        y = torch.full((N, H, W, Cout), float('nan'), dtype=torch.float16, device=DEV)
-        part = torch.full((N * (H * W // 256) * (Cout // 8) * 2,), float('nan'), dtype=torch.float32, device=DEV)
-        ch = C.c_int(-1)
-        rc = L.pdhip_conv_ht_f16(_ptr(xd), _ptr(wp), _ptr(bd), _ptr(rd), 1 if res == 2 else 0, _ptr(y), N, H, W, Cin, Cout, pad, _ptr(zp), _ptr(ws), ws.numel(),
-                                 _ptr(part), C.byref(ch), _stream())
-        assert rc == 0, L.pdhip_last_error()
-        torch.cuda.synchronize()
-        outs.append((y, part))
-    L.pdhip_debug_set_conv_ht(old, 0)
+    with hook('conv_ht', 2, slabs):
+        for _ in range(2):
+            y = torch.full((N, H, W, Cout), float('nan'), dtype=torch.float16, device=DEV)
+            part = torch.full((N * (H * W // 256) * (Cout // 8) * 2,), float('nan'), dtype=torch.float32, device=DEV)
+            ch = C.c_int(-1)
+            rc = L.pdhip_conv_ht_f16(_ptr(xd), _ptr(wp), _ptr(bd), _ptr(rd), 1 if res == 2 else 0, _ptr(y), N, H, W, Cin, Cout, pad, _ptr(zp), _ptr(ws),
+                                     ws.numel(), _ptr(part), C.byref(ch), _stream())
+            assert rc == 0, L.pdhip_last_error()
+            torch.cuda.synchronize()
+            outs.append((y, part))
     assert int(ws[:4096].abs().sum().item()) == 0
     if slabs > 1 or (slabs == 0 and (N, HW, Cin, Cout) == (1, 64, 512, 512)):
         assert not torch.isnan(ws[4096:4096 + 16384]).any(), "the split form must have been taken"
