@@ -708,6 +708,33 @@ int pdhip_debug_set_mesh_contains_slabs(int slabs);   /* 0 (default): the column
  * Q == 0: zeros.  PDHIP_E_ARG: Q < 0 or > 2^26, a null pointer (named). */
 int pdhip_occupancy_iou(const uint8_t* a, const uint8_t* b, int Q, int64_t* out, void* stream);
 
+/* ---- point-to-mesh distance (csrc/mesh_distance.hip; models/POCO/eval/src/eval.py: distance_p2m, i.e. trimesh.proximity.closest_point).
+ * pdhip_closest_on_mesh: for every point the closest point of the mesh's surface, its squared distance and the face.  vertices [Vn,3] f32, faces [F,3]
+ * i64, points [Q,3] f32 on the device, all widened to f64; every operation below is one f64 operation (no FMA, / correctly rounded).  With
+ * dot(u,v) = (u.x v.x + u.y v.y) + u.z v.z, the closest point x of triangle (a, b, c) to q is Ericson's region walk:
+ *   ab = b - a, ac = c - a, bc = c - b;  d1 = dot(ab, q - a), d2 = dot(ac, q - a);  d3 = dot(ab, q - b), d4 = dot(ac, q - b);  d5 = dot(ab, q - c),
+ *   d6 = dot(ac, q - c);  vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4, e43 = d4 - d3, e56 = d5 - d6;  the first case that holds:
+ *   1. d1 <= 0 and d2 <= 0: a;   2. d3 >= 0 and d4 <= d3: b;   3. vc <= 0, d1 >= 0, d3 <= 0: a + (d1 / (d1 - d3)) ab;   4. d6 >= 0 and d5 <= d6: c;
+ *   5. vb <= 0, d2 >= 0, d6 <= 0: a + (d2 / (d2 - d6)) ac;   6. va <= 0, e43 >= 0, e56 >= 0: b + (e43 / (e43 + e56)) bc;
+ *   7. otherwise, den = 1 / ((va + vb) + vc): (a + ab (vb den)) + ac (vc den).
+ * The face's value is dot(q - x, q - x).  A face whose normal ab x ac (each component a difference of two products) is exactly (0, 0, 0) contributes
+ * nothing; a face whose value is NaN never wins.  d2[q] is the minimum over the remaining faces, face[q] the SMALLEST index that attains it, closest[q]
+ * (f64 [Q,3], or NULL: not wanted) that face's x; a point for which no face has a value gets d2 = +inf, face = -1, closest = NaN.  A per-face value
+ * depends on no other face, so the result equals the all-pairs evaluation bit for bit on every path, depends on the order of neither the points nor
+ * (apart from the index that wins a tie) the faces, and two calls give equal bytes (no floating-point atomics).  counts (device [4]): queries
+ * certified by the ring scan over the cell list of the small faces, queries finished by the staged scan of all faces, faces on the large list (scanned
+ * by every query: faces that span more than two cells of the grid on an axis, and slivers), degenerate faces skipped; counts[0] + counts[1] == Q.
+ * ws: pdhip_closest_on_mesh_workspace_bytes(Vn, F, Q) device bytes, a function of (F, Q) alone (0 for sizes the entry refuses).  PDHIP_E_ARG with the
+ * cause, and d2 / face / closest / counts untouched: a null pointer (named), Vn < 1, F == 0 or every face degenerate ("degenerate"), F > 2^23
+ * (pdhip_simplify_mesh's limit), Q < 0 or > 2^26 (pdhip_nearest_points' limit), a face index outside [0, Vn), a non-finite referenced vertex or point.
+ * An unreferenced vertex, finite or not, changes nothing.  Q == 0: PDHIP_OK, counts zeroed, the mesh still validated.  The read of the bounding box
+ * and of the counts of bad inputs SYNCHRONISES the stream once (96 bytes).  (The size query is not called ..._ws_bytes: tests/test_ws_bytes_cpu.py
+ * fixes the set of queries with that suffix.) */
+size_t pdhip_closest_on_mesh_workspace_bytes(int Vn, int F, int Q);
+int pdhip_closest_on_mesh(const float* vertices, int Vn, const int64_t* faces, int F, const float* points, int Q, double* d2, int32_t* face,
+                          double* closest, int32_t* counts, void* ws, void* stream);
+int pdhip_debug_set_closest_on_mesh(int cells_per_axis, int path);   /* test hook; same results under every setting.  cells_per_axis 0 (default): the grid's cells per axis follow F (sqrt(F / 32), at most 96); 1 .. 96: that many.  path 0 (default); 1: every live face on the large list; 2: every query to the all-faces scan.  Returns 4 * (previous cells_per_axis) + previous path */
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,9 @@ _SIGS = {
     'pdhip_mesh_contains': (C.c_int, [vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp]),
     'pdhip_debug_set_mesh_contains_slabs': (C.c_int, [i32]),
     'pdhip_occupancy_iou': (C.c_int, [vp, vp, i32, vp, vp]),
+    'pdhip_closest_on_mesh_workspace_bytes': (sz, [i32, i32, i32]),
+    'pdhip_closest_on_mesh': (C.c_int, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
+    'pdhip_debug_set_closest_on_mesh': (C.c_int, [i32, i32]),
     'pdhip_rescale_vertices': (C.c_int, [vp, i32, i32, vp, vp, vp, f64, vp]),
     'pdhip_optimize_color_ws_bytes': (sz, [i32, i32, i32]),
     'pdhip_optimize_color': (C.c_int, [vp, i32, vp, vp, i32, i32, vp, i32, vp, f64, i32, vp, vp, vp]),

@@ -8,6 +8,9 @@ distance_p2p, get_threshold_percentage) with the reference's names, keys and arg
   check_mesh_contains(vertices, faces, points, hash_resolution) -> bool [Q]: the reference's point-in-mesh test
                                        (eval/src/utils/libmesh/inside_mesh.py; pdhip_mesh_contains, csrc/occupancy.hip)
   compute_iou(occ1, occ2)           -> the volumetric intersection over union of two occupancy arrays (eval/src/common.py:6-33)
+  closest_on_mesh(vertices, faces, points) -> (d2 [Q] float64, face [Q] int32[, closest [Q,3] float64]): the exact closest point of the surface
+                                       (trimesh.proximity.closest_point; pdhip_closest_on_mesh, csrc/mesh_distance.hip)
+  distance_p2m(points, vertices, faces) -> sqrt(d2) [Q] float64 (eval.py:195-202 with the mesh as (vertices, faces))
 
 Completeness is target -> prediction, accuracy is prediction -> target, each the mean over the points of its source cloud; the
 normal entries are means of |n_src . n_tgt[nearest]| of the normalised normals; F = 2 P R / (P + R) with P / R the share of
@@ -19,8 +22,11 @@ Coordinates are float32 on the device (the reference casts the sampled cloud to 
 for containment at the points and compared with the ground-truth occupancies, which sample_colored_pc_from_mesh.sample_occupancy_batch
 writes in the reference's .npz layout.  Without them the key is absent from the result.
 
-Not built: `remove_wall` (eval.py:48-69, a scene-dataset crop) and `distance_p2m` (unused by the reference).  CPU tensors raise
-PdhipError: there is no CPU path."""
+eval_mesh(..., p2m=True) adds the completeness measured against the predicted SURFACE instead of its samples: 'completeness-p2m',
+'completeness2-p2m' and 'normals completeness-p2m' are the mean distance, the mean squared distance and the mean |n_tgt . n_face| from the target
+cloud to the mesh (distance_p2m's primitive, reduced by the same kernels with the faces in the place of the sampled points).
+
+Not built: `remove_wall` (eval.py:48-69, a scene-dataset crop).  CPU tensors raise PdhipError: there is no CPU path."""
 import math
 
 import numpy as np
@@ -67,8 +73,8 @@ def cloud_sums(d2, idx, normals_src, normals_tgt, M, thresholds, out_sums, out_w
     T = thresholds.shape[0]
     ws = torch.empty((max(int(L.pdhip_cloud_metrics_workspace_bytes(T)), 8),), dtype=torch.uint8, device=d2.device)
     check(L.pdhip_cloud_metrics(ptr(d2, torch.float64), ptr(idx, torch.int32), d2.shape[0], ptr(normals_src, torch.float32, allow_none=True),
-                                ptr(normals_tgt, torch.float32, allow_none=True), M, ptr(thresholds, torch.float64), T, ptr(out_sums),
-                                ptr(out_within), ptr(ws), stream()), 'pdhip_cloud_metrics')
+                                ptr(normals_tgt, torch.float32, allow_none=True), M, ptr(thresholds, torch.float64) if T else ptr(None, allow_none=True),
+                                T, ptr(out_sums), ptr(out_within, allow_none=True), ptr(ws), stream()), 'pdhip_cloud_metrics')
 
 
 def eval_pointcloud(pointcloud, pointcloud_tgt, normals=None, normals_tgt=None, thresholds=DEFAULT_THRESHOLDS):
@@ -148,13 +154,7 @@ def check_mesh_contains(vertices, faces, points, hash_resolution=512, return_cou
     v = _cloud(vertices, 'vertices')
     dev = v.device
     p = _cloud(points, 'points', dev)
-    if isinstance(faces, np.ndarray):
-        faces = torch.from_numpy(np.ascontiguousarray(faces)).to(dev)
-    if not (torch.is_tensor(faces) and faces.is_cuda):
-        raise _lib.PdhipError("geometry_metrics: expected faces on the GPU; pointdreamer_amd has no CPU path")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"faces must be [F, 3], got {tuple(faces.shape)}")
-    f = faces.detach().to(torch.int64).contiguous()
+    f = _faces(faces, dev)
     Vn, F, Q, R = v.shape[0], f.shape[0], p.shape[0], int(hash_resolution)
     occ = torch.zeros((Q,), dtype=torch.uint8, device=dev)
     counts = torch.zeros((4,), dtype=torch.int32, device=dev)
@@ -163,6 +163,79 @@ def check_mesh_contains(vertices, faces, points, hash_resolution=512, return_cou
     check(L.pdhip_mesh_contains(opt(v), Vn, opt(f), F, opt(p), Q, R, opt(occ), ptr(counts), ptr(ws), stream()), 'pdhip_mesh_contains')
     occ = occ.view(torch.bool)
     return (occ, counts) if return_counts else occ
+
+
+def _faces(faces, dev):
+    """[F,3] int64 contiguous on the GPU (a numpy array follows `dev`)."""
+    if isinstance(faces, np.ndarray):
+        faces = torch.from_numpy(np.ascontiguousarray(faces)).to(dev)
+    if not (torch.is_tensor(faces) and faces.is_cuda):
+        raise _lib.PdhipError("geometry_metrics: expected faces on the GPU; pointdreamer_amd has no CPU path")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces must be [F, 3], got {tuple(faces.shape)}")
+    return faces.detach().to(torch.int64).contiguous()
+
+
+def closest_on_mesh(vertices, faces, points, return_closest=False, return_counts=False):
+    """trimesh.proximity.closest_point -> (d2 [Q] float64, face [Q] int32[, closest [Q,3] float64][, counts]) on the device: the squared distance
+    of every point to the surface, the face that attains it (the smallest index on a tie) and the closest point of that face (include/pdhip.h has
+    the definition; the result equals its all-pairs evaluation bit for bit).  vertices [Vn,3] on the GPU, faces [F,3] and points [Q,3] on the GPU
+    or numpy arrays, which follow the device of `vertices`.  counts: the int32 [4] tensor (queries certified by the ring scan, queries finished by
+    the scan of all faces, faces on the large list, degenerate faces skipped)."""
+    L = _lib.lib()
+    v = _cloud(vertices, 'vertices')
+    dev = v.device
+    p = _cloud(points, 'points', dev)
+    f = _faces(faces, dev)
+    Vn, F, Q = v.shape[0], f.shape[0], p.shape[0]
+    d2 = torch.empty((Q,), dtype=torch.float64, device=dev)
+    face = torch.empty((Q,), dtype=torch.int32, device=dev)
+    closest = torch.empty((Q, 3), dtype=torch.float64, device=dev) if return_closest else None
+    counts = torch.zeros((4,), dtype=torch.int32, device=dev)
+    ws = torch.empty((max(int(L.pdhip_closest_on_mesh_workspace_bytes(Vn, F, Q)), 8),), dtype=torch.uint8, device=dev)   # (0: the entry refuses the sizes)
+    opt = lambda x: ptr(x) if x is not None and x.numel() else ptr(None, allow_none=True)
+    check(L.pdhip_closest_on_mesh(opt(v), Vn, opt(f), F, opt(p), Q, opt(d2), opt(face), opt(closest), ptr(counts), ptr(ws), stream()),
+          'pdhip_closest_on_mesh')
+    out = (d2, face)
+    if return_closest:
+        out += (closest,)
+    if return_counts:
+        out += (counts,)
+    return out
+
+
+def distance_p2m(points, vertices, faces):
+    """eval.py:195-202 with the mesh as (vertices, faces) -> float64 [Q] on the device: the distance of every point to the surface."""
+    return torch.sqrt(closest_on_mesh(vertices, faces, points)[0])
+
+
+def face_normals(vertices, faces):
+    """cross(b - a, c - a) of every face in float64 torch ops, cast to float32 [F,3] (not normalised: pdhip_cloud_metrics normalises in f64)."""
+    tri = vertices.to(torch.float64)[faces]
+    return torch.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=1).to(torch.float32).contiguous()
+
+
+P2M_KEYS = ('completeness-p2m', 'completeness2-p2m', 'normals completeness-p2m')
+
+
+def completeness_p2m(vertices, faces, pointcloud_tgt, normals_tgt):
+    """{'completeness-p2m', 'completeness2-p2m', 'normals completeness-p2m'}: target cloud -> predicted mesh, reduced by pdhip_cloud_metrics with
+    idx = face, M = F and the face normals as the targets' normals.  ONE device -> host copy."""
+    v = _cloud(vertices, 'vertices')
+    dev = v.device
+    f = _faces(faces, dev)
+    tgt = _cloud(pointcloud_tgt, 'pointcloud_tgt', dev)
+    n_tgt = _cloud(normals_tgt, 'normals_tgt', dev) if normals_tgt is not None else None
+    if n_tgt is not None and n_tgt.shape[0] != tgt.shape[0]:
+        raise ValueError(f"normals_tgt {tuple(n_tgt.shape)} does not match pointcloud_tgt {tuple(tgt.shape)}")
+    d2, face = closest_on_mesh(v, f, tgt)
+    sums = torch.zeros((4,), dtype=torch.float64, device=dev)
+    cloud_sums(d2, face, n_tgt, face_normals(v, f) if n_tgt is not None else None, f.shape[0], torch.zeros((0,), dtype=torch.float64, device=dev),
+               sums, None)
+    s = sums.cpu().tolist()                                        # the one device -> host copy
+    n = tgt.shape[0]
+    return {'completeness-p2m': s[0] / n, 'completeness2-p2m': s[1] / n,
+            'normals completeness-p2m': s[2] / n if n_tgt is not None else float('nan')}
 
 
 def iou_from_counts(intersection, union):
@@ -214,19 +287,26 @@ def _occ_tgt(occ_tgt, Q, dev):
 
 
 def eval_mesh(vertices, faces, pointcloud_tgt, normals_tgt, n_points=100000, seed=0, rand=None, thresholds=DEFAULT_THRESHOLDS,
-              points_iou=None, occ_tgt=None):
+              points_iou=None, occ_tgt=None, p2m=False):
     """eval.py:37-89 without `remove_wall`: the scores of n_points samples of the mesh, their face normals as the prediction's normals.  A mesh
     without vertices or faces scores as the empty cloud.  With points_iou [Q,3] and occ_tgt (their ground-truth occupancies, [Q] or the
-    np.packbits form of the .npz) the result gains 'iou' (0. for an empty mesh, eval.py:86-87); without them the key is absent."""
+    np.packbits form of the .npz) the result gains 'iou' (0. for an empty mesh, eval.py:86-87); without them the key is absent.  p2m: the result
+    gains P2M_KEYS, the completeness against the surface itself (completeness_p2m; the empty cloud's constants for an empty mesh), at the price of
+    one more device -> host copy."""
     with_iou = points_iou is not None and occ_tgt is not None
     if vertices.shape[0] == 0 or faces.shape[0] == 0:
         out = eval_pointcloud(np.empty((0, 3)), pointcloud_tgt, np.empty((0, 3)), normals_tgt, thresholds)
         if with_iou:
             out['iou'] = 0.
+        if p2m:
+            out.update({'completeness-p2m': EMPTY_PCL_DICT['completeness'], 'completeness2-p2m': EMPTY_PCL_DICT['completeness2'],
+                        'normals completeness-p2m': EMPTY_PCL_DICT_NORMALS['normals completeness']})
         return out
     coords, nrm = sample_mesh_cloud(vertices, faces, n_points, seed, rand)
     out = eval_pointcloud(coords, pointcloud_tgt, nrm, normals_tgt, thresholds)
     if with_iou:
         occ = check_mesh_contains(vertices, faces, points_iou)
         out['iou'] = compute_iou(occ, _occ_tgt(occ_tgt, occ.shape[0], occ.device))
+    if p2m:
+        out.update(completeness_p2m(vertices, faces, pointcloud_tgt, normals_tgt))
     return out

@@ -8,7 +8,9 @@ Every <cls_id>/<shape_name>/models/model_normalized.obj under the prediction roo
 sample_colored_pc_from_mesh writes.  One line per shape, then the mean over the shapes; the result also goes to
 `<parent of pred root>/<time>_geometry_eval_result.txt`.  A shape without ground truth is a FileNotFoundError that names it.
 With `--points_root_path <data_root>/point` every shape that has <cls_id>/<shape_name>.npz there (points + packed occupancies, written by
-`sample_colored_pc_from_mesh --occupancy`) is also scored by the volumetric IoU: an `iou` column, its mean over the shapes that have one."""
+`sample_colored_pc_from_mesh --occupancy`) is also scored by the volumetric IoU: an `iou` column, its mean over the shapes that have one.
+With `--p2m` every shape is also scored by the completeness of the ground-truth cloud against the predicted SURFACE (geometry_metrics.P2M_KEYS:
+mean distance, mean squared distance, normal consistency): three more columns and their means."""
 import argparse
 import os
 import time
@@ -23,16 +25,18 @@ KEYS = ('chamfer-L1', 'chamfer-L2', 'completeness', 'accuracy', 'normals', 'f-sc
 MESH = os.path.join('models', 'model_normalized.obj')
 
 
-def eval(pred_root_path, gt_root_path, n_points=100000, seed=0, device=None, points_root_path=None):
+def eval(pred_root_path, gt_root_path, n_points=100000, seed=0, device=None, points_root_path=None, p2m=False):
     """Returns dict(per_shape={name: the twelve scores}, mean={key: mean over the shapes}, sample_num, result_file).  points_root_path
     (<data_root>/point, what sample_colored_pc_from_mesh --occupancy writes): a shape with <cls_id>/<shape_name>.npz there is also scored
-    by `iou`, and the mean of that column runs over those shapes (NaN when there is none)."""
+    by `iou`, and the mean of that column runs over those shapes (NaN when there is none).  p2m: the three point-to-mesh completeness scores as well."""
     device = device if device is not None else torch.device('cuda')
     names = [n for n in shape_names(pred_root_path) if os.path.exists(os.path.join(pred_root_path, n, MESH))]
     if not names:
         raise FileNotFoundError(f'no <cls_id>/<shape_name>/{MESH} under {pred_root_path}')
     per_shape = {}
     shown = KEYS + ('iou',) if points_root_path is not None else KEYS
+    if p2m:
+        shown = shown + geometry_metrics.P2M_KEYS
     print('shape\t' + '\t'.join(shown))
     for name in names:
         gt = [os.path.join(gt_root_path, name, f) for f in ('coords.npy', 'normals.npy')]
@@ -47,7 +51,7 @@ def eval(pred_root_path, gt_root_path, n_points=100000, seed=0, device=None, poi
             with np.load(occ_file) as z:
                 iou_args = dict(points_iou=z['points'].astype(np.float32), occ_tgt=z['occupancies'])
         r = geometry_metrics.eval_mesh(torch.from_numpy(vertices).to(device), torch.from_numpy(faces).to(device), coords, normals,
-                                       n_points=n_points, seed=seed, **iou_args)
+                                       n_points=n_points, seed=seed, p2m=p2m, **iou_args)
         per_shape[name] = r
         print(name + '\t' + '\t'.join(repr(float(r.get(k, float('nan')))) for k in shown))
     keys = list(next(iter(per_shape.values())))
@@ -80,8 +84,10 @@ def main(argv=None):
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--points_root_path", type=str, default=None,
                    help="<data_root>/point: <cls_id>/<shape>.npz with points + occupancies (sample_colored_pc_from_mesh --occupancy) -> the iou column")
+    p.add_argument("--p2m", action="store_true",
+                   help="also the completeness of the ground-truth cloud against the predicted surface itself (point to mesh): three more columns")
     args = p.parse_args(argv)
-    return eval(args.pred_root_path, args.gt_root_path, args.n_points, args.seed, points_root_path=args.points_root_path)
+    return eval(args.pred_root_path, args.gt_root_path, args.n_points, args.seed, points_root_path=args.points_root_path, p2m=args.p2m)
 
 
 if __name__ == '__main__':
