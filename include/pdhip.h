@@ -735,6 +735,33 @@ int pdhip_closest_on_mesh(const float* vertices, int Vn, const int64_t* faces, i
                           double* closest, int32_t* counts, void* ws, void* stream);
 int pdhip_debug_set_closest_on_mesh(int cells_per_axis, int path);   /* test hook; same results under every setting.  cells_per_axis 0 (default): the grid's cells per axis follow F (sqrt(F / 32), at most 96); 1 .. 96: that many.  path 0 (default); 1: every live face on the large list; 2: every query to the all-faces scan.  Returns 4 * (previous cells_per_axis) + previous path */
 
+/* ---- farthest-point subsampling (csrc/subsample.hip; no reference counterpart: demo.py:371-374 refuses clouds above 30 000 points).
+ * pdhip_fps: M of the N points, each the farthest from those picked before it.  points [N,3] f32 on the device, widened to f64;
+ * d2(i, j) = (dx*dx + dy*dy) + dz*dz with dx = xi - xj, op by op (pdhip_nearest_points' convention).  idx[0] = start, min_d2[0] = +inf; after pick k every
+ * unselected point i has mind[i] = min over the picks so far of d2(i, pick); pick k + 1 is the unselected point with the largest mind, of those the
+ * SMALLEST original index, and min_d2[k + 1] is that value.  A selected point is never selected again, also when mind is 0 everywhere (duplicates).
+ * So min_d2[1:] never increases, and the first m picks of a run with M picks are the run with m picks.  idx (device [M] i32), min_d2 (device [M] f64)
+ * equal the brute-force scan bit for bit: a cell list over the points' box prunes by a lower bound that never exceeds a member's computed d2.  Two calls
+ * give equal bytes (no floating-point atomics).  counts (device [4]): cells per axis of the grid, occupied cells, point updates performed over all
+ * picks (the brute-force scan performs N * M; saturates at 2^31 - 1), 0.  The pick loop runs in ONE workgroup (no cooperative launch, no barrier
+ * across workgroups).  ws: pdhip_fps_workspace_bytes(N, M) device bytes, a function of N alone (0 for sizes the entry refuses).  PDHIP_E_ARG with the cause, and idx / min_d2 /
+ * counts untouched: a null pointer (named), N < 1 or > 2^24, M < 1 or > N, start outside [0, N), a non-finite coordinate.  The read of the bounding
+ * box and of the non-finite count SYNCHRONISES the stream once (32 bytes).  (The size query is not called ..._ws_bytes: tests/test_ws_bytes_cpu.py
+ * fixes the set of queries with that suffix.) */
+size_t pdhip_fps_workspace_bytes(int N, int M);
+int pdhip_fps(const float* points, int N, int M, int start, int32_t* idx, double* min_d2, int32_t* counts, void* ws, void* stream);
+/* pdhip_owner_mean_colors: the mean colour of the points each sample owns (a box filter over the subsample's Voronoi cells).  owner [N] i32 in [0, M):
+ * the position in the selection of the sample nearest to point i (pdhip_nearest_points(points, N, points[idx], M)); colors [N,3] f32 in [0, 1];
+ * fallback, out [M,3] f32; all on the device.  Per sample and channel sum = sum of llrint(c * 2^32) (c widened to f64) over its points, an int64 built
+ * with integer atomics, and their count; out = (f32)(((f64)sum / (f64)count) / 2^32).  A sample that owns nothing (a duplicate of an earlier sample)
+ * takes fallback.  Exact, independent of the order of the points, equal bytes on repeats.  ws_or_null: pdhip_owner_mean_colors_workspace_bytes(M) device
+ * bytes, or NULL: the entry allocates and frees its own, and synchronises once more.  PDHIP_E_ARG with the cause, and out untouched: a null pointer
+ * (named), N < 0 or > 2^26, M < 1 or > 2^26, an owner outside [0, M), a colour outside [0, 1] or non-finite.  The read of the two counts of bad inputs
+ * SYNCHRONISES the stream once (8 bytes). */
+int pdhip_debug_set_fps_cells(int cells_per_axis);   /* tuning / test hook; same results under every setting.  0 (default): the grid's cells per axis follow N (cbrt(N / 32), at most 40); 1 .. 40: that many (1: every pick updates every point).  Returns the previous value */
+size_t pdhip_owner_mean_colors_workspace_bytes(int M);
+int pdhip_owner_mean_colors(const int32_t* owner, const float* colors, int N, int M, const float* fallback, float* out, void* ws_or_null, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,11 @@ _SIGS = {
     'pdhip_closest_on_mesh_workspace_bytes': (sz, [i32, i32, i32]),
     'pdhip_closest_on_mesh': (C.c_int, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
     'pdhip_debug_set_closest_on_mesh': (C.c_int, [i32, i32]),
+    'pdhip_fps_workspace_bytes': (sz, [i32, i32]),
+    'pdhip_fps': (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    'pdhip_debug_set_fps_cells': (C.c_int, [i32]),
+    'pdhip_owner_mean_colors_workspace_bytes': (sz, [i32]),
+    'pdhip_owner_mean_colors': (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp]),
     'pdhip_rescale_vertices': (C.c_int, [vp, i32, i32, vp, vp, vp, f64, vp]),
     'pdhip_optimize_color_ws_bytes': (sz, [i32, i32, i32]),
     'pdhip_optimize_color': (C.c_int, [vp, i32, vp, vp, i32, i32, vp, i32, vp, f64, i32, vp, vp, vp]),

@@ -5,6 +5,10 @@ same YAML keys (configs/*.yaml of the reference) and the same output tree as /ro
       models/model_normalized.{obj,mtl,png}, others/{k}_{sparse,mask0,mask2,inpainted}.png, others/atlas_wo_background.png
       and, only with the opt-in key `render_views` (6 or 20; `render_res`, default 512): rendered_imgs/albedo_%03d.png
 
+A cloud above 30 000 points is refused as in the reference (demo.py:371-374) unless the opt-in key `subsample: fps` is set: then it is subsampled on
+the device to `subsample_num` points (default 30 000) by farthest-point sampling, `subsample_colors: mean` averaging the colours each sample stands
+for; input_pc.ply is the subsample, and `geo_from: 'SPR'` still reconstructs from the full cloud.
+
 Geometry: the reference's drop-in hooks -- `<pc>_untextured_mesh.obj` next to the PLY (demo.py:391-399), the cached
 `geo/<name>_untextured/models/model_normalized.obj` (demo.py:401-406) and the cached `geo/xatlas_<res>.pth` dict (demo.py:428-448)
 -- and, with `geo_from: 'SPR'`, a mesh reconstructed from the cloud on the device (spr.recon_one_shape_SPR; POCO stays out of
@@ -38,6 +42,11 @@ GEOMETRY_KEYS = ('spr_depth', 'spr_knn', 'spr_faces')
 # opt-in stage behind the texturing path: render_views (6 or 20 'self_defined' views) writes <out>/rendered_imgs/albedo_%03d.png at
 # render_res (default 512); without render_views nothing is rendered and the output tree is unchanged
 RENDER_KEYS = ('render_views', 'render_res')
+# opt-in stage in front of everything: subsample: 'fps' takes a cloud above SUBSAMPLE_LIMIT points down to subsample_num (default and at most the
+# limit) by farthest-point sampling on the device (subsample.py); subsample_colors: 'point' (default) keeps the samples' own colours, 'mean' gives each
+# sample the mean colour of the points it stands for.  Without `subsample` such a cloud is refused as in the reference
+SUBSAMPLE_KEYS = ('subsample', 'subsample_num', 'subsample_colors')
+SUBSAMPLE_LIMIT = 30000
 
 
 class Cfg(dict):
@@ -77,7 +86,8 @@ def load_config(cfg_file, overrides=None):
     are validated, upstream keys are kept but unused, an unknown key is an error (a typo must not silently fall back)."""
     cfg = Cfg(yaml.safe_load(open(cfg_file)))
     cfg.update(overrides or {})
-    unknown = [k for k in cfg if k not in SUPPORTED_KEYS and k not in UPSTREAM_KEYS and k not in GEOMETRY_KEYS and k not in RENDER_KEYS]
+    unknown = [k for k in cfg if k not in SUPPORTED_KEYS and k not in UPSTREAM_KEYS and k not in GEOMETRY_KEYS and k not in RENDER_KEYS
+               and k not in SUBSAMPLE_KEYS]
     if unknown:
         raise KeyError(f"{cfg_file}: unknown config keys {unknown}")
     if 'texture_gen_method' not in cfg:
@@ -99,6 +109,13 @@ def load_config(cfg_file, overrides=None):
         raise ValueError(f"render_views={cfg.render_views!r}: the 'self_defined' evaluation cameras come as 6 or 20 views")
     if 'render_res' in cfg and not (isinstance(cfg.render_res, int) and not isinstance(cfg.render_res, bool) and 1 <= cfg.render_res <= 16384):
         raise ValueError(f"render_res={cfg.render_res!r}: the side of the rendered views is an integer in 1 .. 16384")
+    if 'subsample' in cfg and cfg.subsample not in ('fps',):
+        raise ValueError(f"subsample={cfg.subsample!r}: the subsampler of clouds above {SUBSAMPLE_LIMIT} points is 'fps' (farthest point)")
+    if 'subsample_num' in cfg and not (isinstance(cfg.subsample_num, int) and not isinstance(cfg.subsample_num, bool)
+                                       and 1 <= cfg.subsample_num <= SUBSAMPLE_LIMIT):
+        raise ValueError(f"subsample_num={cfg.subsample_num!r}: the size of the subsample is an integer in 1 .. {SUBSAMPLE_LIMIT}")
+    if 'subsample_colors' in cfg and cfg.subsample_colors not in ('point', 'mean'):
+        raise ValueError(f"subsample_colors={cfg.subsample_colors!r}: 'point' (the samples' own colours) or 'mean' (of the points each stands for)")
     if cfg.optimize_from == 'None':                      # YAML `None` is the string 'None' (demo.py:213 treats both alike)
         cfg['optimize_from'] = None
     return cfg
@@ -188,7 +205,7 @@ def _load_shape(cfg, pc_file, name, device, logger):
     for d in ('geo', 'models', 'others'):
         os.makedirs(os.path.join(out, d), exist_ok=True)
     xyz, rgb = io_utils.read_ply_xyzrgb(pc_file)
-    if len(xyz) > 30000:
+    if len(xyz) > 30000 and 'subsample' not in cfg:
         print(f"Point number > 30000! ({len(xyz)} points)({pc_file}) \n Please try uniformly subsampling the input point cloud first")
         raise NotImplementedError
     xyz = torch.tensor(np.asarray(xyz, np.float32)).to(device)
@@ -196,6 +213,17 @@ def _load_shape(cfg, pc_file, name, device, logger):
     vmin, vmax = xyz.min(0)[0], xyz.max(0)[0]
     xyz -= (vmax + vmin) / 2.
     xyz /= (vmax - vmin).max()
+    # above the limit (only with `subsample`): the cloud is normalised by its FULL box, so that a supplied mesh still lines up; the SPR geometry
+    # below reconstructs from the full cloud, the texturing path gets the subsample
+    full = (xyz, rgb) if len(xyz) > SUBSAMPLE_LIMIT else None
+    if full is not None:
+        from . import subsample
+        start = time.time()
+        xyz, rgb, _, min_d2 = subsample.subsample_cloud(full[0], full[1], num=cfg.get('subsample_num', SUBSAMPLE_LIMIT),
+                                                        colors_from=cfg.get('subsample_colors', 'point'), return_min_d2=True)
+        radius = float(min_d2[-1].sqrt()) if len(xyz) > 1 else float('inf')
+        logger.info(f'subsampled {len(full[0])} -> {len(xyz)} points by farthest-point sampling (covering radius {radius:.6g}, colours: '
+                    f'{cfg.get("subsample_colors", "point")}; {time.time() - start} s)')
     io_utils.save_colored_pc_ply(xyz.cpu().numpy(), rgb.cpu().numpy(), os.path.join(out, 'input_pc.ply'))
     geo_path = pc_file.replace('.ply', '_untextured_mesh.obj')
     xatlas_file = os.path.join(out, 'geo', f'xatlas_{cfg.xatlas_texture_res}.pth')
@@ -207,7 +235,8 @@ def _load_shape(cfg, pc_file, name, device, logger):
         logger.info('Generating geometry by SPR...')
         start = time.time()
         depth = cfg.get('spr_depth', spr.DEFAULT_DEPTH)
-        rv, rf, _, rc = spr.recon_one_shape_SPR(xyz, rgb, depth=depth, knn=cfg.get('spr_knn', spr.DEFAULT_KNN), save_path=cached_geo,
+        geo_xyz, geo_rgb = full if full is not None else (xyz, rgb)
+        rv, rf, _, rc = spr.recon_one_shape_SPR(geo_xyz, geo_rgb, depth=depth, knn=cfg.get('spr_knn', spr.DEFAULT_KNN), save_path=cached_geo,
                                                 return_counts=True, target_faces=cfg.get('spr_faces'))
         decimated = (f', decimated from {rc["faces_reconstructed"]} faces in {rc["simplify_rounds"]} rounds'
                      if 'faces_reconstructed' in rc else '')
