@@ -762,6 +762,38 @@ int pdhip_debug_set_fps_cells(int cells_per_axis);   /* tuning / test hook; same
 size_t pdhip_owner_mean_colors_workspace_bytes(int M);
 int pdhip_owner_mean_colors(const int32_t* owner, const float* colors, int N, int M, const float* fallback, float* out, void* ws_or_null, void* stream);
 
+/* ---- exact k nearest neighbours and statistical outlier removal (csrc/knn.hip; no reference counterpart: `input_already_noisy` only picks a POCO
+ * weight set there.  The filter is PCL's StatisticalOutlierRemoval / Open3D's remove_statistical_outlier).
+ * pdhip_knn_points: for every query the EXACT k nearest targets.  queries [Q,3], targets [M,3] f32 on the device; with the inputs widened to f64,
+ * dx = qx - tx (dy, dz alike) and d2 = (dx*dx + dy*dy) + dz*dz op by op, row q of d2 (device [Q,k] f64) and idx (device [Q,k] i32) holds the k SMALLEST
+ * pairs (d2, target index) in ascending lexicographic order: equal distances are ordered by index, and the same order decides the set when the tie
+ * falls at the k-th place.  Both equal a brute-force f64 scan followed by a stable sort bit for bit, do not depend on the order of the queries, and two
+ * calls give equal bytes (no floating-point atomics); with k == 1 they are the bytes of pdhip_nearest_points.  k = 1 .. pdhip_knn_max_k() (64).
+ * counts (device [4]): queries certified by the ring scan over the targets' cell list, queries finished by the staged sweep of all targets behind it
+ * (far from every target, or in crowded cells), grid cells per axis, 0; counts[0] + counts[1] == Q.  Every thread keeps its candidate list in LDS:
+ * pdhip_knn_lds_bytes(k) = 12 * 65 * k bytes per workgroup of 64 queries.  ws: pdhip_knn_points_workspace_bytes(Q, M, k) device bytes, a function
+ * of (Q, M) alone (0 for sizes the entry refuses).  PDHIP_E_ARG with the cause, and d2 / idx / counts untouched: a null pointer (named), k < 1,
+ * k > 64 or k > M, M < 1 or > 2^26, Q < 0 or > 2^26, a non-finite coordinate in either cloud.  Q == 0: PDHIP_OK, counts zeroed.  The read of the two
+ * bounding boxes, of the two non-finite counts and of the targets' per-axis coordinate histograms SYNCHRONISES the stream once (64 bytes + 12 KiB);
+ * the grid is laid over the part of the targets' span -- their box cut per axis to the 1 % .. 99 % quantiles and widened by a tenth, so that a few
+ * far points do not decide the cell size -- that the queries' box meets.  (The size query is not called ..._ws_bytes: tests/test_ws_bytes_cpu.py fixes the set of queries with that suffix.) */
+size_t pdhip_knn_points_workspace_bytes(int Q, int M, int k);
+int pdhip_knn_max_k(void);
+size_t pdhip_knn_lds_bytes(int k);
+int pdhip_knn_points(const float* queries, int Q, const float* targets, int M, int k, double* d2, int32_t* idx, int32_t* counts, void* ws, void* stream);
+int pdhip_debug_set_knn(int cells_per_axis, int path);   /* tuning / test hook; same results under every setting.  cells_per_axis 0 (default): the grid's cells per axis follow M and k (sqrt(M / max(8, k / 2)), at most 128); 1 .. 64: that many.  path 0 (default): the ring scan, then the sweep for the queries it gave up; 1: the sweep for every query; 2: as 0 with the grid over the targets' whole box (no quantile cut).  Returns 4 * (previous cells_per_axis) + previous path, or -1 (and changes nothing) for a value outside these ranges */
+/* pdhip_sor_filter: statistical outlier removal over the output of pdhip_knn_points.  knn_d2 [N,kk] f64 on the device: the kk = k + 1 nearest neighbours
+ * of every point of a cloud in the cloud itself; slot 0 (the point itself, or a duplicate of it with a smaller index: distance 0 either way) is skipped.
+ * mean_d[i] = (sum over j = 1 .. k of sqrt(knn_d2[i][j])) / k, summed sequentially in slot order in f64; mu = mean of mean_d,
+ * sigma = sqrt(sum (mean_d - mu)^2 / (N - 1)) in two passes, both sums over a fixed tree that is a function of N alone (equal bits on repeats);
+ * t = mu + std_ratio * sigma; stats (device [4] f64) = mu, sigma, t, 0; keep[i] (device [N] u8) = mean_d[i] <= t; kept_idx[0 .. counts[0]) (device [N]
+ * i32) = the kept indices, ascending; counts (device [4]) = kept, removed, 0, 0.  ws: pdhip_sor_filter_workspace_bytes(N) device bytes (0 for sizes
+ * the entry refuses).  PDHIP_E_ARG with the cause, and nothing written: a null pointer (named), N < 2 or > 2^26, kk < 2 or > 64, std_ratio negative
+ * or not finite, a negative or non-finite knn_d2.  The read of the count of bad distances SYNCHRONISES the stream once (4 bytes). */
+size_t pdhip_sor_filter_workspace_bytes(int N);
+int pdhip_sor_filter(const double* knn_d2, int N, int kk, double std_ratio, double* mean_d, double* stats, uint8_t* keep, int32_t* kept_idx,
+                     int32_t* counts, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,7 +67,14 @@ _SIGS = {
     'pdhip_debug_set_fps_cells': (C.c_int, [i32]),
     'pdhip_owner_mean_colors_workspace_bytes': (sz, [i32]),
     'pdhip_owner_mean_colors': (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp]),
-    'pdhip_rescale_vertices': (C.c_int, [vp, i32, i32, vp, vp, vp, f64, vp]),
+    'pdhip_knn_points_workspace_bytes': (sz, [i32, i32, i32]),
+    'pdhip_knn_max_k': (C.c_int, []),
+    'pdhip_knn_lds_bytes': (sz, [i32]),
+    'pdhip_knn_points': (C.c_int, [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]),
+    'pdhip_debug_set_knn': (C.c_int, [i32, i32]),
+    'pdhip_sor_filter_workspace_bytes': (sz, [i32]),
+    'pdhip_sor_filter': (C.c_int, [vp, i32, i32, f64, vp, vp, vp, vp, vp, vp, vp]),
+    'pdhip_rescale_vertices':(C.c_int, [vp, i32, i32, vp, vp, vp, f64, vp]),
     'pdhip_optimize_color_ws_bytes': (sz, [i32, i32, i32]),
     'pdhip_optimize_color': (C.c_int, [vp, i32, vp, vp, i32, i32, vp, i32, vp, f64, i32, vp, vp, vp]),
     'pdhip_resize_mask': (C.c_int, [vp, i32, i32, i32, vp, i32, i32, vp]),

@@ -9,6 +9,10 @@ A cloud above 30 000 points is refused as in the reference (demo.py:371-374) unl
 the device to `subsample_num` points (default 30 000) by farthest-point sampling, `subsample_colors: mean` averaging the colours each sample stands
 for; input_pc.ply is the subsample, and `geo_from: 'SPR'` still reconstructs from the full cloud.
 
+With the opt-in key `remove_outliers: statistical` (`outlier_neighbors`, default 20; `outlier_std_ratio`, default 2.0) the raw cloud first loses the
+points whose mean distance to their nearest neighbours lies above mean + ratio * std of that quantity (outliers.py): the point limit, the box
+normalisation, a supplied mesh's normalisation, SPR and `subsample` see only the kept points; the removed ones go to others/removed_outliers.ply.
+
 Geometry: the reference's drop-in hooks -- `<pc>_untextured_mesh.obj` next to the PLY (demo.py:391-399), the cached
 `geo/<name>_untextured/models/model_normalized.obj` (demo.py:401-406) and the cached `geo/xatlas_<res>.pth` dict (demo.py:428-448)
 -- and, with `geo_from: 'SPR'`, a mesh reconstructed from the cloud on the device (spr.recon_one_shape_SPR; POCO stays out of
@@ -47,6 +51,10 @@ RENDER_KEYS = ('render_views', 'render_res')
 # sample the mean colour of the points it stands for.  Without `subsample` such a cloud is refused as in the reference
 SUBSAMPLE_KEYS = ('subsample', 'subsample_num', 'subsample_colors')
 SUBSAMPLE_LIMIT = 30000
+# opt-in stage in front of that: remove_outliers: 'statistical' drops the points whose mean distance to their outlier_neighbors (default 20) nearest
+# neighbours lies above mean + outlier_std_ratio (default 2.0) * std of that quantity (outliers.py), on the raw coordinates, before the point limit
+# and the box normalisation; the removed points go to others/removed_outliers.ply.  Without the key nothing is filtered
+OUTLIER_KEYS = ('remove_outliers', 'outlier_neighbors', 'outlier_std_ratio')
 
 
 class Cfg(dict):
@@ -87,7 +95,7 @@ def load_config(cfg_file, overrides=None):
     cfg = Cfg(yaml.safe_load(open(cfg_file)))
     cfg.update(overrides or {})
     unknown = [k for k in cfg if k not in SUPPORTED_KEYS and k not in UPSTREAM_KEYS and k not in GEOMETRY_KEYS and k not in RENDER_KEYS
-               and k not in SUBSAMPLE_KEYS]
+               and k not in SUBSAMPLE_KEYS and k not in OUTLIER_KEYS]
     if unknown:
         raise KeyError(f"{cfg_file}: unknown config keys {unknown}")
     if 'texture_gen_method' not in cfg:
@@ -116,6 +124,14 @@ def load_config(cfg_file, overrides=None):
         raise ValueError(f"subsample_num={cfg.subsample_num!r}: the size of the subsample is an integer in 1 .. {SUBSAMPLE_LIMIT}")
     if 'subsample_colors' in cfg and cfg.subsample_colors not in ('point', 'mean'):
         raise ValueError(f"subsample_colors={cfg.subsample_colors!r}: 'point' (the samples' own colours) or 'mean' (of the points each stands for)")
+    if 'remove_outliers' in cfg and cfg.remove_outliers not in ('statistical',):
+        raise ValueError(f"remove_outliers={cfg.remove_outliers!r}: the outlier filter is 'statistical' (mean k-NN distance against mean + ratio * std)")
+    if 'outlier_neighbors' in cfg and not (isinstance(cfg.outlier_neighbors, int) and not isinstance(cfg.outlier_neighbors, bool)
+                                           and 1 <= cfg.outlier_neighbors <= 63):
+        raise ValueError(f"outlier_neighbors={cfg.outlier_neighbors!r}: the neighbours of the outlier filter are an integer in 1 .. 63")
+    if 'outlier_std_ratio' in cfg and not (isinstance(cfg.outlier_std_ratio, (int, float)) and not isinstance(cfg.outlier_std_ratio, bool)
+                                           and 0.0 <= cfg.outlier_std_ratio < float('inf')):
+        raise ValueError(f"outlier_std_ratio={cfg.outlier_std_ratio!r}: the ratio of the outlier filter is a finite number >= 0")
     if cfg.optimize_from == 'None':                      # YAML `None` is the string 'None' (demo.py:213 treats both alike)
         cfg['optimize_from'] = None
     return cfg
@@ -199,12 +215,31 @@ def render_result(cfg, vertices, uvs, faces, mesh_tex_idx, atlas_img, output_roo
     return save_path
 
 
+def _remove_outliers(cfg, xyz, rgb, out, device, logger):
+    """The opt-in `remove_outliers` stage on the raw cloud as read from the PLY: (xyz, rgb) of the kept points, in the file's order; the removed
+    points -> <out>/others/removed_outliers.ply."""
+    from . import outliers
+    start = time.time()
+    xyz, rgb = np.asarray(xyz, np.float32), np.asarray(rgb)
+    k, ratio = cfg.get('outlier_neighbors', 20), cfg.get('outlier_std_ratio', 2.0)
+    keep, st = outliers.statistical_outlier_mask(torch.from_numpy(np.ascontiguousarray(xyz)).to(device), nb_neighbors=k, std_ratio=ratio,
+                                                 return_stats=True)
+    keep = keep.cpu().numpy()
+    # (the writer stores uint8(c * 255), truncating: the half keeps every byte of the file's colours)
+    io_utils.save_colored_pc_ply(xyz[~keep], (np.asarray(rgb[~keep], np.float32) + 0.5) / 255.0, os.path.join(out, 'others', 'removed_outliers.ply'))
+    logger.info(f'statistical outlier removal ({k} neighbours, ratio {ratio}): kept {st["kept"]}, removed {st["removed"]} of {len(xyz)} points '
+                f'(mean {st["mean"]:.6g}, std {st["std"]:.6g}, threshold {st["threshold"]:.6g}; {time.time() - start} s)')
+    return xyz[keep], rgb[keep]
+
+
 def _load_shape(cfg, pc_file, name, device, logger):
     """demo.py:359-452: cloud, mesh and atlas of one shape, normalised as the reference does."""
     out = os.path.join(cfg.output_path, name)
     for d in ('geo', 'models', 'others'):
         os.makedirs(os.path.join(out, d), exist_ok=True)
     xyz, rgb = io_utils.read_ply_xyzrgb(pc_file)
+    if 'remove_outliers' in cfg:
+        xyz, rgb = _remove_outliers(cfg, xyz, rgb, out, device, logger)
     if len(xyz) > 30000 and 'subsample' not in cfg:
         print(f"Point number > 30000! ({len(xyz)} points)({pc_file}) \n Please try uniformly subsampling the input point cloud first")
         raise NotImplementedError

@@ -1,0 +1,251 @@
+"""Statistical outlier removal on the device (csrc/knn.hip: pdhip_sor_filter; pointdreamer_amd/outliers.py; the demo's opt-in `remove_outliers` key)
+against the numpy float64 oracle of tests/knn_common.py.  The cloud: 2 000 points on a sphere of radius 0.5 and 32 far points, k = 20, ratio 2.
+Bounds (derived, not measured): mean_d within (k + 4) 2^-52 relative (sqrt within 1 ulp, k sequential adds, one divide); mu, sigma and t within
+N 2^-52 relative of a math.fsum oracle (any summation order of N non-negative terms, doubled)."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import knn_common as kc
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+K, RATIO = kc.SOR_K, kc.SOR_RATIO
+SENT_F, SENT_U8, SENT_I = -7.0, 77, -777
+
+
+def T(a):
+    return torch.from_numpy(np.array(a)).to(DEV)
+
+
+def run_sor(d2, ratio, null=None, N=None, kk=None):
+    """(rc, mean_d, stats, keep, kept_idx, counts) of pdhip_sor_filter; the outputs start as sentinels."""
+    from pointdreamer_amd import _lib
+    from pointdreamer_amd._lib import ptr, stream
+    L = _lib.lib()
+    td = T(np.asarray(d2, np.float64))
+    N = td.shape[0] if N is None else N
+    kk = td.shape[1] if kk is None else kk
+    n = td.shape[0]
+    mean_d = torch.full((n,), SENT_F, dtype=torch.float64, device=DEV)
+    stats = torch.full((4,), SENT_F, dtype=torch.float64, device=DEV)
+    keep = torch.full((n,), SENT_U8, dtype=torch.uint8, device=DEV)
+    kept_idx = torch.full((n,), SENT_I, dtype=torch.int32, device=DEV)
+    counts = torch.full((4,), SENT_I, dtype=torch.int32, device=DEV)
+    ws = torch.empty((max(L.pdhip_sor_filter_workspace_bytes(N), 8),), dtype=torch.uint8, device=DEV)
+    a = dict(knn_d2=ptr(td), mean_d=ptr(mean_d), stats=ptr(stats), keep=ptr(keep), kept_idx=ptr(kept_idx), counts=ptr(counts), ws=ptr(ws))
+    if null is not None:
+        a[null] = None
+    rc = L.pdhip_sor_filter(a['knn_d2'], N, kk, float(ratio), a['mean_d'], a['stats'], a['keep'], a['kept_idx'], a['counts'], a['ws'], stream())
+    torch.cuda.synchronize()
+    return (rc,) + tuple(x.cpu().numpy() for x in (mean_d, stats, keep, kept_idx, counts))
+
+
+def untouched(mean_d, stats, keep, kept_idx, counts):
+    return (np.all(mean_d == SENT_F) and np.all(stats == SENT_F) and np.all(keep == SENT_U8) and np.all(kept_idx == SENT_I)
+            and np.all(counts == SENT_I))
+
+
+@pytest.fixture(scope="module")
+def device_run():
+    """The filter on the shared cloud, from the DEVICE's own k-NN: (knn d2, the outputs of run_sor)."""
+    from pointdreamer_amd import outliers
+    pts, _ = kc.sor_cloud()
+    d2, idx = outliers.knn_points(T(pts), T(pts), K + 1)
+    od2, oidx = kc.oracle_knn(pts, pts, K + 1)
+    assert np.array_equal(d2.cpu().numpy().view(np.uint64), od2.view(np.uint64)) and np.array_equal(idx.cpu().numpy(), oidx)
+    return od2, run_sor(od2, RATIO)
+
+
+def test_mean_distances_and_statistics_lie_within_the_derived_bounds(device_run):
+    _, (rc, mean_d, stats, keep, kept_idx, counts) = device_run
+    o = kc.oracle_sor_cloud()
+    N = len(mean_d)
+    b_mean, b_stat = kc.sor_bounds(N, K)
+    rel = np.abs(mean_d - o['mean_d']) / o['mean_d']
+    print('mean_d: max relative error', rel.max(), 'bound', b_mean)
+    assert rc == 0 and rel.max() <= b_mean
+    for name, got in zip(('mean', 'std', 'threshold'), stats[:3]):
+        err = abs(got - o[name]) / o[name]
+        print(name, got, 'oracle', o[name], 'relative error', err, 'bound', b_stat)
+        assert err <= b_stat
+    assert stats[3] == 0.0
+
+
+def test_mask_is_the_devices_own_comparison_and_the_oracles_mask(device_run):
+    _, (rc, mean_d, stats, keep, kept_idx, counts) = device_run
+    pts, surf = kc.sor_cloud()
+    o = kc.oracle_sor_cloud()
+    N = len(pts)
+    assert set(np.unique(keep).tolist()) <= {0, 1}
+    assert np.array_equal(keep.astype(bool), mean_d <= stats[2])                    # exactly, for the device's own mean_d and t
+    b_mean, b_stat = kc.sor_bounds(N, K)
+    gap = np.abs(o['mean_d'] - o['threshold']).min()
+    assert gap > b_mean * o['mean_d'].max() + b_stat * o['threshold']               # (on the oracle alone) nobody within the bounds of the threshold
+    assert np.array_equal(keep.astype(bool), o['keep'])
+    assert (keep == 0).sum() == 31 and not (surf & (keep == 0)).any()
+
+
+def test_kept_indices_are_ascending_and_the_counts_add_up(device_run):
+    _, (rc, mean_d, stats, keep, kept_idx, counts) = device_run
+    N = len(keep)
+    kept = int(counts[0])
+    assert counts.tolist() == [int(keep.sum()), N - int(keep.sum()), 0, 0] and kept + counts[1] == N
+    assert np.array_equal(kept_idx[:kept], np.nonzero(keep)[0].astype(np.int32)) and np.all(np.diff(kept_idx[:kept]) > 0)
+    assert np.all(kept_idx[kept:] == SENT_I)                                        # nothing behind the kept count is written
+
+
+def test_two_calls_give_equal_bytes(device_run):
+    d2, first = device_run
+    again = run_sor(d2, RATIO)
+    for x, y in zip(first[1:], again[1:]):
+        assert x.tobytes() == y.tobytes()
+
+
+def test_the_smallest_cloud_on_exact_values():
+    rc, mean_d, stats, keep, kept_idx, counts = run_sor(np.array([[0.0, 1.0, 1.0, 1.0], [0.0, 9.0, 9.0, 9.0]]), 0.5)
+    assert rc == 0 and mean_d.tolist() == [1.0, 3.0] and stats.tolist() == [2.0, np.sqrt(2.0), 2.0 + 0.5 * np.sqrt(2.0), 0.0]
+    assert keep.tolist() == [1, 0] and counts.tolist() == [1, 1, 0, 0] and kept_idx.tolist() == [0, SENT_I]
+
+
+@pytest.mark.parametrize("N", [257, 70001])
+def test_statistics_over_other_sizes(N):
+    """More than one workgroup, and more elements than one pass of the workgroups' strided sums: the same bounds."""
+    rng = np.random.default_rng(N)
+    d2 = np.sort(rng.random((N, 4)), axis=1)
+    d2[:, 0] = 0.0
+    rc, mean_d, stats, keep, kept_idx, counts = run_sor(d2, 1.0)
+    o = kc.oracle_sor(d2, 1.0)
+    b_mean, b_stat = kc.sor_bounds(N, 3)
+    assert rc == 0 and (np.abs(mean_d - o['mean_d']) <= b_mean * o['mean_d']).all()
+    for name, got in zip(('mean', 'std', 'threshold'), stats[:3]):
+        assert abs(got - o[name]) <= b_stat * o[name], (name, got, o[name])
+    assert np.array_equal(keep.astype(bool), mean_d <= stats[2]) and counts[0] + counts[1] == N and counts[0] == keep.sum()
+    assert np.array_equal(kept_idx[:counts[0]], np.nonzero(keep)[0].astype(np.int32))
+
+
+def test_identical_points_have_no_spread_and_are_all_kept():
+    from pointdreamer_amd import outliers
+    p = T(np.tile(np.array([[0.3, -2.0, 7.0]], np.float32), (300, 1)))
+    keep, st = outliers.statistical_outlier_mask(p, nb_neighbors=20, std_ratio=2.0, return_stats=True)
+    assert bool(keep.all()) and st['std'] == 0.0 and st['mean'] == 0.0 and st['threshold'] == 0.0 and st['kept'] == 300 and st['removed'] == 0
+
+
+# ---- the wrappers
+def test_wrappers_return_the_oracles_selection():
+    from pointdreamer_amd import outliers
+    pts, _ = kc.sor_cloud()
+    o = kc.oracle_sor_cloud()
+    cols = T(np.random.default_rng(1).random((len(pts), 3), dtype=np.float32))
+    keep, st = outliers.statistical_outlier_mask(T(pts), return_stats=True)             # (the defaults are k = 20, ratio = 2)
+    assert keep.dtype == torch.bool and np.array_equal(keep.cpu().numpy(), o['keep'])
+    assert sorted(st) == ['kept', 'mean', 'mean_d', 'removed', 'std', 'threshold'] and st['kept'] == int(o['keep'].sum()) and st['removed'] == 31
+    assert st['mean_d'].shape == (len(pts),) and st['mean_d'].dtype == torch.float64 and abs(st['threshold'] - o['threshold']) < 1e-12
+    assert torch.equal(outliers.statistical_outlier_mask(T(pts), K, RATIO), keep)
+    p, c, kept = outliers.remove_statistical_outliers(T(pts), cols, nb_neighbors=K, std_ratio=RATIO)
+    want = np.nonzero(o['keep'])[0]
+    assert kept.dtype == torch.int64 and np.array_equal(kept.cpu().numpy(), want)
+    assert np.array_equal(p.cpu().numpy(), pts[want]) and torch.equal(c, cols[kept])
+    p2, c2, kept2 = outliers.remove_statistical_outliers(T(pts))
+    assert c2 is None and torch.equal(kept2, kept) and torch.equal(p2, p)
+
+
+@pytest.mark.parametrize("nb", [0, 64, 2032, 2.0, True])
+def test_wrappers_refuse_neighbour_counts_outside_the_range(nb):
+    from pointdreamer_amd import outliers
+    pts, _ = kc.sor_cloud()
+    with pytest.raises(ValueError, match='nb_neighbors'):
+        outliers.statistical_outlier_mask(T(pts), nb_neighbors=nb)
+    with pytest.raises(ValueError, match='nb_neighbors'):
+        outliers.statistical_outlier_mask(T(pts[:10]), nb_neighbors=10)                 # N - 1 = 9
+
+
+# ---- refusals write nothing
+@pytest.mark.parametrize("null", ['knn_d2', 'mean_d', 'stats', 'keep', 'kept_idx', 'counts', 'ws'])
+def test_refuses_a_null_pointer_by_name(null, device_run):
+    from pointdreamer_amd import _lib
+    out = run_sor(device_run[0][:100], RATIO, null=null)
+    assert out[0] == -1 and b'null pointer (%s)' % null.encode() in _lib.lib().pdhip_last_error() and untouched(*out[1:])
+
+
+@pytest.mark.parametrize("kw,word", [(dict(N=1), b'N=1'), (dict(kk=1), b'kk=1'), (dict(ratio=-1.0), b'std_ratio=-1'),
+                                     (dict(ratio=float('nan')), b'std_ratio=nan'), (dict(ratio=float('inf')), b'std_ratio=inf')])
+def test_refuses_bad_sizes_and_ratios(kw, word, device_run):
+    from pointdreamer_amd import _lib
+    out = run_sor(device_run[0][:100], kw.pop('ratio', RATIO), **kw)
+    assert out[0] == -1 and word in _lib.lib().pdhip_last_error() and untouched(*out[1:])
+
+
+@pytest.mark.parametrize("bad", [-1.0e-300, float('nan'), float('inf')])
+def test_refuses_a_negative_or_non_finite_distance(bad, device_run):
+    from pointdreamer_amd import _lib, outliers
+    d2 = np.array(device_run[0][:500])
+    d2[7, 0] = bad                                                                  # (slot 0 is skipped by the sum, not by the check)
+    d2[499, K] = bad
+    out = run_sor(d2, RATIO)
+    assert out[0] == -1 and b'2 negative or non-finite' in _lib.lib().pdhip_last_error() and untouched(*out[1:])
+    with pytest.raises(_lib.PdhipError, match='negative or non-finite'):
+        outliers.sor_filter(T(d2), RATIO)
+
+
+# ---- demo
+@pytest.fixture(scope="module")
+def noisy_ply(tmp_path_factory):
+    """A sphere cloud from synthetic.py's generator with twelve far points, as the demo reads it back from the PLY."""
+    from pointdreamer_amd import io_utils, synthetic
+    sh = synthetic.make_shape(3000, A=64, stacks=8, slices=16, seed=11)
+    rng = np.random.default_rng(12)
+    v = rng.standard_normal((12, 3))
+    far = (v / np.linalg.norm(v, axis=1, keepdims=True) * rng.uniform(1.5, 4.0, (12, 1))).astype(np.float32)
+    perm = rng.permutation(3012)
+    xyz = (np.concatenate([np.asarray(sh['points'], np.float32), far])[perm] * np.float32(1.7) + np.float32(0.3)).astype(np.float32)
+    rgb = np.concatenate([np.asarray(sh['colors'], np.float32), rng.random((12, 3), dtype=np.float32)])[perm]
+    pc = str(tmp_path_factory.mktemp('noisy') / 'scan.ply')
+    io_utils.save_colored_pc_ply(xyz, rgb, pc)
+    return pc
+
+
+def test_demo_filters_the_cloud_before_everything_else(noisy_ply, tmp_path):
+    from pointdreamer_amd import demo, io_utils
+    xyz, rgb = io_utils.read_ply_xyzrgb(noisy_ply)
+    d2, _ = kc.oracle_knn(xyz, xyz, K + 1)
+    o = kc.oracle_sor(d2, RATIO)
+    b_mean, b_stat = kc.sor_bounds(len(xyz), K)
+    assert np.abs(o['mean_d'] - o['threshold']).min() > b_mean * o['mean_d'].max() + b_stat * o['threshold']
+    keep = o['keep']
+    assert (~keep).sum() == 12 and np.linalg.norm((xyz[~keep] - 0.3) / 1.7, axis=1).min() > 1.4           # the far points go, the sphere stays
+    base = ["--config", os.path.join(ROOT, "configs", "nearest.yaml"), "--pc_file", noisy_ply, "--set", "xatlas_texture_res=256", "cam_res=128",
+            "res=64", "point_validation_by_o3d=False"]
+    out = demo.main(base + [f"output_path={tmp_path / 'filtered'}", "remove_outliers=statistical"])[0]
+    for f in ("input_pc.ply", "others/removed_outliers.ply", "models/model_normalized.obj", "models/model_normalized.png"):
+        assert os.path.exists(os.path.join(out, f)), f
+    gone, gone_rgb = io_utils.read_ply_xyzrgb(os.path.join(out, "others", "removed_outliers.ply"))
+    assert np.array_equal(gone, xyz[~keep]) and np.array_equal(gone_rgb, rgb[~keep])      # exactly the rest, in the file's order
+    got, got_rgb = io_utils.read_ply_xyzrgb(os.path.join(out, "input_pc.ply"))
+    kept = xyz[keep]
+    vmin, vmax = kept.min(0), kept.max(0)
+    want = (kept - (vmax + vmin) / np.float32(2.0)) / (vmax - vmin).max()                  # the box of the KEPT points
+    assert len(got) == keep.sum() and np.abs(got - want).max() <= 1e-6
+    assert abs(np.abs(got).max() - 0.5) <= 1e-6 and np.abs(np.linalg.norm(got.astype(np.float64), axis=1) - 0.5).max() < 0.02
+    assert np.abs(got_rgb.astype(int) - rgb[keep].astype(int)).max() <= 1                 # (the writer truncates c / 255 * 255)
+    # the keys' values reach the filter: one neighbour and ratio 0 keep the points at or below the mean
+    out1 = demo.main(base + [f"output_path={tmp_path / 'strict'}", "remove_outliers=statistical", "outlier_neighbors=1", "outlier_std_ratio=0"])[0]
+    o1 = kc.oracle_sor(kc.oracle_knn(xyz, xyz, 2)[0], 0.0)
+    assert np.abs(o1['mean_d'] - o1['threshold']).min() > 1e-9
+    assert len(io_utils.read_ply_xyzrgb(os.path.join(out1, "input_pc.ply"))[0]) == o1['keep'].sum() < 0.9 * len(xyz)
+
+
+def test_demo_without_the_key_keeps_every_point(noisy_ply, tmp_path):
+    from pointdreamer_amd import demo, io_utils
+    xyz, _ = io_utils.read_ply_xyzrgb(noisy_ply)
+    out = demo.main(["--config", os.path.join(ROOT, "configs", "nearest.yaml"), "--pc_file", noisy_ply, "--set", "xatlas_texture_res=256",
+                     "cam_res=128", "res=64", "point_validation_by_o3d=False", f"output_path={tmp_path / 'plain'}"])[0]
+    got, _ = io_utils.read_ply_xyzrgb(os.path.join(out, "input_pc.ply"))
+    vmin, vmax = xyz.min(0), xyz.max(0)
+    want = (xyz - (vmax + vmin) / np.float32(2.0)) / (vmax - vmin).max()
+    assert len(got) == len(xyz) and np.abs(got - want).max() <= 1e-6
+    assert not os.path.exists(os.path.join(out, "others", "removed_outliers.ply"))
+    assert np.abs(np.linalg.norm(got.astype(np.float64), axis=1)).max() > 0.45 and np.median(np.linalg.norm(got.astype(np.float64), axis=1)) < 0.2
