@@ -794,6 +794,42 @@ size_t pdhip_sor_filter_workspace_bytes(int N);
 int pdhip_sor_filter(const double* knn_d2, int N, int kk, double std_ratio, double* mean_d, double* stats, uint8_t* keep, int32_t* kept_idx,
                      int32_t* counts, void* ws, void* stream);
 
+/* ---- connected components of a mesh and compaction to a subset of its faces (csrc/mesh_components.hip; no reference counterpart: the filter on top,
+ * mesh_components.filter_components, is MeshLab's "Remove isolated pieces").
+ * pdhip_mesh_components: faces [F,3] i64 on the device, ANY indexed triangle list with indices in [0, Vn): it need not be closed, manifold or oriented,
+ * and a face may repeat an index.  Two vertices are connected when some face names both; a component is a class of the transitive closure over the
+ * referenced vertices.  Its root is its smallest vertex index, and the components are numbered 0 .. C-1 by ascending root.  vertex_comp (device [Vn]
+ * i32): the component of every vertex, -1 for a vertex no face names; face_comp (device [F] i32) = vertex_comp[faces[f][0]]; per component
+ * comp_root, comp_vertices, comp_faces (device [comp_capacity] i32: smallest index, vertices, faces) and, when comp_box is not NULL (vertices [Vn,3]
+ * f32 on the device are then required, and otherwise never read), comp_box (device [comp_capacity,6] f32: min x y z, then max x y z, over the
+ * component's vertices).  counts (device [4]): C, referenced vertices, unreferenced vertices, 0.  The per-component arrays hold comp_capacity
+ * entries: when C > comp_capacity the entry still writes vertex_comp, face_comp, counts and the entries of the first comp_capacity components and
+ * returns PDHIP_OK -- the caller reads C and calls again (entries from C on are never written).  Every output is a function of the mesh alone:
+ * it depends on neither the order of the faces, nor the rotation of a face's indices, nor the threads' order, and two calls give equal bytes
+ * (a lock-free union-find that keeps parent[v] <= v, integer atomics, boxes by atomicMin / atomicMax on the ordered encoding of the f32 bits; a
+ * box bound that is zero may carry either sign).  ws: pdhip_mesh_components_workspace_bytes(Vn, F) device bytes (0 for sizes the entry refuses).
+ * PDHIP_E_ARG with the cause, and every output untouched: a null pointer (named; only vertices and comp_box may be NULL, comp_box without vertices
+ * may not), Vn < 1, F < 0, Vn > 2^26, F > 2^23, comp_capacity < 0, a face index outside [0, Vn), a referenced vertex that is not finite when boxes
+ * are asked for.  F == 0: PDHIP_OK, counts = 0, 0, Vn, 0, every vertex_comp -1, no synchronisation.  Otherwise the read of the check words and of C
+ * SYNCHRONISES the stream once, after the last launch (32 bytes).  Every walk of the union-find goes to strictly smaller indices and is bounded by
+ * 2 Vn + 64 steps all the same; should one use them up, PDHIP_E_STATE and no output.  (The size queries are not called ..._ws_bytes:
+ * tests/test_ws_bytes_cpu.py fixes the set of queries with that suffix.) */
+size_t pdhip_mesh_components_workspace_bytes(int Vn, int F);
+int pdhip_mesh_components(const int64_t* faces, int F, const float* vertices_or_null, int Vn, int32_t* vertex_comp, int32_t* face_comp,
+                          int32_t* comp_root, int32_t* comp_vertices, int32_t* comp_faces, float* comp_box_or_null, int comp_capacity,
+                          int32_t* counts, void* ws, void* stream);
+/* pdhip_compact_mesh: the faces with face_keep[f] != 0 (device [F] u8) and the vertices they name, both in input order -- pdhip_simplify_mesh's output
+ * contract: every output vertex is referenced.  out_vertices (device [Vn,3] f32) and, with colors [Vn,3] f32, out_colors: copies bit for bit;
+ * out_faces (device [F,3] i64): the kept faces re-indexed; vertex_map (device [Vn] i32, may be NULL): the new index of every vertex, -1 for a dropped
+ * one.  counts (device [4]): output vertices, output faces, 0, 0.  Two exclusive scans through the shared tiled scan; equal bytes on repeats.
+ * ws: pdhip_compact_mesh_workspace_bytes(Vn, F) device bytes (0 for sizes the entry refuses).  PDHIP_E_ARG with the cause, and every output
+ * untouched: a null pointer (named), colors without out_colors or the reverse, Vn < 1, F < 0, Vn > 2^26, F > 2^23, a face index outside [0, Vn)
+ * (in a dropped face too).  The read of the check word SYNCHRONISES the stream once, after the last launch. */
+size_t pdhip_compact_mesh_workspace_bytes(int Vn, int F);
+int pdhip_compact_mesh(const float* vertices, int Vn, const int64_t* faces, int F, const float* colors_or_null, const uint8_t* face_keep,
+                       float* out_vertices, int64_t* out_faces, float* out_colors_or_null, int32_t* vertex_map_or_null, int32_t* counts, void* ws,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

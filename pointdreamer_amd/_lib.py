@@ -74,6 +74,10 @@ _SIGS = {
     'pdhip_debug_set_knn': (C.c_int, [i32, i32]),
     'pdhip_sor_filter_workspace_bytes': (sz, [i32]),
     'pdhip_sor_filter': (C.c_int, [vp, i32, i32, f64, vp, vp, vp, vp, vp, vp, vp]),
+    'pdhip_mesh_components_workspace_bytes': (sz, [i32, i32]),
+    'pdhip_mesh_components': (C.c_int, [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
+    'pdhip_compact_mesh_workspace_bytes': (sz, [i32, i32]),
+    'pdhip_compact_mesh': (C.c_int, [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'pdhip_rescale_vertices':(C.c_int, [vp, i32, i32, vp, vp, vp, f64, vp]),
     'pdhip_optimize_color_ws_bytes': (sz, [i32, i32, i32]),
     'pdhip_optimize_color': (C.c_int, [vp, i32, vp, vp, i32, i32, vp, i32, vp, f64, i32, vp, vp, vp]),

@@ -13,6 +13,9 @@ With the opt-in key `remove_outliers: statistical` (`outlier_neighbors`, default
 points whose mean distance to their nearest neighbours lies above mean + ratio * std of that quantity (outliers.py): the point limit, the box
 normalisation, a supplied mesh's normalisation, SPR and `subsample` see only the kept points; the removed ones go to others/removed_outliers.ply.
 
+With the opt-in keys `spr_components: largest` / `spr_min_component_share` the mesh reconstructed under `geo_from: 'SPR'` loses its small floating
+pieces on the device (mesh_components.py) before it is decimated, cached and textured; elsewhere the keys have no effect.
+
 Geometry: the reference's drop-in hooks -- `<pc>_untextured_mesh.obj` next to the PLY (demo.py:391-399), the cached
 `geo/<name>_untextured/models/model_normalized.obj` (demo.py:401-406) and the cached `geo/xatlas_<res>.pth` dict (demo.py:428-448)
 -- and, with `geo_from: 'SPR'`, a mesh reconstructed from the cloud on the device (spr.recon_one_shape_SPR; POCO stays out of
@@ -55,6 +58,10 @@ SUBSAMPLE_LIMIT = 30000
 # neighbours lies above mean + outlier_std_ratio (default 2.0) * std of that quantity (outliers.py), on the raw coordinates, before the point limit
 # and the box normalisation; the removed points go to others/removed_outliers.ply.  Without the key nothing is filtered
 OUTLIER_KEYS = ('remove_outliers', 'outlier_neighbors', 'outlier_std_ratio')
+# opt-in stage behind the SPR reconstruction (geo_from: 'SPR' only, before spr_faces' decimation): spr_components: 'largest' keeps the component of the
+# reconstructed mesh with the most faces ('all', the default when absent: every component, as before); spr_min_component_share (a float in (0, 1])
+# keeps the components with at least that share of the largest one's face count (mesh_components.py).  The cached geometry OBJ is the filtered mesh
+COMPONENT_KEYS = ('spr_components', 'spr_min_component_share')
 
 
 class Cfg(dict):
@@ -95,7 +102,7 @@ def load_config(cfg_file, overrides=None):
     cfg = Cfg(yaml.safe_load(open(cfg_file)))
     cfg.update(overrides or {})
     unknown = [k for k in cfg if k not in SUPPORTED_KEYS and k not in UPSTREAM_KEYS and k not in GEOMETRY_KEYS and k not in RENDER_KEYS
-               and k not in SUBSAMPLE_KEYS and k not in OUTLIER_KEYS]
+               and k not in SUBSAMPLE_KEYS and k not in OUTLIER_KEYS and k not in COMPONENT_KEYS]
     if unknown:
         raise KeyError(f"{cfg_file}: unknown config keys {unknown}")
     if 'texture_gen_method' not in cfg:
@@ -132,6 +139,12 @@ def load_config(cfg_file, overrides=None):
     if 'outlier_std_ratio' in cfg and not (isinstance(cfg.outlier_std_ratio, (int, float)) and not isinstance(cfg.outlier_std_ratio, bool)
                                            and 0.0 <= cfg.outlier_std_ratio < float('inf')):
         raise ValueError(f"outlier_std_ratio={cfg.outlier_std_ratio!r}: the ratio of the outlier filter is a finite number >= 0")
+    if 'spr_components' in cfg and cfg.spr_components not in ('all', 'largest'):
+        raise ValueError(f"spr_components={cfg.spr_components!r}: the components kept of the SPR geometry are 'all' or 'largest' (the one with the most faces)")
+    if 'spr_min_component_share' in cfg and not (isinstance(cfg.spr_min_component_share, (int, float))
+                                                 and not isinstance(cfg.spr_min_component_share, bool) and 0.0 < cfg.spr_min_component_share <= 1.0):
+        raise ValueError(f"spr_min_component_share={cfg.spr_min_component_share!r}: the share of the largest component's face count that a component "
+                         "of the SPR geometry needs is a number in (0, 1]")
     if cfg.optimize_from == 'None':                      # YAML `None` is the string 'None' (demo.py:213 treats both alike)
         cfg['optimize_from'] = None
     return cfg
@@ -232,6 +245,16 @@ def _remove_outliers(cfg, xyz, rgb, out, device, logger):
     return xyz[keep], rgb[keep]
 
 
+def _component_rules(cfg):
+    """The opt-in COMPONENT_KEYS as recon_one_shape_SPR's keyword: nothing without them (or with spr_components: 'all' alone), so that nothing new runs."""
+    rules = {}
+    if cfg.get('spr_components', 'all') == 'largest':
+        rules['keep'] = 'largest'
+    if 'spr_min_component_share' in cfg:
+        rules['min_face_share'] = float(cfg.spr_min_component_share)
+    return dict(keep_components=rules) if rules else {}
+
+
 def _load_shape(cfg, pc_file, name, device, logger):
     """demo.py:359-452: cloud, mesh and atlas of one shape, normalised as the reference does."""
     out = os.path.join(cfg.output_path, name)
@@ -272,11 +295,14 @@ def _load_shape(cfg, pc_file, name, device, logger):
         depth = cfg.get('spr_depth', spr.DEFAULT_DEPTH)
         geo_xyz, geo_rgb = full if full is not None else (xyz, rgb)
         rv, rf, _, rc = spr.recon_one_shape_SPR(geo_xyz, geo_rgb, depth=depth, knn=cfg.get('spr_knn', spr.DEFAULT_KNN), save_path=cached_geo,
-                                                return_counts=True, target_faces=cfg.get('spr_faces'))
+                                                return_counts=True, target_faces=cfg.get('spr_faces'), **_component_rules(cfg))
         decimated = (f', decimated from {rc["faces_reconstructed"]} faces in {rc["simplify_rounds"]} rounds'
-                     if 'faces_reconstructed' in rc else '')
+                     if 'simplify_rounds' in rc else '')
         logger.info(f'Get Geometry time: {time.time() - start} s by SPR (depth {depth}: {rc["vertices"]} vertices, {rc["faces"]} '
                     f'faces{decimated}, {rc["iterations"]} solver iterations; normals oriented by {rc["orientation"]})')
+        if 'components' in rc:
+            logger.info(f'SPR components: {rc["components"]} found, {rc["components_kept"]} kept, {rc["faces_dropped"]} of '
+                        f'{rc["faces_reconstructed"]} reconstructed faces dropped')
     if os.path.exists(geo_path) or os.path.exists(cached_geo):
         supplied = os.path.exists(geo_path)
         v, f, vt, ft = io_utils.load_obj_mesh(geo_path if supplied else cached_geo, with_uv=True)

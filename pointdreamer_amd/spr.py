@@ -2,7 +2,8 @@
 normals for a point set, screened Poisson reconstruction and quadric decimation.  Here the first two run on the device
 (csrc/surface_recon.hip): oriented normals from k nearest neighbours + visibility votes, a Poisson solve on a dense grid of
 2^depth cells per axis, marching cubes with welded vertices.  The mesh is this project's own (not pymeshlab's): a closed,
-consistently oriented triangle mesh, every component of the iso-surface included.  The third, decimation to a face count, is this
+consistently oriented triangle mesh, every component of the iso-surface included (`keep_components=` drops the small floating ones on the
+device: mesh_components.py).  The third, decimation to a face count, is this
 build's own as well (csrc/simplify_mesh.hip, `simplify_mesh` / `target_faces=`): quadric-error edge collapses in rounds of independent
 collapses on the device, topology preserved; pymeshlab's decimator is not reproduced."""
 import numpy as np
@@ -141,19 +142,27 @@ def _to_device(a, name):
 
 
 def recon_one_shape_SPR(coords, colors, gt_normals=None, save_path=None, depth=DEFAULT_DEPTH, simplify_face_num=None, *, knn=DEFAULT_KNN,
-                        return_counts=False, target_faces=None):
+                        return_counts=False, target_faces=None, keep_components=None):
     """baselines/spr.py:16-75 with its argument order and 3-tuple (vertices [Vn,3], faces [F,3], vertex_colors [Vn,3]), as GPU
     tensors.  coords / colors / gt_normals: GPU tensors or numpy arrays (numpy goes to the current device).  gt_normals None: the
     normals are estimated.  save_path: the mesh is written as an OBJ.  depth: 6, 7 or 8 (a dense grid of 2^depth cells per axis, not
     the reference's octree depth 12).  simplify_face_num: pymeshlab's decimation is not reproduced -- anything but None is refused.
     target_faces: this build's own decimator (simplify_mesh) after the reconstruction, before save_path is written; with return_counts
-    the dict gains faces_reconstructed and simplify_rounds."""
+    the dict gains faces_reconstructed and simplify_rounds.  keep_components: 'largest' or a dict of mesh_components.filter_components' rules
+    (keep, min_faces, min_face_share, min_diameter_share): the floating pieces of the iso-surface that fail them are dropped after the
+    reconstruction and BEFORE the decimation, so target_faces budgets only the kept geometry; the vertex colours are carried through and with
+    return_counts the dict gains components and components_kept (and faces_reconstructed).  None: nothing new is called."""
     if simplify_face_num is not None:
         raise NotImplementedError("recon_one_shape_SPR: pymeshlab's quadric edge-collapse decimation (simplify_face_num) is not reproduced; "
                                   "this build's own decimator is the keyword target_faces=")
     if int(depth) not in DEPTHS:
         raise ValueError(f"depth={depth}: the dense grid supports depth 6, 7 or 8 (2^depth cells per axis); the reference's default 12 "
                          "is an octree depth")
+    if keep_components is not None:
+        rules = dict(keep='largest') if keep_components == 'largest' else keep_components
+        if not isinstance(rules, dict) or not rules or any(k not in ('keep', 'min_faces', 'min_face_share', 'min_diameter_share') for k in rules):
+            raise ValueError(f"keep_components={keep_components!r}: 'largest' or a dict of filter_components' rules (keep, min_faces, "
+                             "min_face_share, min_diameter_share)")
     xyz = _to_device(coords, 'coords')
     rgb = _to_device(colors, 'colors')
     counts = None
@@ -162,9 +171,15 @@ def recon_one_shape_SPR(coords, colors, gt_normals=None, save_path=None, depth=D
     else:
         normals = _to_device(gt_normals, 'gt_normals')
     verts, faces, vcol, rc = poisson_reconstruct(xyz, normals, depth=depth, colors=rgb, return_counts=True)
+    if keep_components is not None:
+        from . import mesh_components
+        verts, faces, vcol, cc = mesh_components.filter_components(verts, faces, colors=vcol, return_counts=True, **rules)
+        rc = dict(rc, faces_reconstructed=rc['faces'], vertices=cc['vertices_after'], faces=cc['faces_after'], components=cc['components'],
+                  components_kept=cc['components_kept'], faces_dropped=cc['faces_before'] - cc['faces_after'])
     if target_faces is not None:
         verts, faces, vcol, sc = simplify_mesh(verts, faces, target_faces, colors=vcol, return_counts=True)
-        rc = dict(rc, faces_reconstructed=rc['faces'], vertices=sc['vertices'], faces=sc['faces'], simplify_rounds=sc['rounds'])
+        rc = dict(rc, faces_reconstructed=rc.get('faces_reconstructed', rc['faces']), vertices=sc['vertices'], faces=sc['faces'],
+                  simplify_rounds=sc['rounds'])
     if save_path is not None:
         from . import io_utils
         io_utils.save_obj_mesh(verts.cpu().numpy(), faces.cpu().numpy(), save_path)
