@@ -39,6 +39,14 @@ extern "C" {
 int pdhip_version(void);
 int pdhip_lab_build(void);   /* 0 for a product build; > 0: that many translation units carry a wrong-result PD_LAB_* timing switch (csrc/common.h) -- tests refuse such a library */
 const char* pdhip_last_error(void);
+/* test hook: the carve log.  While it is on, every region that a workspace-taking entry or a size query of the calling thread carves
+ * (csrc/common.h, Carve::take) is recorded as (base, offset, bytes); a size query records a null base.  Everything in a workspace outside
+ * the recorded regions is alignment slack that no kernel may touch.  on != 0 / 0 switches it on / off; either clears the log; returns the
+ * previous state.  Off by default, thread-local, host code only. */
+int pdhip_debug_carve_log(int on);
+/* copies out up to `capacity` recorded (base, offset, bytes) triples, 3 uint64 each, in the order they were carved, and returns how many
+ * regions were carved since the log was switched on: more than the 256 the log keeps, or more than capacity, means that some are missing */
+int pdhip_debug_carve_log_read(uint64_t* triples, int capacity);
 
 /* ---- P1: ours_utils.get_rendered_hard_mask_and_face_idx_batch, transform + crop part
  *      (pointdreamer/ours_utils.py:93-141).  minmax_ws: 4*V uint32 scratch.

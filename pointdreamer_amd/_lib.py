@@ -20,6 +20,8 @@ _SIGS = {
     'pdhip_version': (C.c_int, []),
     'pdhip_lab_build': (C.c_int, []),
     'pdhip_last_error': (C.c_char_p, []),
+    'pdhip_debug_carve_log': (C.c_int, [i32]),
+    'pdhip_debug_carve_log_read': (C.c_int, [vp, i32]),
     'pdhip_project_points': (C.c_int, [vp, i32, vp, i32, vp, i32, i32, f64, vp, vp, vp, vp, vp, vp, vp, vp]),
     'pdhip_project_points_shapes': (C.c_int, [vp, i32, i32, vp, i32, vp, i32, i32, f64, vp, vp, vp, vp, vp, vp, vp, vp]),
     'pdhip_raster_mesh_shapes': (C.c_int, [vp, i32, i32, i32, vp, i32, i32, vp, sz, vp, vp, vp, vp]),

@@ -60,12 +60,19 @@ static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b)
 
 // ---- caller-allocated workspaces: a unit's carve function hands out its regions through one Carve, and both the unit's
 // _ws_bytes query (base == nullptr: sizes only) and its entry (base == ws) call that function, so size and layout cannot disagree.
+// The carve log (pdhip_debug_carve_log, capi.hip; host code, thread-local, off by default) records every region a Carve hands out as
+// (base, offset, bytes), for a null base too, so that a test can hold an entry to its regions: every byte of the workspace outside them
+// is alignment slack, and must stay as the caller left it.
+extern __thread int g_carve_log;                          // (__thread: constant-initialised, so a read needs no thread_local init wrapper)
+void carve_record(const void* base, size_t off, size_t bytes);
+
 struct Carve {
     char* base;
     size_t off;
     template <class T> T* take(size_t n) {                         // n elements at the next multiple of 256 bytes
         off = bytes();
         T* p = reinterpret_cast<T*>(base ? base + off : nullptr);
+        if (g_carve_log) carve_record(base, off, n * sizeof(T));
         off += n * sizeof(T);
         return p;
     }

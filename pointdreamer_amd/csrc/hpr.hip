@@ -1527,7 +1527,7 @@ static size_t carve_hpr(HprWs& w, void* base, int V, int N) {
     Carve c{static_cast<char*>(base), 0};
     w.head = c.take<HprHead>(1);
     w.hist = c.take<int>((size_t)V * HPR_NCELL);
-    w.outside = c.take<uint8_t>((size_t)V * N);
+    w.outside = c.take<uint8_t>(((size_t)V * N + 255) & ~(size_t)255);   // (whole 256-byte lines: the one fill below runs across the region's end)
     w.csf = c.take<float4>((size_t)V * HPR_KC);                    // (entries past the set's end: the eye)
     w.pos_of = c.take<int>(lists);                                 // (the extremes' claim flags until the scatter fills it)
     w.mdir = c.take<int>(lists);

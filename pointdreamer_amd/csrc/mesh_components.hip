@@ -24,6 +24,7 @@ constexpr int TB = 256;
 constexpr int MAX_V = 1 << 26, MAX_F = 1 << 23;                    // the limits of the neighbouring entries (pdhip_knn_points, pdhip_simplify_mesh)
 constexpr int SMALL_SCAN = 16384;                                  // up to here the one-workgroup scan of radix_sort.h: one launch, not three
 enum { M_ERR = 0, M_CAP, M_C, M_NREF, M_WORDS = 8 };
+constexpr int MISC_LINE = 256 / sizeof(int);                        // carve_compact: misc as one whole 256-byte line (M_WORDS of it used)
 enum { ERR_INDEX = 1, ERR_NONFINITE = 2 };
 
 __device__ __forceinline__ int ld_agent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -304,7 +305,7 @@ struct CompactWs {
 static size_t carve_compact(CompactWs& w, void* base, int Vn, int F) {
     const size_t nv = (size_t)Vn, nf = (size_t)F;
     Carve c{static_cast<char*>(base), 0};
-    w.misc = c.take<int>(M_WORDS); w.vflag = c.take<int>(nv);
+    w.misc = c.take<int>(MISC_LINE); w.vflag = c.take<int>(nv);      // (a whole line: the one fill below clears misc and vflag, and what lies between)
     w.zero_bytes = c.off;
     w.vexcl = c.take<int>(nv); w.fflag = c.take<int>(nf); w.fexcl = c.take<int>(nf);
     const size_t tiles = scan_tiles(nv > nf ? nv : nf);

@@ -839,102 +839,17 @@ def test_i0_linear_inpaint_vs_scipy_delaunay(pd, case, local):
     assert np.array_equal(np.nan_to_num(N_(views)[0], nan=-1), np.nan_to_num(got, nan=-1))
 
 
-def _guard_hpr(pd, L, V, N):
-    rng = np.random.default_rng(N)
-    x = rng.standard_normal((N, 3))
-    x /= np.linalg.norm(x, axis=1, keepdims=True)
-    x[rng.uniform(0, 1, N) < 0.1] *= 0.5                                     # 10 % interior points
-    pts = T(x.astype(np.float32))
-    _, _, eyes, _ = pd['cu'].create_cameras(V, 1.6, 512, device=DEV)
-    eyes = T(np.asarray(eyes, np.float64).reshape(-1, 3))
-    P = pd['lib'].ptr
-
-    def run(ws):
-        vis = torch.full((V, N), 0xAA, dtype=torch.uint8, device=DEV)
-        assert L.pdhip_hidden_point_removal(P(pts), N, P(eyes), V, 100.0, None, P(vis), P(ws), pd['lib'].stream()) == 0
-        return [vis]
-    return L.pdhip_hpr_ws_bytes(V, N), run
-
-
-def _guard_optimize(pd, L, V=2, res=32, A=32, iters=3):
-    """inputs as test_optimize_color_vs_oracle builds them"""
-    from pointdreamer_amd import optimize as popt
-    verts, faces, _ = pd['syn'].uv_sphere(12, 24)
-    ocams, _, _, _ = ocam.create_cameras(V, 1.6, 64)
-    cams = make_cams(pd, [c.params for c in ocams], 64)
-    pr = oproj.project_batch(ocams, verts, verts[:4], True, 0.05)
-    rng = np.random.default_rng(5)
-    F_ = faces.shape[0]
-    g = int(np.ceil(np.sqrt(F_))); cell = 1.0 / g; fi = np.arange(F_)
-    ox, oy = (fi % g) * cell, (fi // g) * cell
-    uvs = np.stack([np.stack([ox + 0.05 * cell, oy + 0.05 * cell], -1), np.stack([ox + 0.95 * cell, oy + 0.05 * cell], -1),
-                    np.stack([ox + 0.05 * cell, oy + 0.95 * cell], -1)], 1).reshape(-1, 2).astype(np.float32)
-    tex = np.arange(F_ * 3).reshape(F_, 3)
-    uv_map, fidx = popt.texture_coordinates(cams, T(verts), T(faces), T(uvs), T(tex), T(pr['uv_centers']), T(pr['uv_scales']), 0.05,
-                                            T(np.ones(V, np.float32)), res)
-    atlas0 = T(rng.uniform(0, 1, (3, A, A)).astype(np.float32))
-    inp = T(rng.uniform(0, 1, (V, 3, 16, 16)).astype(np.float32))
-    shr = pd['lib'].as_u8(T(rng.uniform(0, 1, (V, A, A)) > 0.3))
-    P = pd['lib'].ptr
-
-    def run(ws):
-        atlas, final = atlas0.clone(), torch.empty((V, 3, res, res), device=DEV)
-        assert L.pdhip_optimize_color(P(atlas), A, P(uv_map), P(fidx), V, res, P(inp), 16, P(shr), 5e-2, iters, P(final), P(ws),
-                                      pd['lib'].stream()) == 0
-        assert not torch.equal(atlas, atlas0)
-        return [atlas, final]
-    return L.pdhip_optimize_color_ws_bytes(V, res, A), run
-
-
-def _guard_sparse(pd, L, V=2, N=500, res=32):
-    rng = np.random.default_rng(7)
-    pix = T(rng.integers(4, res - 4, (V, N, 2)).astype(np.int64))
-    col = T(rng.uniform(0, 1, (N, 3)).astype(np.float32))
-    val = T((rng.uniform(0, 1, (V, N)) > 0.3).astype(np.uint8))
-    yy, xx = np.mgrid[:res, :res]
-    hard = T(np.repeat((((yy - res / 2) ** 2 + (xx - res / 2) ** 2) < (0.4 * res) ** 2)[None], V, 0).astype(np.uint8))
-    P = pd['lib'].ptr
-
-    def run(ws):
-        out = [torch.empty((V, 3, res, res), device=DEV) for _ in range(3)] + [torch.empty((V,), device=DEV)]
-        assert L.pdhip_sparse_views(P(pix), P(col), P(val), P(hard), V, N, res, 1, 1, 0.82, P(out[0]), P(out[1]), P(out[2]), P(out[3]),
-                                    None, P(ws), pd['lib'].stream()) == 0
-        assert bool(out[0].any())
-        return out
-    return L.pdhip_sparse_views_ws_bytes(V, N, res), run
-
-
-def _guard_linear(pd, L, local, B=2, Cn=3, H=40, W=40):
-    rng = np.random.default_rng(9)
-    mask = T((rng.uniform(0, 1, (B, H, W)) < 0.3).astype(np.uint8))
-    img = T(rng.uniform(0, 1, (B, Cn, H, W)).astype(np.float32)) * mask[:, None]
-    P = pd['lib'].ptr
-
-    def run(ws):
-        out, tri = torch.empty_like(img), torch.empty((B, H, W, 3), dtype=torch.int32, device=DEV)
-        old = L.pdhip_debug_set_linear_local(local)
-        try:
-            assert L.pdhip_linear_fill(P(img), P(out), B, Cn, H, W, P(mask), 0, H * W, P(ws), P(tri), pd['lib'].stream()) == 0
-        finally:
-            L.pdhip_debug_set_linear_local(old)
-        return [out.view(torch.int32), tri]                                  # (bit patterns: pixels outside the hull are NaN)
-    return L.pdhip_linear_fill_ws_bytes(B, H, W), run
-
-
 @pytest.mark.parametrize("entry", ["hpr_one_level", "hpr_two_level", "optimize_color", "sparse_views", "linear_local", "linear_global"])
 def test_entries_stay_inside_the_workspace_their_query_reports(pd, entry):
     """Every entry that carves a workspace, on a dirty (0x55) buffer of pdhip_*_ws_bytes + 4096 bytes: the 4096 bytes behind the
     reported size keep their pattern, and the results equal those of a run on a zero-filled workspace of exactly the reported size.
-    Shapes: the smallest that reach every region (HPR: one level, and two levels since N > 4 * 1024)."""
-    L = pd['lib'].lib()
-    nbytes, run = {"hpr_one_level": lambda: _guard_hpr(pd, L, 4, 300), "hpr_two_level": lambda: _guard_hpr(pd, L, 2, 5000),
-                   "optimize_color": lambda: _guard_optimize(pd, L), "sparse_views": lambda: _guard_sparse(pd, L),
-                   "linear_local": lambda: _guard_linear(pd, L, 1), "linear_global": lambda: _guard_linear(pd, L, 0)}[entry]()
-    assert nbytes > 0
-    ws = torch.full((nbytes + 4096,), 0x55, dtype=torch.uint8, device=DEV)
-    got = run(ws)
-    assert bool((ws[nbytes:] == 0x55).all()), int((ws[nbytes:] != 0x55).sum())
-    assert not bool((ws[:nbytes] == 0x55).all())                             # (the entry did use it)
-    want = run(torch.zeros((nbytes,), dtype=torch.uint8, device=DEV))
-    for g, w in zip(got, want):
-        assert torch.equal(g, w)
+    Shapes: the smallest that reach every region (HPR: one level, and two levels since N > 4 * 1024).  The builders and the checks live in
+    tests/test_gpu_workspace.py, which runs these six rows and every other entry through them and also holds the slack between the regions."""
+    import test_gpu_workspace as tw
+    row = {"hpr_one_level": "one_level", "hpr_two_level": "two_level", "optimize_color": "parent", "sparse_views": "parent",
+           "linear_local": "parent", "linear_global": "parent"}[entry]
+    import workspace_common as wc
+    assert wc.SHAPES[tw.ENTRIES[entry][0]][row] == {"hpr_one_level": (4, 300), "hpr_two_level": (2, 5000), "optimize_color": (2, 32, 32),
+                                                    "sparse_views": (2, 500, 32), "linear_local": (2, 40, 40), "linear_global": (2, 40, 40)}[entry]
+    regions, slack, nbytes = tw.run_guarded(pd, entry, row)
+    assert nbytes > 0 and regions > 0

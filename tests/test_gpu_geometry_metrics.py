@@ -24,8 +24,8 @@ def T(a):
     return torch.from_numpy(np.array(a)).to(DEV)                  # (a writable copy: the cached clouds are read-only)
 
 
-def run_nearest(q, t, same_buffer=False, path=RING):
-    """(rc, d2, idx, counts) of pdhip_nearest_points; the outputs start as sentinels."""
+def run_nearest(q, t, same_buffer=False, path=RING, ws=None):
+    """(rc, d2, idx, counts) of pdhip_nearest_points; the outputs start as sentinels.  ws: the workspace to use instead of a fresh one."""
     from pointdreamer_amd import _lib
     from pointdreamer_amd._lib import ptr, stream
     L = _lib.lib()
@@ -35,7 +35,8 @@ def run_nearest(q, t, same_buffer=False, path=RING):
     d2 = torch.full((max(Q, 1),), SENT_D2, dtype=torch.float64, device=DEV)
     idx = torch.full((max(Q, 1),), SENT_IDX, dtype=torch.int32, device=DEV)
     counts = torch.full((4,), SENT_CNT, dtype=torch.int32, device=DEV)
-    ws = torch.empty((L.pdhip_nearest_points_workspace_bytes(Q, M),), dtype=torch.uint8, device=DEV)
+    if ws is None:
+        ws = torch.empty((L.pdhip_nearest_points_workspace_bytes(Q, M),), dtype=torch.uint8, device=DEV)
     old = L.pdhip_debug_set_nearest_path(path)
     try:
         rc = L.pdhip_nearest_points(ptr(tq), Q, ptr(tt), M, ptr(d2), ptr(idx), ptr(counts), ptr(ws), stream())
@@ -199,14 +200,15 @@ def test_no_queries_is_ok():
 
 
 # ---- pdhip_cloud_metrics
-def run_metrics(d2, idx, ns, nt, M, thresholds):
+def run_metrics(d2, idx, ns, nt, M, thresholds, ws=None):
     from pointdreamer_amd import _lib
     from pointdreamer_amd._lib import ptr, stream
     L = _lib.lib()
     thr = T(np.asarray(thresholds, np.float64))
     sums = torch.full((4,), -1.0, dtype=torch.float64, device=DEV)
     within = torch.full((len(thresholds),), -1, dtype=torch.int64, device=DEV)
-    ws = torch.empty((L.pdhip_cloud_metrics_workspace_bytes(len(thresholds)),), dtype=torch.uint8, device=DEV)
+    if ws is None:
+        ws = torch.empty((L.pdhip_cloud_metrics_workspace_bytes(len(thresholds)),), dtype=torch.uint8, device=DEV)
     d2t, idxt = T(np.asarray(d2, np.float64)), T(np.asarray(idx, np.int32))
     nst, ntt = (None if ns is None else T(np.asarray(ns, np.float32))), (None if nt is None else T(np.asarray(nt, np.float32)))
     rc = L.pdhip_cloud_metrics(ptr(d2t), ptr(idxt), len(d2), ptr(nst, allow_none=True), ptr(ntt, allow_none=True), M, ptr(thr), len(thresholds),

@@ -23,9 +23,9 @@ def restore_the_hook():
     assert _lib.lib().pdhip_debug_set_knn(0, 0) >= 0
 
 
-def run_knn(q, t, k, hook=(0, 0), null=None, Q=None, M=None):
+def run_knn(q, t, k, hook=(0, 0), null=None, Q=None, M=None, ws=None):
     """(rc, d2 [Q,k], idx [Q,k], counts) of pdhip_knn_points under pdhip_debug_set_knn(*hook); the outputs start as sentinels.  null: the name of an
-    argument passed as NULL.  Q / M: the sizes passed, when they are not the arrays' own."""
+    argument passed as NULL.  Q / M: the sizes passed, when they are not the arrays' own.  ws: the workspace to use instead of a fresh torch.empty one."""
     from pointdreamer_amd import _lib
     from pointdreamer_amd._lib import ptr, stream
     L = _lib.lib()
@@ -37,7 +37,8 @@ def run_knn(q, t, k, hook=(0, 0), null=None, Q=None, M=None):
     d2 = torch.full((max(rows, 1), cols), SENT_D2, dtype=torch.float64, device=DEV)
     idx = torch.full((max(rows, 1), cols), SENT_IDX, dtype=torch.int32, device=DEV)
     counts = torch.full((4,), SENT_CNT, dtype=torch.int32, device=DEV)
-    ws = torch.empty((max(L.pdhip_knn_points_workspace_bytes(Q, M, k), 8),), dtype=torch.uint8, device=DEV)
+    if ws is None:
+        ws = torch.empty((max(L.pdhip_knn_points_workspace_bytes(Q, M, k), 8),), dtype=torch.uint8, device=DEV)
     a = dict(queries=ptr(tq) if rows else None, targets=ptr(tt), d2=ptr(d2), idx=ptr(idx), counts=ptr(counts), ws=ptr(ws))
     if null is not None:
         a[null] = None

@@ -21,8 +21,8 @@ def T(a):
     return torch.from_numpy(np.array(a)).to(DEV)                  # (a writable copy: the cached arrays are read-only)
 
 
-def run_closest(v, f, p, want_closest=True):
-    """(rc, d2, face, closest, counts) of pdhip_closest_on_mesh; the outputs start as sentinels."""
+def run_closest(v, f, p, want_closest=True, ws=None):
+    """(rc, d2, face, closest, counts) of pdhip_closest_on_mesh; the outputs start as sentinels.  ws: the workspace to use instead of a fresh one."""
     from pointdreamer_amd import _lib
     from pointdreamer_amd._lib import ptr, stream
     L = _lib.lib()
@@ -32,7 +32,8 @@ def run_closest(v, f, p, want_closest=True):
     face = torch.full((max(Q, 1),), SENT_FACE, dtype=torch.int32, device=DEV)
     closest = torch.full((max(Q, 1), 3), SENT_D2, dtype=torch.float64, device=DEV)
     counts = torch.full((4,), SENT_CNT, dtype=torch.int32, device=DEV)
-    ws = torch.empty((max(L.pdhip_closest_on_mesh_workspace_bytes(Vn, F, Q), 8),), dtype=torch.uint8, device=DEV)
+    if ws is None:
+        ws = torch.empty((max(L.pdhip_closest_on_mesh_workspace_bytes(Vn, F, Q), 8),), dtype=torch.uint8, device=DEV)
     opt = lambda x: ptr(x) if x.numel() else None
     rc = L.pdhip_closest_on_mesh(ptr(tv), Vn, opt(tf), F, opt(tp), Q, ptr(d2), ptr(face), ptr(closest) if want_closest else None, ptr(counts), ptr(ws),
                                  stream())

@@ -20,8 +20,8 @@ def T(a):
     return torch.from_numpy(np.array(a)).to(DEV)                  # (a writable copy: the cached arrays are read-only)
 
 
-def run_contains(v, f, p, resolution=512):
-    """(rc, occ, counts) of pdhip_mesh_contains; the outputs start as sentinels."""
+def run_contains(v, f, p, resolution=512, ws=None):
+    """(rc, occ, counts) of pdhip_mesh_contains; the outputs start as sentinels.  ws: the workspace to use instead of a fresh one."""
     from pointdreamer_amd import _lib
     from pointdreamer_amd._lib import ptr, stream
     L = _lib.lib()
@@ -29,7 +29,8 @@ def run_contains(v, f, p, resolution=512):
     Vn, F, Q = tv.shape[0], tf.shape[0], tp.shape[0]
     occ = torch.full((max(Q, 1),), SENT_OCC, dtype=torch.uint8, device=DEV)
     counts = torch.full((4,), SENT_CNT, dtype=torch.int32, device=DEV)
-    ws = torch.empty((L.pdhip_mesh_contains_workspace_bytes(Vn, F, Q, resolution),), dtype=torch.uint8, device=DEV)
+    if ws is None:
+        ws = torch.empty((L.pdhip_mesh_contains_workspace_bytes(Vn, F, Q, resolution),), dtype=torch.uint8, device=DEV)
     assert ws.numel() > 0
     rc = L.pdhip_mesh_contains(ptr(tv), Vn, ptr(tf), F, ptr(tp, allow_none=True) if Q else None, Q, resolution, ptr(occ), ptr(counts), ptr(ws),
                                stream())

@@ -21,8 +21,8 @@ def T(a):
     return torch.from_numpy(np.array(a)).to(DEV)
 
 
-def run_sor(d2, ratio, null=None, N=None, kk=None):
-    """(rc, mean_d, stats, keep, kept_idx, counts) of pdhip_sor_filter; the outputs start as sentinels."""
+def run_sor(d2, ratio, null=None, N=None, kk=None, ws=None):
+    """(rc, mean_d, stats, keep, kept_idx, counts) of pdhip_sor_filter; the outputs start as sentinels.  ws: the workspace to use instead of a fresh one."""
     from pointdreamer_amd import _lib
     from pointdreamer_amd._lib import ptr, stream
     L = _lib.lib()
@@ -35,7 +35,8 @@ def run_sor(d2, ratio, null=None, N=None, kk=None):
     keep = torch.full((n,), SENT_U8, dtype=torch.uint8, device=DEV)
     kept_idx = torch.full((n,), SENT_I, dtype=torch.int32, device=DEV)
     counts = torch.full((4,), SENT_I, dtype=torch.int32, device=DEV)
-    ws = torch.empty((max(L.pdhip_sor_filter_workspace_bytes(N), 8),), dtype=torch.uint8, device=DEV)
+    if ws is None:
+        ws = torch.empty((max(L.pdhip_sor_filter_workspace_bytes(N), 8),), dtype=torch.uint8, device=DEV)
     a = dict(knn_d2=ptr(td), mean_d=ptr(mean_d), stats=ptr(stats), keep=ptr(keep), kept_idx=ptr(kept_idx), counts=ptr(counts), ws=ptr(ws))
     if null is not None:
         a[null] = None

@@ -20,8 +20,9 @@ def T(a):
     return torch.from_numpy(np.array(a)).to(DEV)                  # (a writable copy: the cached clouds are read-only)
 
 
-def run_fps(points, M, start=0, null=None, N=None):
-    """(rc, idx, min_d2, counts) of pdhip_fps; the outputs start as sentinels.  null: the name of an argument passed as NULL."""
+def run_fps(points, M, start=0, null=None, N=None, ws=None):
+    """(rc, idx, min_d2, counts) of pdhip_fps; the outputs start as sentinels.  null: the name of an argument passed as NULL.  ws: the workspace to use instead of a
+    fresh torch.empty one."""
     from pointdreamer_amd import _lib
     from pointdreamer_amd._lib import ptr, stream
     L = _lib.lib()
@@ -31,7 +32,8 @@ def run_fps(points, M, start=0, null=None, N=None):
     idx = torch.full((cap,), SENT_IDX, dtype=torch.int32, device=DEV)
     d2 = torch.full((cap,), SENT_D2, dtype=torch.float64, device=DEV)
     counts = torch.full((4,), SENT_CNT, dtype=torch.int32, device=DEV)
-    ws = torch.empty((max(L.pdhip_fps_workspace_bytes(N, M), 8),), dtype=torch.uint8, device=DEV)
+    if ws is None:
+        ws = torch.empty((max(L.pdhip_fps_workspace_bytes(N, M), 8),), dtype=torch.uint8, device=DEV)
     a = dict(points=ptr(tp), idx=ptr(idx), min_d2=ptr(d2), counts=ptr(counts), ws=ptr(ws))
     if null is not None:
         a[null] = None
@@ -135,13 +137,14 @@ def test_python_wrapper_returns_int64_picks_and_subsample_cloud_gathers():
 
 
 # ---- mean colours
-def run_mean(owner, colors, M, fallback, with_ws=True, null=None):
+def run_mean(owner, colors, M, fallback, with_ws=True, null=None, ws=None):
     from pointdreamer_amd import _lib
     from pointdreamer_amd._lib import ptr, stream
     L = _lib.lib()
     to, tc, tf = T(np.asarray(owner, np.int32)), T(np.asarray(colors, np.float32)), T(np.asarray(fallback, np.float32))
     out = torch.full((M, 3), SENT_COL, dtype=torch.float32, device=DEV)
-    ws = torch.empty((L.pdhip_owner_mean_colors_workspace_bytes(M),), dtype=torch.uint8, device=DEV)
+    if ws is None:
+        ws = torch.empty((L.pdhip_owner_mean_colors_workspace_bytes(M),), dtype=torch.uint8, device=DEV)
     a = dict(owner=ptr(to), colors=ptr(tc), fallback=ptr(tf), out=ptr(out))
     if null is not None:
         a[null] = None

@@ -1,0 +1,627 @@
+"""Every workspace-taking entry of libpdhip, held to the regions it carves, on dirty memory.  The Python wrappers hand every entry a torch.empty
+workspace of exactly the size its query reports: uninitialised, with the next tensor of torch's pool right behind it.  Per entry and shape (a row):
+
+  1. the workspace is nbytes + 4096 bytes of 0x55, the carve log (pdhip_debug_carve_log) is on, the outputs start as sentinels;
+  2. every Carve the entry made lies inside the workspace and inside nbytes, aligned and ascending (workspace_common.check_layout);
+  3. every byte outside the logged regions -- the slack in front of each multiple of 256, the `+ 256` behind the last region, the tail -- still
+     holds 0x55: no kernel wrote past a region, inner ones included;
+  4. the entry did write into the workspace;
+  5. two runs on zero-filled workspaces of exactly nbytes give equal bytes, and the run on the dirty workspace gives those bytes too: nothing is
+     read before it is written.  Every output is compared: the whole sentinel-filled buffers where the row calls the C entry itself (what lies
+     behind a kept prefix included), and what the per-unit call helpers return (host copies, cut to the Q rows passed) where it goes through one.
+
+An entry that sizes its workspace without a Carve (test_workspace_cpu.NO_CARVE) is one region of nbytes, or the regions read off its code (NO_CARVE
+below): the tail, 4 and 5 apply.
+Shapes: workspace_common.SHAPES -- ragged (above one 2048-element tile, no multiple of 64), exact tile, the entry's minimum, and the far side of every
+switch by size or debug hook.  They are the smallest at which a region size can be wrong, not the workload's."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import workspace_common as wc
+from oracle import camera as ocam, project as oproj
+
+DEV = 'cuda:0'
+TAIL, FILL = 4096, 0x55
+UNIT = {'pdhip_nearest_fill_ws_ints': 4}                           # bytes per unit of what the query returns
+# the entries that size their workspace without a Carve (test_workspace_cpu.NO_CARVE pins the set), with the regions read off the code where the size
+# is more than its arrays: pdhip_vertex_uv_table uses V ints of its V * 4 + 256 bytes (neighbor_mesh.hip)
+NO_CARVE = {'pdhip_raster_mesh_ws_bytes': None, 'pdhip_nearest_fill_ws_ints': None, 'pdhip_vertex_uv_table_ws_bytes': lambda V, F: [[0, 4 * V]]}
+
+
+@pytest.fixture(scope="module")
+def pd():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    import pointdreamer_amd.camera_utils as cu
+    from pointdreamer_amd import synthetic, _lib
+    _lib.lib()
+    return dict(cu=cu, syn=synthetic, lib=_lib)
+
+
+def T(a, dtype=None):
+    t = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    return t if dtype is None else t.to(dtype)
+
+
+def full(shape, value, dtype):
+    return torch.full(shape, value, dtype=dtype, device=DEV)
+
+
+# ---- inputs
+def torus(a, b, R=0.35, r=0.12):
+    """A closed, consistently oriented torus of a x b quads, counter-clockwise seen from outside: (vertices [ab,3] f32, faces [2ab,3] i64)."""
+    i, j = np.meshgrid(np.arange(a), np.arange(b), indexing='ij')
+    th, ph = 2 * np.pi * i / a, 2 * np.pi * j / b
+    v = np.stack([(R + r * np.cos(ph)) * np.cos(th), (R + r * np.cos(ph)) * np.sin(th), r * np.sin(ph)], -1).reshape(-1, 3).astype(np.float32)
+    vid = lambda ii, jj: (ii % a) * b + (jj % b)
+    q = np.stack([vid(i, j), vid(i + 1, j), vid(i + 1, j + 1), vid(i, j + 1)], -1).reshape(-1, 4)
+    f = np.concatenate([q[:, [0, 1, 2]], q[:, [0, 2, 3]]], 1).reshape(-1, 3).astype(np.int64)
+    return v, f
+
+
+TETRA = (np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], np.float32) * np.float32(0.5),
+         np.array([[0, 2, 1], [0, 1, 3], [0, 3, 2], [1, 2, 3]], np.int64))
+# the smallest closed mesh above the tetrahedron: pdhip_simplify_mesh copies a mesh through without touching its workspace when target_faces >= F, and
+# refuses target_faces < 4, so F = 6 with target 4 is the smallest call that carves
+BIPYRAMID = (np.array([[0.4, 0, 0], [-0.2, 0.35, 0], [-0.2, -0.35, 0], [0, 0, 0.4], [0, 0, -0.4]], np.float32),
+             np.array([[0, 1, 3], [1, 2, 3], [2, 0, 3], [1, 0, 4], [2, 1, 4], [0, 2, 4]], np.int64))
+TRIANGLE = (np.array([[0.1, 0.0, 0.2], [0.4, 0.1, 0.0], [0.0, 0.5, 0.1]], np.float32), np.array([[0, 1, 2]], np.int64))
+
+
+def mesh(Vn, F):
+    """The mesh with exactly Vn vertices and F faces: a torus of workspace_common.TORUS, the tetrahedron, the bipyramid, or one triangle."""
+    for a, b in wc.TORUS.values():
+        if (a * b, 2 * a * b) == (Vn, F):
+            return torus(a, b)
+    return {(4, 4): TETRA, (5, 6): BIPYRAMID, (3, 1): TRIANGLE}[(Vn, F)]
+
+
+def mesh_of_faces(F):
+    return mesh({4230: 2115, 4096: 2048, 1: 3}[F], F)
+
+
+def sphere_cloud(n, seed):
+    v = np.random.default_rng(seed).standard_normal((n, 3))
+    nrm = v / np.linalg.norm(v, axis=1, keepdims=True)
+    return (0.5 * nrm).astype(np.float32), nrm.astype(np.float32)
+
+
+def ok(rc):
+    assert rc == 0, rc
+
+
+# ---- the rows: builder(pd, L, *query arguments) -> run(ws) -> [outputs] (tensors or numpy arrays)
+def b_knn(pd, L, Q, M, k, hook=(0, 0)):
+    import test_gpu_knn as t
+    rng = np.random.default_rng(Q + M)
+    q, tg = rng.random((Q, 3), dtype=np.float32), rng.random((M, 3), dtype=np.float32)
+
+    def run(ws):
+        out = t.run_knn(q, tg, k, hook, ws=ws)
+        ok(out[0])
+        return list(out[1:])
+    return run
+
+
+def b_sor(pd, L, N):
+    import test_gpu_outliers as t
+    kk = 6 if N > 2 else 2
+    d2 = np.sort(np.random.default_rng(N).random((N, kk)), axis=1)
+    d2[:, 0] = 0.0
+
+    def run(ws):
+        out = t.run_sor(d2, 2.0, ws=ws)
+        ok(out[0])
+        return list(out[1:])
+    return run
+
+
+def b_fps(pd, L, N, M):
+    import test_gpu_subsample as t
+    p = np.random.default_rng(N + M).random((N, 3), dtype=np.float32)
+
+    def run(ws):
+        out = t.run_fps(p, M, 0, ws=ws)
+        ok(out[0])
+        return list(out[1:])
+    return run
+
+
+def b_owner_mean(pd, L, M):
+    import test_gpu_subsample as t
+    rng = np.random.default_rng(M)
+    N = 3 * M + 1
+    owner, colors, fallback = rng.integers(0, M, N).astype(np.int32), rng.random((N, 3), dtype=np.float32), rng.random((M, 3), dtype=np.float32)
+
+    def run(ws):
+        rc, out = t.run_mean(owner, colors, M, fallback, ws=ws)
+        ok(rc)
+        return [out]
+    return run
+
+
+def b_nearest(pd, L, Q, M, path=0):
+    import test_gpu_geometry_metrics as t
+    rng = np.random.default_rng(Q + M)
+    q, tg = rng.random((Q, 3), dtype=np.float32), rng.random((M, 3), dtype=np.float32)
+
+    def run(ws):
+        out = t.run_nearest(q, tg, path=path, ws=ws)
+        ok(out[0])
+        return list(out[1:])
+    return run
+
+
+def b_cloud_metrics(pd, L, Tn):
+    import test_gpu_geometry_metrics as t
+    rng = np.random.default_rng(Tn)
+    Q, M = {2113: 5003, 2048: 2048, 1: 1}[Tn], 2113
+    d2, idx = rng.random(Q), rng.integers(0, M, Q).astype(np.int32)
+    ns, nt = rng.standard_normal((Q, 3)).astype(np.float32), rng.standard_normal((M, 3)).astype(np.float32)
+    thr = np.sort(rng.random(Tn))
+    return lambda ws: list(t.run_metrics(d2, idx, ns, nt, M, thr, ws=ws))
+
+
+def b_contains(pd, L, Vn, F, Q, R):
+    import test_gpu_occupancy as t
+    v, f = mesh(Vn, F)
+    p = np.random.default_rng(Q).uniform(-0.6, 0.6, (Q, 3)).astype(np.float32)
+
+    def run(ws):
+        out = t.run_contains(v, f, p, R, ws=ws)
+        ok(out[0])
+        return list(out[1:])
+    return run
+
+
+def b_closest(pd, L, Vn, F, Q, hook=(0, 0)):
+    import test_gpu_mesh_distance as t
+    v, f = mesh(Vn, F)
+    p = np.random.default_rng(Q).uniform(-0.6, 0.6, (Q, 3)).astype(np.float32)
+
+    def run(ws):
+        L.pdhip_debug_set_closest_on_mesh(*hook)
+        try:
+            out = t.run_closest(v, f, p, ws=ws)
+        finally:
+            L.pdhip_debug_set_closest_on_mesh(0, 0)
+        ok(out[0])
+        return list(out[1:])
+    return run
+
+
+def b_components(pd, L, Vn, F):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    v, f = (T(x) for x in mesh(Vn, F))
+    cap = 8
+
+    def run(ws):
+        vcomp, fcomp = full((Vn,), -77, torch.int32), full((F,), -77, torch.int32)
+        root, nv, nf = (full((cap,), -77, torch.int32) for _ in range(3))
+        box, counts = full((cap, 6), -7.0, torch.float32), full((4,), -777, torch.int32)
+        ok(L.pdhip_mesh_components(P(f), F, P(v), Vn, P(vcomp), P(fcomp), P(root), P(nv), P(nf), P(box), cap, P(counts), P(ws), S()))
+        assert counts.tolist()[0] == 1                             # (one piece)
+        return [vcomp, fcomp, root, nv, nf, box, counts]
+    return run
+
+
+def b_compact(pd, L, Vn, F):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    v, f = (T(x) for x in mesh(Vn, F))
+    rng = np.random.default_rng(F)
+    col = T(rng.random((Vn, 3), dtype=np.float32))
+    keep = T((rng.random(F) > 0.3).astype(np.uint8) if F > 1 else np.ones(1, np.uint8))
+
+    def run(ws):
+        ov, oc, of = full((Vn, 3), -7.0, torch.float32), full((Vn, 3), -5.0, torch.float32), full((F, 3), -77, torch.int64)
+        vmap, counts = full((Vn,), -77, torch.int32), full((4,), -777, torch.int32)
+        ok(L.pdhip_compact_mesh(P(v), Vn, P(f), F, P(col), P(keep), P(ov), P(of), P(oc), P(vmap), P(counts), P(ws), S()))
+        return [ov, of, oc, vmap, counts]
+    return run
+
+
+def b_simplify(pd, L, Vn, F):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    v, f = (T(x) for x in mesh(Vn, F))
+    col = T(np.random.default_rng(F).random((Vn, 3), dtype=np.float32))
+
+    def run(ws):
+        ov, oc, of = full((Vn, 3), -7.0, torch.float32), full((Vn, 3), -5.0, torch.float32), full((F, 3), -77, torch.int64)
+        counts = full((4,), -777, torch.int32)
+        ok(L.pdhip_simplify_mesh(P(v), Vn, P(f), F, P(col), max(4, F // 2), P(ov), P(of), P(oc), P(counts), P(ws), S()))    # (the bipyramid may stall: PDHIP_OK)
+        return [ov, of, oc, counts]
+    return run
+
+
+def b_sample(pd, L, F, N):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    v, f = (T(x) for x in mesh_of_faces(F))
+    Vn = v.shape[0]
+    rand = T(np.random.default_rng(F + N).random((N, 3), dtype=np.float32))
+    off, wh, kd = T(np.zeros(1, np.int64)), T(np.zeros((1, 2), np.int32)), T(np.array([[0.2, 0.5, 0.7]], np.float32))
+
+    def run(ws):
+        co, cl, nr = (full((N, 3), -7.0, torch.float32) for _ in range(3))
+        uv, fi, mi = full((N, 2), -7.0, torch.float32), full((N,), -77, torch.int32), full((N,), -77, torch.int32)
+        ok(L.pdhip_sample_mesh(P(v), Vn, P(f), F, None, 0, None, None, None, None, 0, P(off), P(wh), P(kd), 1, P(rand), N, P(co), P(cl), P(nr),
+                               P(uv), P(fi), P(mi), P(ws), S()))
+        return [co, cl, nr, uv, fi, mi]
+    return run
+
+
+def b_uv_atlas(pd, L, Vn, F):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    v, f = (T(x) for x in mesh(Vn, F))
+
+    def run(ws):
+        uvs, tex, chart = full((3 * F, 2), -7.0, torch.float32), full((F, 3), -77, torch.int64), full((F,), -77, torch.int32)
+        counts = full((4,), -777, torch.int32)
+        ok(L.pdhip_uv_atlas(P(v), Vn, P(f), F, 512, 2, P(uvs), P(tex), P(chart), P(counts), P(ws), S()))
+        return [uvs, tex, chart, counts]
+    return run
+
+
+def b_normals(pd, L, N, k, eyes):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    p = T(sphere_cloud(N, N)[0])
+
+    def run(ws):
+        nrm, counts = full((N, 3), -7.0, torch.float32), full((4,), -777, torch.int32)
+        ok(L.pdhip_estimate_normals(P(p), N, k, eyes, 2.0, P(nrm), P(counts), P(ws), S()))
+        return [nrm, counts]
+    return run
+
+
+def b_recon(pd, L, N, depth):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    p, n = (T(x) for x in sphere_cloud(N, N))
+    vcap, fcap = 8 << (2 * depth), 16 << (2 * depth)              # (spr.capacities)
+
+    def run(ws):
+        vb, fb = full((vcap, 3), -7.0, torch.float32), full((fcap, 3), -77, torch.int64)
+        counts, info = full((4,), -777, torch.int32), full((8,), -7.0, torch.float32)
+        ok(L.pdhip_surface_recon(P(p), P(n), None, N, depth, P(vb), vcap, P(fb), fcap, None, P(counts), P(info), P(ws), S()))
+        return [vb, fb, counts, info]
+    return run
+
+
+def b_subdivide(pd, L, V, U, F, K):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    v, f = (T(x) for x in mesh(V, F))
+    assert U == V                                                  # one UV per vertex: the UV index space is the vertex index space
+    rng = np.random.default_rng(K)
+    u, fi = T(rng.random((U, 2), dtype=np.float32)), T(np.sort(rng.choice(F, K, replace=False)).astype(np.int64))
+
+    def run(ws):
+        out = [full((V + 3 * K, 3), -7.0, torch.float32), full((F + 3 * K, 3), -77, torch.int64), full((U + 3 * K, 2), -7.0, torch.float32),
+               full((F + 3 * K, 3), -77, torch.int64)]
+        counts, host = full((4,), -777, torch.int32), (ctypes.c_int32 * 4)()
+        ok(L.pdhip_subdivide_with_uv(P(v), V, P(f), F, P(u), U, P(f), P(fi), K, *[P(o) for o in out], P(counts), host, P(ws), S()))
+        assert list(host) == counts.tolist() and host[3] == K
+        return out + [counts]
+    return run
+
+
+def b_uv_table(pd, L, V, F):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    f = T(mesh(V, F)[1])
+    u = T(np.random.default_rng(V).random((V, 2), dtype=np.float32))
+
+    def run(ws):
+        out, counts = full((V, 2), -7.0, torch.float32), full((1,), -777, torch.int32)
+        ok(L.pdhip_vertex_uv_table(V, P(f), P(f), F, P(u), V, P(out), P(counts), P(ws), S()))
+        return [out, counts]
+    return run
+
+
+def b_csr(pd, L, V, F):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    f = T(mesh(V, F)[1])
+
+    def run(ws):
+        rowptr, colidx, counts = full((V + 1,), -77, torch.int32), full((6 * F,), -77, torch.int32), full((1,), -777, torch.int32)
+        host = (ctypes.c_int32 * 1)()
+        ok(L.pdhip_neighbour_csr(V, P(f), F, P(rowptr), P(colidx), P(counts), host, P(ws), S()))
+        assert host[0] == counts.tolist()[0] > 0
+        return [rowptr, colidx, counts]
+    return run
+
+
+def b_zero_count(pd, L, V):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    c = T((np.random.default_rng(V).random(V) > 0.4).astype(np.float32))
+
+    def run(ws):
+        out, counts, host = full((V,), -77, torch.int32), full((1,), -777, torch.int32), (ctypes.c_int32 * 1)()
+        ok(L.pdhip_compact_zero_count(P(c), V, P(out), P(counts), host, P(ws), S()))
+        return [out, counts]
+    return run
+
+
+def b_image_metrics(pd, L, N, H, W):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    rng = np.random.default_rng(H * W)
+    a, b = (T(rng.integers(0, 256, (N, H, W, 3), dtype=np.uint8)) for _ in range(2))
+    gaussian = 1 if min(H, W) >= 11 and H == W else 0             # (the exact-tile row under the 11 x 11 Gaussian, the others under the 7 x 7 window)
+
+    def run(ws):
+        sse, ssim = full((N,), -77, torch.int64), full((N,), -7.0, torch.float64)
+        ok(L.pdhip_image_metrics(P(a), P(b), N, H, W, 3, gaussian, P(sse), P(ssim), P(ws), S()))
+        return [sse, ssim]
+    return run
+
+
+def b_raster(pd, L, V, F, R, path=0):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    v, f = mesh_of_faces(F)
+    v, f32 = T(v), T(f.astype(np.int32))
+    Vn = v.shape[0]
+    cams = pd['cu'].create_cameras(max(V, 2), 1.6, R, device=DEV)[0][:V]      # (the Fibonacci sphere needs two views)
+    cp = pd['cu'].stack_params(cams)
+    pos, vuv, mm = torch.empty((V, Vn, 4), device=DEV), torch.empty((V, Vn, 2), device=DEV), torch.empty((4 * V,), dtype=torch.int32, device=DEV)
+    ok(L.pdhip_project_points(P(cp), V, P(v), Vn, None, 0, 0, 0.0, P(pos), P(vuv), None, None, None, None, P(mm), S()))
+    nbytes = L.pdhip_raster_mesh_ws_bytes(V, F, R)
+
+    def run(ws):
+        hard, fidx, depth = full((V, R, R), 0xAA, torch.uint8), full((V, R, R), -77, torch.int64), full((V, R, R), -7.0, torch.float32)
+        old = L.pdhip_debug_set_raster_path(path)
+        try:
+            ok(L.pdhip_raster_mesh_ws(P(pos), V, Vn, P(f32), F, R, P(ws), nbytes, P(hard), P(fidx), P(depth), S()))
+        finally:
+            L.pdhip_debug_set_raster_path(old)
+        return [hard, fidx, depth]
+    return run
+
+
+def b_nearest_fill(pd, L, B, H, W):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    rng = np.random.default_rng(H * W)
+    mask = (rng.random((B, H, W)) < 0.3).astype(np.uint8)
+    mask[:, 0, 0] = 1                                              # (every image has a site)
+    mask, img = T(mask), T(rng.random((B, 3, H, W), dtype=np.float32))
+
+    def run(ws):
+        out = full((B, 3, H, W), -7.0, torch.float32)
+        ok(L.pdhip_nearest_fill(P(img), P(out), B, 3, H, W, 3 * H * W, H * W, 1, P(mask), 0, H * W, P(ws), S()))
+        return [out]
+    return run
+
+
+# the six cases of test_gpu_geometry.py::test_entries_stay_inside_the_workspace_their_query_reports, moved here with their shapes as arguments
+def b_hpr(pd, L, V, N):
+    rng = np.random.default_rng(N)
+    x = rng.standard_normal((N, 3))
+    x /= np.linalg.norm(x, axis=1, keepdims=True)
+    x[rng.uniform(0, 1, N) < 0.1] *= 0.5                                     # 10 % interior points
+    pts = T(x.astype(np.float32))
+    _, _, eyes, _ = pd['cu'].create_cameras(max(V, 2), 1.6, 512, device=DEV)          # (the Fibonacci sphere needs two views)
+    eyes = T(np.asarray(eyes.cpu() if torch.is_tensor(eyes) else eyes, np.float64).reshape(-1, 3)[:V])
+    P = pd['lib'].ptr
+
+    def run(ws):
+        vis = torch.full((V, N), 0xAA, dtype=torch.uint8, device=DEV)
+        assert L.pdhip_hidden_point_removal(P(pts), N, P(eyes), V, 100.0, None, P(vis), P(ws), pd['lib'].stream()) == 0
+        return [vis]
+    return run
+
+
+def b_optimize(pd, L, V, res, A, iters=3):
+    """inputs as test_optimize_color_vs_oracle builds them"""
+    from pointdreamer_amd import optimize as popt
+    verts, faces, _ = pd['syn'].uv_sphere(12, 24)
+    ocams = ocam.create_cameras(max(V, 2), 1.6, 64)[0][:V]                  # (the Fibonacci sphere needs two views)
+    cams = [pd['cu'].Camera(c.params, 64, DEV) for c in ocams]
+    pr = oproj.project_batch(ocams, verts, verts[:4], True, 0.05)
+    rng = np.random.default_rng(5)
+    F_ = faces.shape[0]
+    g = int(np.ceil(np.sqrt(F_))); cell = 1.0 / g; fi = np.arange(F_)
+    ox, oy = (fi % g) * cell, (fi // g) * cell
+    uvs = np.stack([np.stack([ox + 0.05 * cell, oy + 0.05 * cell], -1), np.stack([ox + 0.95 * cell, oy + 0.05 * cell], -1),
+                    np.stack([ox + 0.05 * cell, oy + 0.95 * cell], -1)], 1).reshape(-1, 2).astype(np.float32)
+    tex = np.arange(F_ * 3).reshape(F_, 3)
+    uv_map, fidx = popt.texture_coordinates(cams, T(verts), T(faces), T(uvs), T(tex), T(pr['uv_centers']), T(pr['uv_scales']), 0.05,
+                                            T(np.ones(V, np.float32)), res)
+    atlas0 = T(rng.uniform(0, 1, (3, A, A)).astype(np.float32))
+    inp = T(rng.uniform(0, 1, (V, 3, 16, 16)).astype(np.float32))
+    shr = pd['lib'].as_u8(T(rng.uniform(0, 1, (V, A, A)) > 0.3))
+    P = pd['lib'].ptr
+
+    def run(ws):
+        atlas, final = atlas0.clone(), torch.empty((V, 3, res, res), device=DEV)
+        assert L.pdhip_optimize_color(P(atlas), A, P(uv_map), P(fidx), V, res, P(inp), 16, P(shr), 5e-2, iters, P(final), P(ws),
+                                      pd['lib'].stream()) == 0
+        assert A < 32 or not torch.equal(atlas, atlas0)
+        return [atlas, final]
+    return run
+
+
+def b_sparse(pd, L, V, N, res):
+    rng = np.random.default_rng(7)
+    lo = min(4, res // 4)
+    pix = T(rng.integers(lo, res - lo, (V, N, 2)).astype(np.int64))
+    col = T(rng.uniform(0, 1, (N, 3)).astype(np.float32))
+    val = T((rng.uniform(0, 1, (V, N)) > 0.3).astype(np.uint8))
+    yy, xx = np.mgrid[:res, :res]
+    hard = T(np.repeat((((yy - res / 2) ** 2 + (xx - res / 2) ** 2) < (0.4 * res) ** 2)[None], V, 0).astype(np.uint8))
+    P = pd['lib'].ptr
+
+    def run(ws):
+        out = [torch.empty((V, 3, res, res), device=DEV) for _ in range(3)] + [torch.empty((V,), device=DEV)]
+        assert L.pdhip_sparse_views(P(pix), P(col), P(val), P(hard), V, N, res, 1, 1, 0.82, P(out[0]), P(out[1]), P(out[2]), P(out[3]),
+                                    None, P(ws), pd['lib'].stream()) == 0
+        assert N < 100 or bool(out[0].any())                                # (a single point may be invalid in its view)
+        return out
+    return run
+
+
+def b_linear(pd, L, B, H, W, local=1, Cn=3):
+    rng = np.random.default_rng(9)
+    m = (rng.uniform(0, 1, (B, H, W)) < 0.3).astype(np.uint8)
+    if H * W < 100:
+        m[:, 0, 0] = 1                                                       # (a 1 x 1 image has its site)
+    mask = T(m)
+    img = T(rng.uniform(0, 1, (B, Cn, H, W)).astype(np.float32)) * mask[:, None]
+    P = pd['lib'].ptr
+
+    def run(ws):
+        out, tri = torch.empty_like(img), torch.empty((B, H, W, 3), dtype=torch.int32, device=DEV)
+        old = L.pdhip_debug_set_linear_local(local)
+        try:
+            assert L.pdhip_linear_fill(P(img), P(out), B, Cn, H, W, P(mask), 0, H * W, P(ws), P(tri), pd['lib'].stream()) == 0
+        finally:
+            L.pdhip_debug_set_linear_local(old)
+        return [out.view(torch.int32), tri]                                  # (bit patterns: pixels outside the hull are NaN)
+    return run
+
+
+# entry -> (size query, builder, {row: extra builder arguments}); the shapes are workspace_common.SHAPES[query][row name up to '+']
+ENTRIES = {
+    'knn_points': ('pdhip_knn_points_workspace_bytes', b_knn, {'ragged': {}, 'tile': {}, 'min': {}, 'ragged+sweep': dict(hook=(0, 1)),
+                                                               'ragged+box_grid': dict(hook=(0, 2)), 'tile+one_cell': dict(hook=(1, 0))}),
+    'sor_filter': ('pdhip_sor_filter_workspace_bytes', b_sor, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'fps': ('pdhip_fps_workspace_bytes', b_fps, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'owner_mean_colors': ('pdhip_owner_mean_colors_workspace_bytes', b_owner_mean, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'nearest_points': ('pdhip_nearest_points_workspace_bytes', b_nearest, {'ragged': {}, 'tile': {}, 'min': {}, 'ragged+staged': dict(path=1),
+                                                                           'tile+staged': dict(path=1)}),
+    'cloud_metrics': ('pdhip_cloud_metrics_workspace_bytes', b_cloud_metrics, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'mesh_contains': ('pdhip_mesh_contains_workspace_bytes', b_contains, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'closest_on_mesh': ('pdhip_closest_on_mesh_workspace_bytes', b_closest, {'ragged': {}, 'tile': {}, 'min': {}, 'ragged+large_list': dict(hook=(0, 1)),
+                                                                             'ragged+all_faces': dict(hook=(0, 2))}),
+    'mesh_components': ('pdhip_mesh_components_workspace_bytes', b_components, {'ragged': {}, 'tile': {}, 'min': {}, 'switch': {}}),
+    'compact_mesh': ('pdhip_compact_mesh_workspace_bytes', b_compact, {'ragged': {}, 'tile': {}, 'min': {}, 'switch': {}}),   # (scan_flags: both scans tiled)
+    'simplify_mesh': ('pdhip_simplify_mesh_workspace_bytes', b_simplify, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'sample_mesh': ('pdhip_sample_mesh_workspace_bytes', b_sample, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'uv_atlas': ('pdhip_uv_atlas_ws_bytes', b_uv_atlas, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'estimate_normals': ('pdhip_estimate_normals_ws_bytes', b_normals, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'surface_recon': ('pdhip_surface_recon_ws_bytes', b_recon, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'subdivide_with_uv': ('pdhip_subdivide_with_uv_ws_bytes', b_subdivide, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'vertex_uv_table': ('pdhip_vertex_uv_table_ws_bytes', b_uv_table, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'neighbour_csr': ('pdhip_neighbour_csr_ws_bytes', b_csr, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'compact_zero_count': ('pdhip_compact_zero_count_ws_bytes', b_zero_count, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'image_metrics': ('pdhip_image_metrics_workspace_bytes', b_image_metrics, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'raster_mesh_ws': ('pdhip_raster_mesh_ws_bytes', b_raster, {'ragged': {}, 'tile': {}, 'min': {}, 'ragged+atomic': dict(path=1),
+                                                               'tile+atomic': dict(path=1)}),
+    'nearest_fill': ('pdhip_nearest_fill_ws_ints', b_nearest_fill, {'ragged': {}, 'tile': {}, 'min': {}}),
+    # the six existing cases (HPR: one level up to 4 * 1024 points, two levels above)
+    'hpr_one_level': ('pdhip_hpr_ws_bytes', b_hpr, {'one_level': {}, 'tile': {}, 'min': {}}),
+    'hpr_two_level': ('pdhip_hpr_ws_bytes', b_hpr, {'two_level': {}, 'ragged': {}, 'two_tiles': {}}),
+    'optimize_color': ('pdhip_optimize_color_ws_bytes', b_optimize, {'parent': {}, 'ragged': {}, 'tile': {}, 'min': {}}),
+    'sparse_views': ('pdhip_sparse_views_ws_bytes', b_sparse, {'parent': {}, 'ragged': {}, 'tile': {}, 'min': {}}),
+    'linear_local': ('pdhip_linear_fill_ws_bytes', b_linear, {k: dict(local=1) for k in ('parent', 'ragged', 'tile', 'min')}),
+    'linear_global': ('pdhip_linear_fill_ws_bytes', b_linear, {k: dict(local=0) for k in ('parent', 'ragged', 'tile', 'min')}),
+}
+ROWS = [(entry, row) for entry, (_, _, rows) in ENTRIES.items() for row in rows]
+# outputs left out of the bit-equality check, each with the reason (include/pdhip.h documents it as order-dependent): none
+ORDER_DEPENDENT = {}
+
+
+def as_bytes(x):
+    return x.tobytes() if isinstance(x, np.ndarray) else x.detach().contiguous().cpu().numpy().tobytes()
+
+
+def build(pd, entry, row):
+    L = pd['lib'].lib()
+    query, builder, rows = ENTRIES[entry]
+    args = wc.SHAPES[query][row.split('+')[0]]
+    nbytes = getattr(L, query)(*args) * UNIT.get(query, 1)
+    return query, args, nbytes, builder(pd, L, *args, **rows[row])
+
+
+def run_guarded(pd, entry, row, spoil=None):
+    """Steps 1 - 5 of the module docstring for one row; returns (regions logged, slack bytes inside nbytes, nbytes).  spoil(run, nbytes) -> run:
+    test_the_checks_can_fail wraps the entry in a fault of its own making."""
+    L = pd['lib'].lib()
+    query, args, nbytes, run = build(pd, entry, row)
+    assert nbytes > 0
+    if spoil is not None:
+        run = spoil(run, nbytes)
+    ws = torch.full((nbytes + TAIL,), FILL, dtype=torch.uint8, device=DEV)
+    base = ws.data_ptr()
+    with wc.CarveLog(L) as log:
+        got = run(ws)
+        torch.cuda.synchronize()
+        carved, triples = log.read()
+    assert carved == len(triples), f"the carve log kept {len(triples)} of {carved} regions"
+    if query in NO_CARVE:
+        assert carved == 0
+        cover = np.array(NO_CARVE[query](*args) if NO_CARVE[query] else [[0, nbytes]], np.int64)
+    else:
+        assert carved > 0
+        _, first = np.unique(triples, axis=0, return_index=True)   # (an entry may carve its workspace once per stage: equal layouts, logged again)
+        triples = triples[np.sort(first)]
+        inside = (triples[:, 0] == 0) | ((triples[:, 0] >= base) & (triples[:, 0] + triples[:, 1] + triples[:, 2] <= base + nbytes))
+        assert inside.all(), ("a region outside the workspace", triples[~inside].tolist(), base, nbytes)    # (a null base: a size query asked while carving)
+        cover = wc.check_layout(len(triples), triples, base, nbytes)
+    # the canaries: everything outside the cover, built on the device as a difference array
+    edge = torch.zeros((nbytes + TAIL + 1,), dtype=torch.int32, device=DEV)
+    live = cover[cover[:, 1] > 0]
+    edge.index_add_(0, T(live[:, 0]), torch.ones(len(live), dtype=torch.int32, device=DEV))
+    edge.index_add_(0, T(live[:, 0] + live[:, 1]), -torch.ones(len(live), dtype=torch.int32, device=DEV))
+    canary = torch.cumsum(edge, 0)[:-1] <= 0
+    gaps = wc.uncovered(nbytes + TAIL, cover)
+    assert int(canary.sum()) == int((gaps[:, 1] - gaps[:, 0]).sum())
+    bad = torch.nonzero(canary & (ws != FILL)).flatten()
+    if bad.numel():
+        at = bad[:8].tolist()
+        before = [cover[cover[:, 0] <= o][-1].tolist() if (cover[:, 0] <= o).any() else None for o in at]
+        pytest.fail(f"{entry}[{row}] {query}{args}: {bad.numel()} bytes outside the carved regions changed; first offsets {at}, "
+                    f"the regions (offset, bytes) in front of them {before}; workspace of {nbytes} bytes")
+    assert bool((ws[:nbytes] != FILL).any())                       # the entry did use it
+    zero = [run(torch.zeros((nbytes,), dtype=torch.uint8, device=DEV)) for _ in range(2)]
+    torch.cuda.synchronize()
+    skip = ORDER_DEPENDENT.get(entry, {})
+    assert len(got) == len(zero[0]) == len(zero[1]) > len(skip)
+    for i, (g, a, b) in enumerate(zip(got, zero[0], zero[1])):
+        if i in skip:
+            continue
+        assert as_bytes(a) == as_bytes(b), f"{entry}[{row}]: output {i} differs between two runs on zeroed workspaces"
+        assert as_bytes(g) == as_bytes(a), f"{entry}[{row}]: output {i} on the 0x55 workspace differs from the zeroed one: a read before a write"
+    slack = wc.slack_bytes(nbytes, cover)
+    print(f"WSROW {entry} {row} {query}{args} bytes {nbytes} regions {len(cover) if query not in NO_CARVE else 0} slack {slack}")
+    return len(cover), slack, nbytes
+
+
+def test_the_table_has_three_rows_for_each_of_the_28_entries():
+    """(no GPU needed)"""
+    assert len(ENTRIES) == 28 and all(len(rows) >= 3 for _, _, rows in ENTRIES.values())
+    assert len({(q, wc.SHAPES[q][row.split('+')[0]], tuple(sorted(kw.items()))) for _, (q, _, rows) in ENTRIES.items() for row, kw in rows.items()}) \
+        == len(ROWS)                                               # no row twice
+    from pointdreamer_amd import _lib
+    queries = {n for n in _lib._SIGS if n.endswith(('_ws_bytes', '_workspace_bytes', '_ws_ints'))}
+    assert {q for q, _, _ in ENTRIES.values()} == queries          # every geometry size query has its entry here
+
+
+@pytest.mark.gpu
+def test_the_checks_can_fail(pd):
+    """The same rows with a fault added behind the entry, in the test's own torch code: a byte written into the slack behind the last region, into
+    the tail, and an output that takes in a workspace byte the entry never wrote."""
+    def writes_at(offset_from_nbytes):
+        def spoil(run, nbytes):
+            def spoiled(ws):
+                out = run(ws)
+                if ws.numel() > nbytes:                            # (the dirty run; the zeroed workspaces have no tail)
+                    ws[nbytes + offset_from_nbytes] = 7
+                return out
+            return spoiled
+        return spoil
+
+    def reads_slack(run, nbytes):
+        return lambda ws: run(ws) + [ws[nbytes - 8:nbytes].clone()]
+    for entry, row in (('owner_mean_colors', 'min'), ('sor_filter', 'ragged'), ('nearest_fill', 'tile')):
+        run_guarded(pd, entry, row)
+        carving = ENTRIES[entry][0] not in NO_CARVE
+        with pytest.raises(pytest.fail.Exception, match='outside the carved regions changed'):
+            run_guarded(pd, entry, row, spoil=writes_at(0))       # the first byte of the tail
+        if carving:
+            with pytest.raises(pytest.fail.Exception, match='outside the carved regions changed'):
+                run_guarded(pd, entry, row, spoil=writes_at(-1))  # the last byte of the `+ 256` behind the last region
+            with pytest.raises(AssertionError, match='a read before a write'):
+                run_guarded(pd, entry, row, spoil=reads_slack)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry,row", ROWS, ids=[f"{e}-{r}" for e, r in ROWS])
+def test_entry_stays_inside_its_regions_and_reads_nothing_unwritten(pd, entry, row):
+    run_guarded(pd, entry, row)
