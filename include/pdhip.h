@@ -838,6 +838,39 @@ int pdhip_compact_mesh(const float* vertices, int Vn, const int64_t* faces, int 
                        float* out_vertices, int64_t* out_faces, float* out_colors_or_null, int32_t* vertex_map_or_null, int32_t* counts, void* ws,
                        void* stream);
 
+/* ---- Taubin lambda | mu smoothing of a mesh with uniform ("umbrella") weights, and its boundary vertices (csrc/mesh_smooth.hip; no reference
+ * counterpart: MeshLab's "Taubin Smooth").  Both entries work on the neighbour CSR of pdhip_neighbour_csr: rowptr (device [Vn+1] i32) and colidx
+ * (device [rowptr[Vn]] i32), row v = the unique neighbours N(v) of vertex v, ascending, v itself not among them.  EVERY buffer is an argument the caller
+ * allocates: there is no workspace and no size query.
+ * pdhip_smooth_mesh: vertices (device [Vn,3] f32) -> out_vertices (device [Vn,3] f32); connectivity, and so faces and colours, are not touched.  The
+ * state is f64, the input converted exactly.  One pass with factor s: a held vertex (held[v] != 0; held may be NULL) and a vertex with an empty row keep
+ * their position; every other vertex gets x'[v] = x[v] + s * (m - x[v]), m = (sum of x[j], j in N(v)) / |N(v)|, per coordinate: the sum taken
+ * sequentially in row order from 0.0, then one IEEE division, one subtraction, one multiplication, one addition, none of them fused.  Every vertex reads
+ * the old state (Jacobi).  One step = a pass with lambda, then, if mu != 0, a pass with mu; after `steps` steps the state is rounded once to f32.  The
+ * result is therefore bit-equal to that definition evaluated in numpy; it depends on the mesh only through the neighbour sets -- not on the order of the
+ * faces, the rotation of a face's indices or the threads' order -- and two calls give equal bytes.  It is NOT invariant under relabelling the
+ * vertices: the order of each sum follows the indices.  state_a, state_b (device [Vn,4] f64 each, 32-byte aligned, distinct): ping-pong scratch, the
+ * fourth word of a row is padding; their contents before and after the call mean nothing.  counts (device [4] i32): vertices moved, held (with a
+ * non-empty row), isolated (empty row), and the check word; they add up to Vn.  Launches: one check, then steps * (mu != 0 ? 2 : 1) passes, the first
+ * reading `vertices`, the last writing out_vertices.
+ * PDHIP_E_ARG with the cause, before any device call: a null pointer (named; only held may be NULL), Vn < 1, Vn > 2^26, steps < 1, steps > 10000,
+ * lambda not in (0, 1], mu not finite or > 0, -lambda <= mu < 0 (not a Taubin pair: the pass band 1/lambda + 1/mu must be positive),
+ * |(1 - 2 lambda)(1 - 2 mu)| > 1 (a step would amplify the highest frequency, k = 2, of the normalised umbrella operator), a state buffer that is not
+ * 32-byte aligned, state_a == state_b.  mu == 0 is the plain Laplacian.  PDHIP_E_ARG from the check launch, out_vertices and the state buffers
+ * untouched (counts is written): rowptr[0] != 0 or rowptr not monotone up to rowptr[Vn], a colidx outside [0, Vn), a vertex with a non-empty row that
+ * is not finite.  The read of counts SYNCHRONISES the stream once, after the last launch (16 bytes).
+ * pdhip_mesh_boundary_vertices: faces [F,3] i64 on the device and THEIR neighbour CSR.  An ordered pair (a, b), a != b, is a boundary pair when it
+ * occurs exactly once among the 6 F ordered pairs of the faces (each edge of each face in both directions); a boundary vertex is one with a boundary
+ * pair; an edge on three faces or more is not boundary.  pair_faces (device [rowptr[Vn]] i32): the occurrences of the pair (v, colidx[pos]);
+ * boundary (device [Vn] u8): 1 for a boundary vertex; counts (device [4] i32): boundary vertices, boundary pairs / 2 (edges on one face), pairs on more
+ * than two faces / 2, and the check word.  Integer atomics only: a function of the mesh alone, equal bytes on repeats.  PDHIP_E_ARG: a null pointer
+ * (named), Vn < 1, F < 1, Vn > 2^26, F > 2^23; and from the device, boundary untouched (pair_faces is then undefined): rowptr not a CSR (rowptr[0] != 0,
+ * not monotone, rowptr[Vn] > 6 F), a face index outside [0, Vn), a pair of a face that its row does not hold.  SYNCHRONISES once, after the last launch. */
+int pdhip_mesh_boundary_vertices(const int64_t* faces, int F, int Vn, const int32_t* rowptr, const int32_t* colidx, int32_t* pair_faces,
+                                 uint8_t* boundary, int32_t* counts, void* stream);
+int pdhip_smooth_mesh(const float* vertices, int Vn, const int32_t* rowptr, const int32_t* colidx, const uint8_t* held_or_null, int steps,
+                      double lambda, double mu, double* state_a, double* state_b, float* out_vertices, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,9 @@ normalisation, a supplied mesh's normalisation, SPR and `subsample` see only the
 With the opt-in keys `spr_components: largest` / `spr_min_component_share` the mesh reconstructed under `geo_from: 'SPR'` loses its small floating
 pieces on the device (mesh_components.py) before it is decimated, cached and textured; elsewhere the keys have no effect.
 
+With the opt-in key `spr_smooth: <steps>` (`spr_smooth_lambda`, default 0.5; `spr_smooth_mu`, default -0.53: MeshLab's Taubin pair) the vertices of
+that mesh are smoothed on the device (mesh_smooth.py) after the components filter and before the decimation; faces and colours stay as they are.
+
 Geometry: the reference's drop-in hooks -- `<pc>_untextured_mesh.obj` next to the PLY (demo.py:391-399), the cached
 `geo/<name>_untextured/models/model_normalized.obj` (demo.py:401-406) and the cached `geo/xatlas_<res>.pth` dict (demo.py:428-448)
 -- and, with `geo_from: 'SPR'`, a mesh reconstructed from the cloud on the device (spr.recon_one_shape_SPR; POCO stays out of
@@ -62,6 +65,10 @@ OUTLIER_KEYS = ('remove_outliers', 'outlier_neighbors', 'outlier_std_ratio')
 # reconstructed mesh with the most faces ('all', the default when absent: every component, as before); spr_min_component_share (a float in (0, 1])
 # keeps the components with at least that share of the largest one's face count (mesh_components.py).  The cached geometry OBJ is the filtered mesh
 COMPONENT_KEYS = ('spr_components', 'spr_min_component_share')
+# opt-in stage behind that one (geo_from: 'SPR' only, still before spr_faces' decimation): spr_smooth: the number of Taubin steps (mesh_smooth.py) that
+# smooth the vertices of the reconstructed mesh, with spr_smooth_lambda (default 0.5) and spr_smooth_mu (default -0.53; 0: the plain Laplacian).
+# The cached geometry OBJ is the smoothed mesh; without spr_smooth nothing is smoothed
+SMOOTH_KEYS = ('spr_smooth', 'spr_smooth_lambda', 'spr_smooth_mu')
 
 
 class Cfg(dict):
@@ -102,7 +109,7 @@ def load_config(cfg_file, overrides=None):
     cfg = Cfg(yaml.safe_load(open(cfg_file)))
     cfg.update(overrides or {})
     unknown = [k for k in cfg if k not in SUPPORTED_KEYS and k not in UPSTREAM_KEYS and k not in GEOMETRY_KEYS and k not in RENDER_KEYS
-               and k not in SUBSAMPLE_KEYS and k not in OUTLIER_KEYS and k not in COMPONENT_KEYS]
+               and k not in SUBSAMPLE_KEYS and k not in OUTLIER_KEYS and k not in COMPONENT_KEYS and k not in SMOOTH_KEYS]
     if unknown:
         raise KeyError(f"{cfg_file}: unknown config keys {unknown}")
     if 'texture_gen_method' not in cfg:
@@ -145,6 +152,16 @@ def load_config(cfg_file, overrides=None):
                                                  and not isinstance(cfg.spr_min_component_share, bool) and 0.0 < cfg.spr_min_component_share <= 1.0):
         raise ValueError(f"spr_min_component_share={cfg.spr_min_component_share!r}: the share of the largest component's face count that a component "
                          "of the SPR geometry needs is a number in (0, 1]")
+    if any(k in cfg for k in SMOOTH_KEYS):
+        from . import mesh_smooth
+        if 'spr_smooth' not in cfg:
+            raise ValueError("spr_smooth_lambda / spr_smooth_mu steer the smoothing that spr_smooth: <steps> asks for: spr_smooth is missing")
+        try:
+            mesh_smooth.check_params(cfg.spr_smooth, cfg.get('spr_smooth_lambda', mesh_smooth.DEFAULT_LAMBDA),
+                                     cfg.get('spr_smooth_mu', mesh_smooth.DEFAULT_MU))
+        except ValueError as e:
+            raise ValueError(f"spr_smooth={cfg.spr_smooth!r}, spr_smooth_lambda={cfg.get('spr_smooth_lambda')!r}, "
+                             f"spr_smooth_mu={cfg.get('spr_smooth_mu')!r}: {e}") from None
     if cfg.optimize_from == 'None':                      # YAML `None` is the string 'None' (demo.py:213 treats both alike)
         cfg['optimize_from'] = None
     return cfg
@@ -255,6 +272,15 @@ def _component_rules(cfg):
     return dict(keep_components=rules) if rules else {}
 
 
+def _smooth_rules(cfg):
+    """The opt-in SMOOTH_KEYS as recon_one_shape_SPR's keyword: nothing without spr_smooth, so that nothing new runs."""
+    if 'spr_smooth' not in cfg:
+        return {}
+    from . import mesh_smooth
+    return dict(smooth=dict(steps=int(cfg.spr_smooth), lam=float(cfg.get('spr_smooth_lambda', mesh_smooth.DEFAULT_LAMBDA)),
+                            mu=float(cfg.get('spr_smooth_mu', mesh_smooth.DEFAULT_MU))))
+
+
 def _load_shape(cfg, pc_file, name, device, logger):
     """demo.py:359-452: cloud, mesh and atlas of one shape, normalised as the reference does."""
     out = os.path.join(cfg.output_path, name)
@@ -295,7 +321,7 @@ def _load_shape(cfg, pc_file, name, device, logger):
         depth = cfg.get('spr_depth', spr.DEFAULT_DEPTH)
         geo_xyz, geo_rgb = full if full is not None else (xyz, rgb)
         rv, rf, _, rc = spr.recon_one_shape_SPR(geo_xyz, geo_rgb, depth=depth, knn=cfg.get('spr_knn', spr.DEFAULT_KNN), save_path=cached_geo,
-                                                return_counts=True, target_faces=cfg.get('spr_faces'), **_component_rules(cfg))
+                                                return_counts=True, target_faces=cfg.get('spr_faces'), **_component_rules(cfg), **_smooth_rules(cfg))
         decimated = (f', decimated from {rc["faces_reconstructed"]} faces in {rc["simplify_rounds"]} rounds'
                      if 'simplify_rounds' in rc else '')
         logger.info(f'Get Geometry time: {time.time() - start} s by SPR (depth {depth}: {rc["vertices"]} vertices, {rc["faces"]} '
@@ -303,6 +329,9 @@ def _load_shape(cfg, pc_file, name, device, logger):
         if 'components' in rc:
             logger.info(f'SPR components: {rc["components"]} found, {rc["components_kept"]} kept, {rc["faces_dropped"]} of '
                         f'{rc["faces_reconstructed"]} reconstructed faces dropped')
+        if 'smooth_steps' in rc:
+            sm = _smooth_rules(cfg)['smooth']
+            logger.info(f'SPR smoothing: {rc["smooth_steps"]} Taubin steps (lambda {sm["lam"]:g}, mu {sm["mu"]:g}): {rc["smooth_moved"]} vertices moved')
     if os.path.exists(geo_path) or os.path.exists(cached_geo):
         supplied = os.path.exists(geo_path)
         v, f, vt, ft = io_utils.load_obj_mesh(geo_path if supplied else cached_geo, with_uv=True)

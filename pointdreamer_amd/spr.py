@@ -142,7 +142,7 @@ def _to_device(a, name):
 
 
 def recon_one_shape_SPR(coords, colors, gt_normals=None, save_path=None, depth=DEFAULT_DEPTH, simplify_face_num=None, *, knn=DEFAULT_KNN,
-                        return_counts=False, target_faces=None, keep_components=None):
+                        return_counts=False, target_faces=None, keep_components=None, smooth=None):
     """baselines/spr.py:16-75 with its argument order and 3-tuple (vertices [Vn,3], faces [F,3], vertex_colors [Vn,3]), as GPU
     tensors.  coords / colors / gt_normals: GPU tensors or numpy arrays (numpy goes to the current device).  gt_normals None: the
     normals are estimated.  save_path: the mesh is written as an OBJ.  depth: 6, 7 or 8 (a dense grid of 2^depth cells per axis, not
@@ -151,7 +151,10 @@ def recon_one_shape_SPR(coords, colors, gt_normals=None, save_path=None, depth=D
     the dict gains faces_reconstructed and simplify_rounds.  keep_components: 'largest' or a dict of mesh_components.filter_components' rules
     (keep, min_faces, min_face_share, min_diameter_share): the floating pieces of the iso-surface that fail them are dropped after the
     reconstruction and BEFORE the decimation, so target_faces budgets only the kept geometry; the vertex colours are carried through and with
-    return_counts the dict gains components and components_kept (and faces_reconstructed).  None: nothing new is called."""
+    return_counts the dict gains components and components_kept (and faces_reconstructed).  None: nothing new is called.  smooth: an int (Taubin steps
+    with MeshLab's lambda 0.5 and mu -0.53) or a dict of steps, lam, mu (mesh_smooth.taubin_smooth, boundary vertices held): the vertices are smoothed
+    AFTER keep_components and BEFORE target_faces, so the decimator's quadrics see the smoothed surface; faces and vertex colours stay as they are, and
+    with return_counts the dict gains smooth_steps and smooth_moved.  None: nothing new is called."""
     if simplify_face_num is not None:
         raise NotImplementedError("recon_one_shape_SPR: pymeshlab's quadric edge-collapse decimation (simplify_face_num) is not reproduced; "
                                   "this build's own decimator is the keyword target_faces=")
@@ -163,6 +166,16 @@ def recon_one_shape_SPR(coords, colors, gt_normals=None, save_path=None, depth=D
         if not isinstance(rules, dict) or not rules or any(k not in ('keep', 'min_faces', 'min_face_share', 'min_diameter_share') for k in rules):
             raise ValueError(f"keep_components={keep_components!r}: 'largest' or a dict of filter_components' rules (keep, min_faces, "
                              "min_face_share, min_diameter_share)")
+    if smooth is not None:
+        from . import mesh_smooth
+        sm = dict(steps=smooth) if isinstance(smooth, int) and not isinstance(smooth, bool) else smooth
+        if not isinstance(sm, dict) or 'steps' not in sm or any(k not in ('steps', 'lam', 'mu') for k in sm):
+            raise ValueError(f"smooth={smooth!r}: a number of Taubin steps or a dict of steps, lam, mu")
+        try:
+            sm = dict(zip(('steps', 'lam', 'mu'), mesh_smooth.check_params(sm['steps'], sm.get('lam', mesh_smooth.DEFAULT_LAMBDA),
+                                                                         sm.get('mu', mesh_smooth.DEFAULT_MU))))
+        except ValueError as e:
+            raise ValueError(f"smooth={smooth!r}: {e}") from None
     xyz = _to_device(coords, 'coords')
     rgb = _to_device(colors, 'colors')
     counts = None
@@ -176,6 +189,9 @@ def recon_one_shape_SPR(coords, colors, gt_normals=None, save_path=None, depth=D
         verts, faces, vcol, cc = mesh_components.filter_components(verts, faces, colors=vcol, return_counts=True, **rules)
         rc = dict(rc, faces_reconstructed=rc['faces'], vertices=cc['vertices_after'], faces=cc['faces_after'], components=cc['components'],
                   components_kept=cc['components_kept'], faces_dropped=cc['faces_before'] - cc['faces_after'])
+    if smooth is not None:
+        verts, mc = mesh_smooth.taubin_smooth(verts, faces, return_counts=True, **sm)
+        rc = dict(rc, smooth_steps=mc['steps'], smooth_moved=mc['moved'])
     if target_faces is not None:
         verts, faces, vcol, sc = simplify_mesh(verts, faces, target_faces, colors=vcol, return_counts=True)
         rc = dict(rc, faces_reconstructed=rc.get('faces_reconstructed', rc['faces']), vertices=sc['vertices'], faces=sc['faces'],
