@@ -1,10 +1,16 @@
 // Point cell list: the box a uniform grid is laid over, the points sorted by cell key (radix_sort.h) with cstart[c] = first sorted point whose
-// key is >= c, the sorted (x, y, z, index) copy, the cube of cells a scan visits.  Shared by surface_recon.hip (f32 3-D grid), cloud_metrics.hip
-// (f64 3-D grid) and occupancy.hip (f64 xy grid); each keeps its grid struct, the key functor that repeats its cell arithmetic operation for
-// operation, its face bound and its refusal messages.  Internal linkage: each including unit gets its own copy.  Zero scratch.
+// key is >= c, the sorted (x, y, z, index) copy, the cube of cells a scan visits.  Shared by surface_recon.hip (f32 3-D grid, cell_of, ring_bound)
+// and occupancy.hip (f64 xy grid over `inv`), each of which keeps its grid struct, the key functor that repeats its cell arithmetic operation for
+// operation, its face bound and its refusal messages: their arithmetic differs and goldens pin it; and by cloud_metrics.hip, knn.hip, subsample.hip
+// and mesh_distance.hip, which share the f64 3-D grid of the last section: the grid, the key, the certificate's face bound, the (d2, index)
+// minimum and the staged scan of everything for the queries the certificate leaves.  Internal linkage: each including unit gets its own copy.
+// Zero scratch.
 #pragma once
 #include "radix_sort.h"
 #include <string.h>
+#include <math.h>
+#include <limits.h>
+#include <algorithm>
 
 namespace pdhip {
 namespace {
@@ -148,6 +154,182 @@ struct CellCube {
 };
 __device__ __forceinline__ CellCube cube_around(int cx, int cy, int cz, int r, int C) {
     return CellCube{max(cx - r, 0), min(cx + r, C - 1), max(cy - r, 0), min(cy + r, C - 1), max(cz - r, 0), min(cz + r, C - 1)};
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// the f64 3-D grid: C^3 cubic cells of edge cs from the corner (ox, oy, oz).  A point outside is clamped into a boundary cell.  Host code as well:
+// a host program can run the very cull against an oracle without a device
+struct Grid3 {
+    double ox, oy, oz, cs;
+    int C;
+    __host__ __device__ __forceinline__ int cell(double x, double o) const { return (int)fmin(fmax(floor((x - o) / cs), 0.0), (double)(C - 1)); }
+};
+
+// KeyFn of sort_by_cell: the key of the cell that point i of P falls (or is clamped) into
+struct GridPointKey {
+    const float* P;
+    Grid3 g;
+    __device__ uint64_t operator()(int i) const {
+        const int cx = g.cell((double)P[3 * (size_t)i], g.ox), cy = g.cell((double)P[3 * (size_t)i + 1], g.oy),
+                  cz = g.cell((double)P[3 * (size_t)i + 2], g.oz);
+        return (uint64_t)((cz * g.C + cy) * g.C + cx);
+    }
+};
+
+// The certificate.  A scan that has visited every target of the cells [c0, c1] per axis may stop when its worst kept d2 is <= b * b, b = the
+// smallest grid_face_bound of the three axes, and b > 0: a target that was not visited lies in another cell, that is beyond a face of the cube that
+// is NOT a face of the whole grid (clamping moves points into boundary cells only, so a grid face has nothing behind it -- which is also why points
+// outside the grid cost nothing: only non-grid faces bound), so its distance along that axis is at least q's distance to that face.  The face is
+// pulled in by 1e-12 of the coordinates' magnitude, far more than the f64 rounding of the cell arithmetic (x - o) / cs, of f = o + c cs and of d2:
+// the unvisited target's COMPUTED d2 is then strictly larger than the winner's, and cannot tie with it, so the result equals a brute-force scan bit
+// for bit.  No such face on either side: 1e300, i.e. the cube spans the axis.  (mesh_distance.hip keeps md_face_bound: a triangle's closest point
+// needs a guard of 1e-7 (|q| + gmax) that does not depend on the face, computed once; a guard parameter would change the operations of one side.)
+__host__ __device__ __forceinline__ double grid_face_bound(double q, double o, double cs, int C, int c0, int c1) {
+    double b = 1.0e300;
+    if (c0 > 0) {
+        const double f = o + (double)c0 * cs;
+        b = fmin(b, (q - f) - 1.0e-12 * (fabs(q) + fabs(f)));
+    }
+    if (c1 < C - 1) {
+        const double f = o + (double)(c1 + 1) * cs;
+        b = fmin(b, (f - q) - 1.0e-12 * (fabs(q) + fabs(f)));
+    }
+    return b;
+}
+__host__ __device__ __forceinline__ double grid_cube_bound(const Grid3& g, double qx, double qy, double qz, const CellCube& q) {
+    return fmin(fmin(grid_face_bound(qx, g.ox, g.cs, g.C, q.x0, q.x1), grid_face_bound(qy, g.oy, g.cs, g.C, q.y0, q.y1)),
+                grid_face_bound(qz, g.oz, g.cs, g.C, q.z0, q.z1));
+}
+
+// the lexicographic order of (d2, index): the minimum, and of the candidates that attain it the smallest index, depend on no scan order.  A NaN
+// never wins (both comparisons are false for it).  (take_min spells the condition out: through pair_less the compiler selects where it branched,
+// and the scans' registers grow)
+__host__ __device__ __forceinline__ bool pair_less(double d, int k, double bd, int bi) { return d < bd || (d == bd && k < bi); }
+__host__ __device__ __forceinline__ void take_min(double d, int k, double& bd, int& bi) {
+    if (d < bd || (d == bd && k < bi)) { bd = d; bi = k; }
+}
+
+// d2 = (dx dx + dy dy) + dz dz with the f32 inputs widened to f64, op by op
+__host__ __device__ __forceinline__ double point_d2(double qx, double qy, double qz, const float4& a) {
+    const double dx = qx - (double)a.x, dy = qy - (double)a.y, dz = qz - (double)a.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// host: C cells per axis over the cube of edge ext at mn, stretched by 1e-6 so that the box's far corner falls inside the last cell.  A box
+// without extent: one cell
+static Grid3 grid_over(const double mn[3], double ext, int C) {
+    Grid3 g;
+    g.C = ext > 0.0 ? C : 1;
+    g.cs = ext > 0.0 ? ext / g.C * (1.0 + 1.0e-6) : 1.0;
+    g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2];
+    return g;
+}
+static double box_extent(const double mn[3], const double mx[3]) {
+    double ext = 0.0;
+    for (int a = 0; a < 3; ++a) ext = std::max(ext, mx[a] - mn[a]);
+    return ext;
+}
+// host: mn = the corner of the part of the targets' box [tmn, tmx] that the queries' box meets (of the whole box if they do not meet), returns its
+// extent: a few outliers among the targets do not coarsen the cells where the queries are.  Points outside the grid are clamped into its boundary
+// cells, which the certificate allows
+static double meet_boxes(const double tmn[3], const double tmx[3], const HostBox& q, double mn[3]) {
+    double lo[3], hi[3];
+    bool meet = true;
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = std::max(tmn[a], q.mn[a]);
+        hi[a] = std::min(tmx[a], q.mx[a]);
+        meet = meet && lo[a] <= hi[a];
+    }
+    for (int a = 0; a < 3; ++a) mn[a] = meet ? lo[a] : tmn[a];
+    return meet ? box_extent(lo, hi) : box_extent(tmn, tmx);
+}
+
+// host: the boxes of the targets and of the queries into words[0 .. 2 BOX_WORDS), the nwords words cleared (launches only) ...
+static void launch_point_box(const float* P, int n, uint32_t* box, hipStream_t s) {
+    k_point_box<<<std::min(cdiv(n, CL_T), 1024), CL_T, 0, s>>>(P, n, nullptr, n, 1, box);
+}
+static int launch_cloud_boxes(const float* targets, int M, const float* queries, int Q, uint32_t* words, int nwords, hipStream_t s) {
+    const int rc = clear_boxes(words, 2, nwords, s);
+    if (rc) return rc;
+    launch_point_box(targets, M, words, s);
+    launch_point_box(queries, Q, words + BOX_WORDS, s);
+    PD_LAUNCH_CHECK();
+    return PDHIP_OK;
+}
+// ... and their read (the one synchronisation: what the entry enqueued in between arrives with it), which refuses non-finite coordinates
+static int read_cloud_boxes(const char* entry, const uint32_t* words, HostBox (&box)[2], hipStream_t s) {
+    const int rc = read_boxes(words, box, s);
+    if (rc) return rc;
+    PD_REQUIRE(box[0].bad == 0, "%s: %u target(s) with a non-finite coordinate", entry, box[0].bad);
+    PD_REQUIRE(box[1].bad == 0, "%s: %u query point(s) with a non-finite coordinate", entry, box[1].bad);
+    return PDHIP_OK;
+}
+
+// counts[] of a two-way split of Q queries: {certified, left to the scan of everything (all of them when `all`), cells per axis, 0}
+__global__ void k_split_counts(const int* __restrict__ left_n, int Q, int C, int all, int32_t* __restrict__ counts) {
+    const int n = all ? Q : min(*left_n, Q);
+    counts[0] = Q - n; counts[1] = n; counts[2] = C; counts[3] = 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The staged scan of everything, for the queries far_list[0 .. *far_n) that a ring scan gave up (far from every element: a thread of its own would
+// scan most of the grid; or in crowded cells): every element against every such query, no certificate needed.  Workgroup (tile, slab): T queries of
+// the list against one of SLABS slabs of st[0 .. f.live()), staged in LDS in chunks of CHUNK -> part[slab][i]; k_far_pick takes the minimum over the
+// slabs.  Far: a small struct passed by value with
+//   __device__ int live() const                                                          how many elements of st count
+//   __device__ double d2(double qx, double qy, double qz, const Elem& a, int& k) const   the squared distance to element a, k = its index
+//   static __device__ double none()  /  static __device__ int index(int bi)              the d2 of "nothing yet"; the index to report (bi == INT_MAX: nothing)
+template <int T, int CHUNK, int SLABS, class Elem, class Far>
+__global__ __launch_bounds__(T) void k_far_scan(const float4* __restrict__ sq, const int* __restrict__ far_list, const int* __restrict__ far_n, int Q,
+                                                const Elem* __restrict__ st, Far f, double* __restrict__ part_d2, int* __restrict__ part_idx) {
+    __shared__ Elem s_t[CHUNK];
+    const int t = threadIdx.x;
+    const int n = min(*far_n, Q);
+    if ((int)blockIdx.x * T >= n) return;                          // (the whole workgroup)
+    const int i = blockIdx.x * T + t;
+    const bool have = i < n;
+    double qx = 0.0, qy = 0.0, qz = 0.0;
+    if (have) {
+        const float4 me = sq[far_list[i]];
+        qx = (double)me.x; qy = (double)me.y; qz = (double)me.z;
+    }
+    const int M = f.live();
+    const int per = (M + SLABS - 1) / SLABS;
+    const int b0 = min(M, (int)blockIdx.y * per), e0 = min(M, b0 + per);
+    double bd = Far::none();
+    int bi = INT_MAX;
+    for (int base = b0; base < e0; base += CHUNK) {
+        const int nc = min(CHUNK, e0 - base);
+        __syncthreads();
+        for (int j = t; j < nc; j += T) s_t[j] = st[base + j];
+        __syncthreads();
+        if (have) {
+            for (int j = 0; j < nc; ++j) {
+                const Elem a = s_t[j];
+                int k;
+                const double d = f.d2(qx, qy, qz, a, k);
+                take_min(d, k, bd, bi);
+            }
+        }
+    }
+    if (have) {
+        part_d2[(size_t)blockIdx.y * Q + i] = bd;
+        part_idx[(size_t)blockIdx.y * Q + i] = bi;
+    }
+}
+
+template <int T, int SLABS, class Far>
+__global__ __launch_bounds__(T) void k_far_pick(const float4* __restrict__ sq, const int* __restrict__ far_list, const int* __restrict__ far_n, int Q,
+                                                const double* __restrict__ part_d2, const int* __restrict__ part_idx, double* __restrict__ d2,
+                                                int* __restrict__ idx) {
+    const int i = blockIdx.x * T + threadIdx.x;
+    if (i >= min(*far_n, Q)) return;
+    double bd = Far::none();
+    int bi = INT_MAX;
+    for (int sl = 0; sl < SLABS; ++sl) take_min(part_d2[(size_t)sl * Q + i], part_idx[(size_t)sl * Q + i], bd, bi);
+    const int o = __float_as_int(sq[far_list[i]].w);
+    d2[o] = bd;
+    idx[o] = Far::index(bi);
 }
 
 }  // namespace

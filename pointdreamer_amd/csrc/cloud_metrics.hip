@@ -3,21 +3,21 @@
 //
 //   pdhip_nearest_points
 //     a. bounding boxes and a finiteness test of both clouds (integer atomics on order-preserving keys; one small read that synchronises the
-//        stream); a uniform grid of C^3 cells, C ~ sqrt(M / 8): a few targets per occupied cell of a surface, over the cube of the part of the
-//        targets' box that the queries' box meets.  Points outside the grid are clamped into its boundary cells;
+//        stream); a uniform grid of C^3 cells (cell_list.h's Grid3), C ~ sqrt(M / 8): a few targets per occupied cell of a surface, over the cube of the
+//        part of the targets' box that the queries' box meets (meet_boxes).  Points outside the grid are clamped into its boundary cells;
 //     b. targets sorted by cell key (cell_list.h, as is a.'s box kernel), cstart[c] = first sorted target whose key is >= c, for c = 0 .. C^3 (a binary search per cell): the targets of the
 //        cells x0 .. x1 of a grid row are ONE run of the sorted array; queries sorted by the key of the cell they fall (or are clamped) into;
 //     c. phase 1 (k_cm_stage_scan): a workgroup owns CM_T consecutive sorted queries, takes the bounding cell box of their cells plus one ring,
 //        stages the targets of that box into LDS as (x, y, z, index) in chunks of CM_CHUNK, and every thread scans each chunk for its own query
 //        in f64.  A query is CERTIFIED when its best d2 is <= the squared distance from the query to the nearest face of the staged box that is
-//        not a face of the whole grid (a target that was not staged lies beyond such a face); the faces are pulled in by 1e-12 of the
-//        coordinates' magnitude, far more than the f64 rounding of the cell arithmetic and of d2, so that an unstaged target's d2 is strictly
-//        larger.  A box of more than CM_ROWS grid rows or CM_BOX_CHUNKS chunks certifies nobody;
+//        not a face of the whole grid (cell_list.h's grid_face_bound, which has the argument why an unstaged target's d2 is then strictly
+//        larger).  A box of more than CM_ROWS grid rows or CM_BOX_CHUNKS chunks certifies nobody;
 //     d. phase 2 (k_cm_ring_scan): one thread per query that phase 1 left, the cube of cells [c - r, c + r] scanned from global memory with
 //        r = 1, 2, 4, 8 until the same certificate holds or the cube is the whole grid;
-//     e. far scan (k_cm_far_scan, k_cm_far_pick): a query still open after r = 8 is far from every target, and a thread of its own would scan most of the
-//        grid; a query whose rings hold more than CM_RING_WORK targets sits in crowded cells.  Such queries are scanned against ALL targets, a tile of CM_T of them per workgroup and the targets staged in LDS, the targets cut into
-//        CM_FAR_SLABS slabs over the second grid axis; the minimum over the slabs (smallest index on a tie) is taken by a second kernel.
+//     e. far scan (cell_list.h's k_far_scan, k_far_pick with CmFar): a query still open after r = 8 is far from every target, and a thread of its own
+//        would scan most of the grid; a query whose rings hold more than CM_RING_WORK targets sits in crowded cells.  Such queries are scanned
+//        against ALL targets, a tile of CM_T of them per workgroup and the targets staged in LDS, the sorted targets cut into CM_FAR_SLABS slabs;
+//        the minimum over the slabs (smallest index on a tie) is taken by the second kernel.
 //     Shipped: d + e for every query (in cell order, so that neighbouring threads scan the same cells); c + d + e behind pdhip_debug_set_nearest_path(1).
 //     Measured at 10^5 x 10^5 points (profiles/geometry_metrics_bench.txt) the staged scan loses: a workgroup's 256 queries in row-major cell order span
 //     whole grid rows, every thread scans every target of that box, and the cell list already sits in the L2 -- staging it saves no traffic that matters.
@@ -51,45 +51,10 @@ constexpr int CM_TMAX = 4096;                 // thresholds
 constexpr int CM_NMAX = 1 << 26;
 enum { MISC_UNC = 2 * BOX_WORDS, MISC_FAR = MISC_UNC + 1, MISC_WORDS = 32 };      // behind the two boxes (cell_list.h)
 
-struct CmGrid {
-    double ox, oy, oz, cs;
-    int C;
-};
-
-__device__ __forceinline__ int cm_cell(double x, double o, double cs, int C) {
-    return (int)fmin(fmax(floor((x - o) / cs), 0.0), (double)(C - 1));
-}
-
-// distance from q to the nearest face of the cells [c0, c1] that is not a face of the whole grid, less the safety margin
-__device__ __forceinline__ double cm_face_bound(double q, double o, double cs, int C, int c0, int c1) {
-    double b = 1.0e300;
-    if (c0 > 0) {
-        const double f = o + (double)c0 * cs;
-        b = fmin(b, (q - f) - 1.0e-12 * (fabs(q) + fabs(f)));
-    }
-    if (c1 < C - 1) {
-        const double f = o + (double)(c1 + 1) * cs;
-        b = fmin(b, (f - q) - 1.0e-12 * (fabs(q) + fabs(f)));
-    }
-    return b;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// b. the key of the cell that point i of P falls (or is clamped) into
-struct CmKey {
-    const float* P;
-    CmGrid g;
-    __device__ uint64_t operator()(int i) const {
-        const int cx = cm_cell((double)P[3 * (size_t)i], g.ox, g.cs, g.C), cy = cm_cell((double)P[3 * (size_t)i + 1], g.oy, g.cs, g.C),
-                  cz = cm_cell((double)P[3 * (size_t)i + 2], g.oz, g.cs, g.C);
-        return (uint64_t)((cz * g.C + cy) * g.C + cx);
-    }
-};
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // c. phase 1
 __global__ __launch_bounds__(CM_T) void k_cm_stage_scan(const float4* __restrict__ sq, int Q, const float4* __restrict__ st,
-                                                        const int* __restrict__ cstart, CmGrid g, double* __restrict__ d2,
+                                                        const int* __restrict__ cstart, Grid3 g, double* __restrict__ d2,
                                                         int* __restrict__ idx, int* __restrict__ unc_list, int* __restrict__ unc_n) {
     __shared__ float4 s_t[CM_CHUNK];
     __shared__ int s_rs[CM_ROWS];                                  // first sorted target of a row of the box
@@ -107,7 +72,7 @@ __global__ __launch_bounds__(CM_T) void k_cm_stage_scan(const float4* __restrict
     if (have) {
         me = sq[p];
         qx = (double)me.x; qy = (double)me.y; qz = (double)me.z;
-        const int cx = cm_cell(qx, g.ox, g.cs, C), cy = cm_cell(qy, g.oy, g.cs, C), cz = cm_cell(qz, g.oz, g.cs, C);
+        const int cx = g.cell(qx, g.ox), cy = g.cell(qy, g.oy), cz = g.cell(qz, g.oz);
         atomicMin(&s_box[0], cx); atomicMin(&s_box[1], cy); atomicMin(&s_box[2], cz);
         atomicMax(&s_box[3], cx); atomicMax(&s_box[4], cy); atomicMax(&s_box[5], cz);
     }
@@ -164,10 +129,7 @@ __global__ __launch_bounds__(CM_T) void k_cm_stage_scan(const float4* __restrict
             if (have) {
                 for (int j = 0; j < n; ++j) {
                     const float4 a = s_t[j];
-                    const double dx = qx - (double)a.x, dy = qy - (double)a.y, dz = qz - (double)a.z;
-                    const double d = (dx * dx + dy * dy) + dz * dz;
-                    const int i = __float_as_int(a.w);
-                    if (d < bd || (d == bd && i < bi)) { bd = d; bi = i; }
+                    take_min(point_d2(qx, qy, qz, a), __float_as_int(a.w), bd, bi);
                 }
             }
         }
@@ -175,8 +137,7 @@ __global__ __launch_bounds__(CM_T) void k_cm_stage_scan(const float4* __restrict
     if (!have) return;
     bool cert = false;
     if (ok && bi != INT_MAX) {
-        const double b = fmin(fmin(cm_face_bound(qx, g.ox, g.cs, C, x0, x1), cm_face_bound(qy, g.oy, g.cs, C, y0, y1)),
-                              cm_face_bound(qz, g.oz, g.cs, C, z0, z1));
+        const double b = grid_cube_bound(g, qx, qy, qz, CellCube{x0, x1, y0, y1, z0, z1});
         cert = b > 0.0 && bd <= b * b;
     }
     if (cert) {
@@ -191,7 +152,7 @@ __global__ __launch_bounds__(CM_T) void k_cm_stage_scan(const float4* __restrict
 // ---------------------------------------------------------------------------------------------------------------------------
 // d. phase 2: the queries list[0 .. *n_ptr) (list == nullptr: all n_all sorted queries)
 __global__ __launch_bounds__(CM_P2_T) void k_cm_ring_scan(const float4* __restrict__ sq, const int* __restrict__ list, const int* __restrict__ n_ptr,
-                                                          int n_all, const float4* __restrict__ st, const int* __restrict__ cstart, CmGrid g,
+                                                          int n_all, const float4* __restrict__ st, const int* __restrict__ cstart, Grid3 g,
                                                           double* __restrict__ d2, int* __restrict__ idx, int* __restrict__ far_list,
                                                           int* __restrict__ far_n) {
     const int i = blockIdx.x * CM_P2_T + threadIdx.x;
@@ -201,7 +162,7 @@ __global__ __launch_bounds__(CM_P2_T) void k_cm_ring_scan(const float4* __restri
     const float4 me = sq[sp];
     const double qx = (double)me.x, qy = (double)me.y, qz = (double)me.z;
     const int C = g.C;
-    const int cx = cm_cell(qx, g.ox, g.cs, C), cy = cm_cell(qy, g.oy, g.cs, C), cz = cm_cell(qz, g.oz, g.cs, C);
+    const int cx = g.cell(qx, g.ox), cy = g.cell(qy, g.oy), cz = g.cell(qz, g.oz);
     double bd = 1.0e300;
     int bi = INT_MAX, work = 0;
     for (int r = 1;; r *= 2) {
@@ -217,14 +178,12 @@ __global__ __launch_bounds__(CM_P2_T) void k_cm_ring_scan(const float4* __restri
                 }
                 for (int p = b; p < e; ++p) {
                     const float4 a = st[p];
-                    const double dx = qx - (double)a.x, dy = qy - (double)a.y, dz = qz - (double)a.z;
-                    const double d = (dx * dx + dy * dy) + dz * dz;
+                    const double d = point_d2(qx, qy, qz, a);
                     const int k = __float_as_int(a.w);
-                    if (d < bd || (d == bd && k < bi)) { bd = d; bi = k; }
+                    if (d < bd || (d == bd && k < bi)) { bd = d; bi = k; }       // (take_min, spelled out: through it this kernel takes two VGPRs more)
                 }
             }
-        const double b = fmin(fmin(cm_face_bound(qx, g.ox, g.cs, C, q.x0, q.x1), cm_face_bound(qy, g.oy, g.cs, C, q.y0, q.y1)),
-                              cm_face_bound(qz, g.oz, g.cs, C, q.z0, q.z1));
+        const double b = grid_cube_bound(g, qx, qy, qz, q);
         if (q.covers(C) || (bi != INT_MAX && b > 0.0 && bd <= b * b)) break;
         if (r >= CM_RING_MAX) {                                    // far from every target: a thread of its own would scan most of the grid
             far_list[atomicAdd(far_n, 1)] = sp;
@@ -236,68 +195,17 @@ __global__ __launch_bounds__(CM_P2_T) void k_cm_ring_scan(const float4* __restri
     idx[o] = bi;
 }
 
-// e. the queries the ring scan gave up: every target against every such query, no certificate needed.  Workgroup (tile, slab): CM_T queries of the
-// list against one slab of the sorted targets, staged in LDS in chunks of CM_CHUNK -> part[slab][i]; k_cm_far_pick takes the minimum over the slabs.
-__global__ __launch_bounds__(CM_T) void k_cm_far_scan(const float4* __restrict__ sq, const int* __restrict__ far_list, const int* __restrict__ far_n,
-                                                      int Q, const float4* __restrict__ st, int M, double* __restrict__ part_d2,
-                                                      int* __restrict__ part_idx) {
-    __shared__ float4 s_t[CM_CHUNK];
-    const int t = threadIdx.x;
-    const int n = min(*far_n, Q);
-    if ((int)blockIdx.x * CM_T >= n) return;                       // (the whole workgroup)
-    const int i = blockIdx.x * CM_T + t;
-    const bool have = i < n;
-    double qx = 0.0, qy = 0.0, qz = 0.0;
-    if (have) {
-        const float4 me = sq[far_list[i]];
-        qx = (double)me.x; qy = (double)me.y; qz = (double)me.z;
+// e. the queries the ring scan gave up against all M sorted targets (cell_list.h's k_far_scan / k_far_pick)
+struct CmFar {
+    int M;
+    __device__ int live() const { return M; }
+    __device__ double d2(double qx, double qy, double qz, const float4& a, int& k) const {
+        k = __float_as_int(a.w);
+        return point_d2(qx, qy, qz, a);
     }
-    const int per = (M + CM_FAR_SLABS - 1) / CM_FAR_SLABS;
-    const int b0 = min(M, (int)blockIdx.y * per), e0 = min(M, b0 + per);
-    double bd = 1.0e300;
-    int bi = INT_MAX;
-    for (int base = b0; base < e0; base += CM_CHUNK) {
-        const int nc = min(CM_CHUNK, e0 - base);
-        __syncthreads();
-        for (int j = t; j < nc; j += CM_T) s_t[j] = st[base + j];
-        __syncthreads();
-        if (have) {
-            for (int j = 0; j < nc; ++j) {
-                const float4 a = s_t[j];
-                const double dx = qx - (double)a.x, dy = qy - (double)a.y, dz = qz - (double)a.z;
-                const double d = (dx * dx + dy * dy) + dz * dz;
-                const int k = __float_as_int(a.w);
-                if (d < bd || (d == bd && k < bi)) { bd = d; bi = k; }
-            }
-        }
-    }
-    if (have) {
-        part_d2[(size_t)blockIdx.y * Q + i] = bd;
-        part_idx[(size_t)blockIdx.y * Q + i] = bi;
-    }
-}
-
-__global__ __launch_bounds__(CM_T) void k_cm_far_pick(const float4* __restrict__ sq, const int* __restrict__ far_list, const int* __restrict__ far_n,
-                                                      int Q, const double* __restrict__ part_d2, const int* __restrict__ part_idx,
-                                                      double* __restrict__ d2, int* __restrict__ idx) {
-    const int i = blockIdx.x * CM_T + threadIdx.x;
-    if (i >= min(*far_n, Q)) return;
-    double bd = 1.0e300;
-    int bi = INT_MAX;
-    for (int sl = 0; sl < CM_FAR_SLABS; ++sl) {
-        const double d = part_d2[(size_t)sl * Q + i];
-        const int k = part_idx[(size_t)sl * Q + i];
-        if (d < bd || (d == bd && k < bi)) { bd = d; bi = k; }
-    }
-    const int o = __float_as_int(sq[far_list[i]].w);
-    d2[o] = bd;
-    idx[o] = bi;
-}
-
-__global__ void k_cm_counts(const int* __restrict__ unc_n, int Q, int C, int forced, int32_t* __restrict__ counts) {
-    const int n = forced ? Q : *unc_n;
-    counts[0] = Q - n; counts[1] = n; counts[2] = C; counts[3] = 0;
-}
+    static __device__ double none() { return 1.0e300; }
+    static __device__ int index(int bi) { return bi; }
+};
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // the reduction: part[w][block], w = 0 sqrt(d2), 1 d2, 2 |n . n|; hist[b] = queries whose distance falls into bin b (T: beyond every threshold)
@@ -425,48 +333,20 @@ extern "C" int pdhip_nearest_points(const float* queries, int Q, const float* ta
     }
     NearWs w;
     carve_nearest(w, ws, Q, M);
-    // a. the targets' box, finiteness of both clouds
-    int rc = clear_boxes(w.misc, 2, MISC_WORDS, s);
+    // a. the boxes, finiteness of both clouds; the grid over the part of the targets' box that the queries' box meets
+    int rc = launch_cloud_boxes(targets, M, queries, Q, w.misc, MISC_WORDS, s);
     if (rc) return rc;
-    k_point_box<<<std::min(cdiv(M, CL_T), 1024), CL_T, 0, s>>>(targets, M, nullptr, M, 1, w.misc);
-    k_point_box<<<std::min(cdiv(Q, CL_T), 1024), CL_T, 0, s>>>(queries, Q, nullptr, Q, 1, w.misc + BOX_WORDS);
-    PD_LAUNCH_CHECK();
     HostBox box[2];                                                // targets, queries
-    rc = read_boxes(w.misc, box, s);
+    rc = read_cloud_boxes("pdhip_nearest_points", w.misc, box, s);
     if (rc) return rc;
-    PD_REQUIRE(box[0].bad == 0, "pdhip_nearest_points: %u target(s) with a non-finite coordinate", box[0].bad);
-    PD_REQUIRE(box[1].bad == 0, "pdhip_nearest_points: %u query point(s) with a non-finite coordinate", box[1].bad);
-    double mn[3], ext = 0.0;
-    for (int a = 0; a < 3; ++a) {
-        mn[a] = box[0].mn[a];
-        ext = std::max(ext, box[0].mx[a] - mn[a]);
-    }
-    // the grid covers the part of the targets' box that the queries' box meets (the whole box if they do not meet): a few outliers among the targets do
-    // not coarsen the cells where the queries are.  Points outside the grid are clamped into its boundary cells, which the certificate allows: it
-    // bounds only by faces that are not faces of the grid.
-    double lo[3], hi[3];
-    bool meet = true;
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = std::max(mn[a], box[1].mn[a]);
-        hi[a] = std::min(box[0].mx[a], box[1].mx[a]);
-        meet = meet && lo[a] <= hi[a];
-    }
-    if (meet) {
-        ext = 0.0;
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = lo[a];
-            ext = std::max(ext, hi[a] - lo[a]);
-        }
-    }
-    CmGrid g;
-    g.C = ext > 0.0 ? cells_axis_max(M) : 1;                       // (a box without extent: one cell)
-    g.cs = ext > 0.0 ? ext / g.C * (1.0 + 1.0e-6) : 1.0;
-    g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2];
+    double mn[3];
+    const double ext = meet_boxes(box[0].mn, box[0].mx, box[1], mn);
+    const Grid3 g = grid_over(mn, ext, cells_axis_max(M));
     const int nc = g.C * g.C * g.C;
     // b. both clouds in cell order
-    int cur = sort_by_cell(w.sb, M, CmKey{targets, g}, (unsigned long long)nc, w.cstart, s);
+    int cur = sort_by_cell(w.sb, M, GridPointKey{targets, g}, (unsigned long long)nc, w.cstart, s);
     k_gather_xyzi<<<cdiv(M, CL_T), CL_T, 0, s>>>(w.sb.v[cur], targets, M, w.st);
-    cur = sort_by_cell(w.sb, Q, CmKey{queries, g}, (unsigned long long)nc, nullptr, s);      // (the queries need the order only)
+    cur = sort_by_cell(w.sb, Q, GridPointKey{queries, g}, (unsigned long long)nc, nullptr, s);      // (the queries need the order only)
     k_gather_xyzi<<<cdiv(Q, CL_T), CL_T, 0, s>>>(w.sb.v[cur], queries, Q, w.sq);
     PD_LAUNCH_CHECK();
     // c, d.
@@ -479,9 +359,9 @@ extern "C" int pdhip_nearest_points(const float* queries, int Q, const float* ta
     } else {
         k_cm_ring_scan<<<cdiv(Q, CM_P2_T), CM_P2_T, 0, s>>>(w.sq, nullptr, nullptr, Q, w.st, w.cstart, g, d2, idx, w.far_list, far_n);
     }
-    k_cm_far_scan<<<dim3(cdiv(Q, CM_T), CM_FAR_SLABS), CM_T, 0, s>>>(w.sq, w.far_list, far_n, Q, w.st, M, w.part_d2, w.part_idx);
-    k_cm_far_pick<<<cdiv(Q, CM_T), CM_T, 0, s>>>(w.sq, w.far_list, far_n, Q, w.part_d2, w.part_idx, d2, idx);
-    k_cm_counts<<<1, 1, 0, s>>>(unc_n, Q, g.C, forced, counts);
+    k_far_scan<CM_T, CM_CHUNK, CM_FAR_SLABS><<<dim3(cdiv(Q, CM_T), CM_FAR_SLABS), CM_T, 0, s>>>(w.sq, w.far_list, far_n, Q, w.st, CmFar{M}, w.part_d2, w.part_idx);
+    k_far_pick<CM_T, CM_FAR_SLABS, CmFar><<<cdiv(Q, CM_T), CM_T, 0, s>>>(w.sq, w.far_list, far_n, Q, w.part_d2, w.part_idx, d2, idx);
+    k_split_counts<<<1, 1, 0, s>>>(unc_n, Q, g.C, forced, counts);             // (unc_n <= Q: a query enters the list once)
     PD_LAUNCH_CHECK();
     return PDHIP_OK;
 }

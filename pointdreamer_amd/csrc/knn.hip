@@ -3,8 +3,8 @@
 //
 //   pdhip_knn_points
 //     a. bounding boxes and a finiteness test of both clouds (cell_list.h's k_point_box) and a histogram of the targets' coordinates per axis
-//        over their box (k_kn_axis_hist), all three read at once (the call's one synchronisation); a uniform f64 grid of C^3 cells, C ~ sqrt(M /
-//        occ) with occ = max(8, k / 2) targets per occupied cell of a surface, over the part of the targets' SPAN that the queries' box meets.
+//        over their box (k_kn_axis_hist), all three read at once (the call's one synchronisation); a uniform f64 grid of C^3 cells (cell_list.h's
+//        Grid3), C ~ sqrt(M / occ) with occ = max(8, k / 2) targets per occupied cell of a surface, over the part of the targets' SPAN that the queries' box meets.
 //        The span is the box cut, per axis, to the bins between the 1 % and 99 % quantiles and widened by a tenth: a clean cloud keeps its box,
 //        and a few points far outside -- what the filter on top exists for -- no longer blow the cells up until the object sits in a handful of
 //        them.  Points outside the grid are clamped into its boundary cells;
@@ -15,8 +15,8 @@
 //        the thread keeps its root, the worst entry, in registers; a candidate that is smaller replaces the root and sinks.  The cube of cells
 //        [c - r, c + r] grows by ONE ring at a time and only the new shell is visited, so that no target is inserted twice.  A query is
 //        CERTIFIED when its list is full and its worst d2 is <= the squared distance to the nearest face of the cube that is not a face of the
-//        grid, the faces pulled in by 1e-12 of the coordinates' magnitude (cloud_metrics.hip's cm_face_bound): a target outside the cube is then
-//        strictly farther than the list's worst, and cannot tie with it.  A cube that covers the grid ends the scan unconditionally.  A query
+//        grid, the faces pulled in by 1e-12 of the coordinates' magnitude (cell_list.h's grid_face_bound has the argument): a target outside the cube
+//        is then strictly farther than the list's worst, and cannot tie with it.  A cube that covers the grid ends the scan unconditionally.  A query
 //        that has seen more than KN_RING_WORK targets (crowded cells) or passed ring KN_RING_MAX (far from every target) goes onto a list;
 //     d. sweep (k_kn_sweep): the queries on that list against ALL targets, staged through LDS in chunks of KN_CHUNK, the same list per thread,
 //        no certificate needed;
@@ -53,40 +53,6 @@ constexpr double KN_TRIM_PAD = 0.1;           // ... widened by this share of th
 constexpr int SOR_T = 256;
 constexpr int SOR_NB = 256;                   // workgroups of the reductions (== SOR_T: one finalize workgroup reads them all)
 enum { MISC_FAR = 2 * BOX_WORDS, MISC_WORDS = 32 };                // behind the two boxes (cell_list.h)
-
-struct KnGrid {
-    double ox, oy, oz, cs;
-    int C;
-};
-
-__device__ __forceinline__ int kn_cell(double x, double o, double cs, int C) {
-    return (int)fmin(fmax(floor((x - o) / cs), 0.0), (double)(C - 1));
-}
-
-// distance from q to the nearest face of the cells [c0, c1] that is not a face of the whole grid, less the safety margin
-__device__ __forceinline__ double kn_face_bound(double q, double o, double cs, int C, int c0, int c1) {
-    double b = 1.0e300;
-    if (c0 > 0) {
-        const double f = o + (double)c0 * cs;
-        b = fmin(b, (q - f) - 1.0e-12 * (fabs(q) + fabs(f)));
-    }
-    if (c1 < C - 1) {
-        const double f = o + (double)(c1 + 1) * cs;
-        b = fmin(b, (f - q) - 1.0e-12 * (fabs(q) + fabs(f)));
-    }
-    return b;
-}
-
-// the key of the cell that point i of P falls (or is clamped) into
-struct KnKey {
-    const float* P;
-    KnGrid g;
-    __device__ uint64_t operator()(int i) const {
-        const int cx = kn_cell((double)P[3 * (size_t)i], g.ox, g.cs, g.C), cy = kn_cell((double)P[3 * (size_t)i + 1], g.oy, g.cs, g.C),
-                  cz = kn_cell((double)P[3 * (size_t)i + 2], g.oz, g.cs, g.C);
-        return (uint64_t)((cz * g.C + cy) * g.C + cx);
-    }
-};
 
 // a. hist[a][b] = targets whose coordinate a falls into bin b of KN_HB equal bins over the targets' box (read from the device: k_point_box ran
 // before on the same stream).  Integer atomics only
@@ -130,8 +96,6 @@ __device__ __forceinline__ KnList kn_list(double* lds, int k, int t) {
     return KnList{lds + t, reinterpret_cast<int*>(lds + KN_LD * k) + t, k, 0, INT_MAX, 1.0e300};
 }
 
-__device__ __forceinline__ bool kn_less(double a, int ai, double b, int bi) { return a < b || (a == b && ai < bi); }
-
 // the pair (d, i) into the max-heap at slots [0, k), from slot p downwards: a child that is larger moves up, the pair settles where none is
 __device__ __forceinline__ void kn_sift(KnList& l, int p, double d, int i) {
     for (int c = 2 * p + 1; c < l.k; c = 2 * p + 1) {
@@ -140,9 +104,9 @@ __device__ __forceinline__ void kn_sift(KnList& l, int p, double d, int i) {
         if (c + 1 < l.k) {
             const double ed = l.sd[(c + 1) * KN_LD];
             const int ei = l.si[(c + 1) * KN_LD];
-            if (kn_less(cd, ci, ed, ei)) { ++c; cd = ed; ci = ei; }
+            if (pair_less(cd, ci, ed, ei)) { ++c; cd = ed; ci = ei; }
         }
-        if (!kn_less(d, i, cd, ci)) break;
+        if (!pair_less(d, i, cd, ci)) break;
         l.sd[p * KN_LD] = cd;
         l.si[p * KN_LD] = ci;
         p = c;
@@ -160,7 +124,7 @@ __device__ __forceinline__ void kn_offer(KnList& l, double d, int i) {
         l.si[l.cnt * KN_LD] = i;
         if (++l.cnt < l.k) return;
         for (int p = l.k / 2 - 1; p >= 0; --p) kn_sift(l, p, l.sd[p * KN_LD], l.si[p * KN_LD]);
-    } else if (kn_less(d, i, l.wd, l.wi)) {
+    } else if (pair_less(d, i, l.wd, l.wi)) {
         kn_sift(l, 0, d, i);
     } else {
         return;
@@ -172,9 +136,7 @@ __device__ __forceinline__ void kn_offer(KnList& l, double d, int i) {
 __device__ __forceinline__ void kn_scan_run(KnList& l, const float4* __restrict__ st, int b, int e, double qx, double qy, double qz) {
     for (int p = b; p < e; ++p) {
         const float4 a = st[p];
-        const double dx = qx - (double)a.x, dy = qy - (double)a.y, dz = qz - (double)a.z;
-        const double d = (dx * dx + dy * dy) + dz * dz;
-        kn_offer(l, d, __float_as_int(a.w));
+        kn_offer(l, point_d2(qx, qy, qz, a), __float_as_int(a.w));
     }
 }
 
@@ -214,7 +176,7 @@ __device__ __forceinline__ void kn_epilogue(KnList& l, double* lds, int t, bool 
 // ---------------------------------------------------------------------------------------------------------------------------
 // c. the ring scan over the Q sorted queries
 __global__ __launch_bounds__(KN_T) void k_kn_ring_scan(const float4* __restrict__ sq, int Q, const float4* __restrict__ st,
-                                                       const int* __restrict__ cstart, KnGrid g, int k, double* __restrict__ d2,
+                                                       const int* __restrict__ cstart, Grid3 g, int k, double* __restrict__ d2,
                                                        int* __restrict__ idx, int* __restrict__ far_list, int* __restrict__ far_n) {
     extern __shared__ double kn_lds[];
     const int t = threadIdx.x;
@@ -227,7 +189,7 @@ __global__ __launch_bounds__(KN_T) void k_kn_ring_scan(const float4* __restrict_
         out = __float_as_int(me.w);
         const double qx = (double)me.x, qy = (double)me.y, qz = (double)me.z;
         const int C = g.C;
-        const int cx = kn_cell(qx, g.ox, g.cs, C), cy = kn_cell(qy, g.oy, g.cs, C), cz = kn_cell(qz, g.oz, g.cs, C);
+        const int cx = g.cell(qx, g.ox), cy = g.cell(qy, g.oy), cz = g.cell(qz, g.oz);
         CellCube in{1, 0, 1, 0, 1, 0};                             // the cube already scanned (none yet)
         int work = 0;
         bool giveup = false;
@@ -249,8 +211,7 @@ __global__ __launch_bounds__(KN_T) void k_kn_ring_scan(const float4* __restrict_
                     }
                 }
             if (giveup) break;
-            const double b = fmin(fmin(kn_face_bound(qx, g.ox, g.cs, C, q.x0, q.x1), kn_face_bound(qy, g.oy, g.cs, C, q.y0, q.y1)),
-                                  kn_face_bound(qz, g.oz, g.cs, C, q.z0, q.z1));
+            const double b = grid_cube_bound(g, qx, qy, qz, q);
             if (q.covers(C) || (l.cnt == k && b > 0.0 && l.wd <= b * b)) { done = true; break; }
             if (r >= KN_RING_MAX) giveup = true;                   // far from every target: a thread of its own would scan most of the grid
             in = q;
@@ -289,11 +250,6 @@ __global__ __launch_bounds__(KN_T) void k_kn_sweep(const float4* __restrict__ sq
         if (have) kn_scan_run(l, s_t, 0, nc, qx, qy, qz);
     }
     kn_epilogue(l, kn_lds, t, have, out, d2, idx);                 // (k <= M: the list is full)
-}
-
-__global__ void k_kn_counts(const int* __restrict__ far_n, int Q, int C, int all_swept, int32_t* __restrict__ counts) {
-    const int n = all_swept ? Q : min(*far_n, Q);
-    counts[0] = Q - n; counts[1] = n; counts[2] = C; counts[3] = 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -482,10 +438,8 @@ extern "C" int pdhip_knn_points(const float* queries, int Q, const float* target
     KnnWs w;
     carve_knn(w, ws, Q, M);
     // a. the boxes, finiteness of both clouds
-    int rc = clear_boxes(w.misc, 2, MISC_WORDS, s);
+    int rc = launch_cloud_boxes(targets, M, queries, Q, w.misc, MISC_WORDS, s);
     if (rc) return rc;
-    k_point_box<<<std::min(cdiv(M, CL_T), 1024), CL_T, 0, s>>>(targets, M, nullptr, M, 1, w.misc);
-    k_point_box<<<std::min(cdiv(Q, CL_T), 1024), CL_T, 0, s>>>(queries, Q, nullptr, Q, 1, w.misc + BOX_WORDS);
     const bool trimmed = g_knn_path != 2;
     static thread_local uint32_t h_hist[3 * KN_HB];
     if (trimmed) {
@@ -494,41 +448,23 @@ extern "C" int pdhip_knn_points(const float* queries, int Q, const float* target
         PD_LAUNCH_CHECK();
         PD_HIP(hipMemcpyAsync(h_hist, w.hist, sizeof(h_hist), hipMemcpyDeviceToHost, s));       // (arrives with the boxes: one synchronisation)
     }
-    PD_LAUNCH_CHECK();
     HostBox box[2];                                                // targets, queries
-    rc = read_boxes(w.misc, box, s);
+    rc = read_cloud_boxes("pdhip_knn_points", w.misc, box, s);
     if (rc) return rc;
-    PD_REQUIRE(box[0].bad == 0, "pdhip_knn_points: %u target(s) with a non-finite coordinate", box[0].bad);
-    PD_REQUIRE(box[1].bad == 0, "pdhip_knn_points: %u query point(s) with a non-finite coordinate", box[1].bad);
     // the grid covers the part of the targets' span (their box between the outer quantiles of every axis) that the queries' box meets, or the whole
-    // span if they do not meet, as pdhip_nearest_points' covers the part of the box
-    double mn[3], lo[3], hi[3], ext = 0.0;
-    bool meet = true;
+    // span if they do not meet
+    double t0[3], t1[3], mn[3];
     for (int a = 0; a < 3; ++a) {
-        double t0 = box[0].mn[a], t1 = box[0].mx[a];
-        if (trimmed) kn_trimmed_span(h_hist + a * KN_HB, M, box[0].mn[a], box[0].mx[a], t0, t1);
-        mn[a] = t0;
-        ext = std::max(ext, t1 - t0);
-        lo[a] = std::max(t0, box[1].mn[a]);
-        hi[a] = std::min(t1, box[1].mx[a]);
-        meet = meet && lo[a] <= hi[a];
+        t0[a] = box[0].mn[a]; t1[a] = box[0].mx[a];
+        if (trimmed) kn_trimmed_span(h_hist + a * KN_HB, M, box[0].mn[a], box[0].mx[a], t0[a], t1[a]);
     }
-    if (meet) {
-        ext = 0.0;
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = lo[a];
-            ext = std::max(ext, hi[a] - lo[a]);
-        }
-    }
-    KnGrid g;
-    g.C = ext > 0.0 ? (g_knn_cells >= 1 ? g_knn_cells : kn_cells_axis(M, k)) : 1;      // (a box without extent: one cell)
-    g.cs = ext > 0.0 ? ext / g.C * (1.0 + 1.0e-6) : 1.0;
-    g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2];
+    const double ext = meet_boxes(t0, t1, box[1], mn);
+    const Grid3 g = grid_over(mn, ext, g_knn_cells >= 1 ? g_knn_cells : kn_cells_axis(M, k));
     const int nc = g.C * g.C * g.C;
     // b. both clouds in cell order
-    int cur = sort_by_cell(w.sb, M, KnKey{targets, g}, (unsigned long long)nc, w.cstart, s);
+    int cur = sort_by_cell(w.sb, M, GridPointKey{targets, g}, (unsigned long long)nc, w.cstart, s);
     k_gather_xyzi<<<cdiv(M, CL_T), CL_T, 0, s>>>(w.sb.v[cur], targets, M, w.st);
-    cur = sort_by_cell(w.sb, Q, KnKey{queries, g}, (unsigned long long)nc, nullptr, s);       // (the queries need the order only)
+    cur = sort_by_cell(w.sb, Q, GridPointKey{queries, g}, (unsigned long long)nc, nullptr, s);       // (the queries need the order only)
     k_gather_xyzi<<<cdiv(Q, CL_T), CL_T, 0, s>>>(w.sb.v[cur], queries, Q, w.sq);
     PD_LAUNCH_CHECK();
     // c, d, e.
@@ -540,7 +476,7 @@ extern "C" int pdhip_knn_points(const float* queries, int Q, const float* target
     for (int p : {7919, 7907, 7901, 7883})                         // (primes: one of them does not divide M <= 2^26 < 7919 * 7907)
         if (M % p != 0) { stride = p; break; }
     k_kn_sweep<<<cdiv(Q, KN_T), KN_T, lds, s>>>(w.sq, all_swept ? nullptr : w.far_list, far_n, Q, w.st, M, stride, k, d2, idx);
-    k_kn_counts<<<1, 1, 0, s>>>(far_n, Q, g.C, all_swept, counts);
+    k_split_counts<<<1, 1, 0, s>>>(far_n, Q, g.C, all_swept, counts);
     PD_LAUNCH_CHECK();
     return PDHIP_OK;
 }

@@ -7,23 +7,23 @@
 //     is culled, as long as every face that is culled has a LARGER value than the winner.
 //     a. k_point_box (cell_list.h): faces checked against [0, Vn), the box of the REFERENCED vertices, their finiteness and that of the points;
 //        k_md_degenerate counts the faces whose normal is exactly zero; one small read that synchronises the stream.  A grid of C^3 cells over the
-//        mesh's box, C ~ sqrt(F / 32);
+//        mesh's box (cell_list.h's Grid3, plus gmax), C ~ sqrt(F / 32);
 //     b. every face gets a key (MdFaceKey): the cell of its box's min corner when it is SMALL (the cells of the two corners differ by at most one
 //        per axis, so the face lies inside the cells [k, k + 1] per axis, and its closest-point arithmetic is well conditioned: below), C^3 when it is
 //        LARGE, C^3 + 1 when it is degenerate.  One sort (cell_list.h) leaves [small faces by cell | large | degenerate], cstart[C^3] and
 //        cstart[C^3 + 1] are where the last two start; the faces are gathered in that order as nine f32 coordinates and the index (widened where
 //        they are used: 40 bytes per face instead of 80, which doubles the faces of an LDS chunk of the all-faces scan);
-//     c. the queries are sorted by the cell they fall (or are clamped) into, so that neighbouring threads scan the same cells;
+//     c. the queries are sorted by the cell they fall (or are clamped) into (cell_list.h's GridPointKey), so that neighbouring threads scan the same cells;
 //     d. k_md_ring_scan, one thread per query: the large list first, then the keys [c - r - 1, c + r] per axis for r = 1, 2, 4, 8.  A small face that
 //        was not scanned lies outside the cells [c - r, c + r], beyond a face of that cube that is not a face of the grid; the query is CERTIFIED when
 //        its best d2 is <= the square of its distance to the nearest such face (md_face_bound), or when the cube is the whole grid;
 //     e. a query still open after r = 8, or whose rings hold more than MD_RING_WORK faces, or facing a large list of more than MD_LARGE_WORK, or whose next cube is the whole grid of a mesh of more than
-//        MD_COVER_WORK live faces (one thread would scan them all), goes to the all-faces scan (k_md_far_scan, k_md_far_pick):
+//        MD_COVER_WORK live faces (one thread would scan them all), goes to the all-faces scan (cell_list.h's k_far_scan, k_far_pick with MdFar):
 //        a tile of MD_T such queries per workgroup, the live faces staged in LDS, cut into MD_FAR_SLABS slabs; no certificate needed;
 //     f. k_md_closest recomputes the winner's closest point from the caller's arrays (the same operations, so the same bits): the scans keep only
 //        (d2, face) in registers.
-//   The guard of the certificate.  cloud_metrics.hip pulls a cube's faces in by 1e-12 of the coordinates' magnitude, which covers the rounding of a
-//   point difference.  A triangle's closest point is computed less accurately: in the interior region x = a + ab v + ac w with v = vb / (va + vb + vc),
+//   The guard of the certificate.  cell_list.h's grid_face_bound pulls a cube's faces in by 1e-12 of the coordinates' magnitude, which covers the
+//   rounding of a point difference.  A triangle's closest point is computed less accurately: in the interior region x = a + ab v + ac w with v = vb / (va + vb + vc),
 //   and va, vb, vc are differences of products of magnitude (L D)^2 (L the edge length, D the distance of the query) while their sum is |n|^2, so
 //   the computed x can leave the triangle, within its plane, by about 2^-53 D^2 L^3 / |n|^2.  Hence (i) the guard here is 1e-7 of (|q| + the largest
 //   coordinate magnitude of the mesh's box), and (ii) a face for which 64 * 2^-53 Dc^2 Lmax^3 / |n|^2, with Dc = 18 cells + Lmax the largest
@@ -59,10 +59,8 @@ constexpr double MD_GUARD = 1.0e-7;
 // behind the two boxes (cell_list.h) a third block of BOX_WORDS words read with them: its BOX_BAD word counts the degenerate faces
 enum { MISC_DEG = 2 * BOX_WORDS + BOX_BAD, MISC_FAR = 3 * BOX_WORDS, MISC_WORDS = 32 };
 
-struct MdGrid {
-    double ox, oy, oz, cs;
+struct MdGrid : Grid3 {
     double gmax;                              // largest coordinate magnitude of the mesh's box
-    int C;
 };
 
 struct alignas(8) MdFace {
@@ -72,10 +70,6 @@ struct alignas(8) MdFace {
 
 __host__ __device__ __forceinline__ int md_imax(int a, int b) { return a > b ? a : b; }
 __host__ __device__ __forceinline__ int md_imin(int a, int b) { return a < b ? a : b; }
-
-__host__ __device__ __forceinline__ int md_cell(double x, double o, double cs, int C) {
-    return (int)fmin(fmax(floor((x - o) / cs), 0.0), (double)(C - 1));
-}
 
 // distance from q to the nearest face of the cells [c0, c1] that is not a face of the whole grid, less the guard
 __host__ __device__ __forceinline__ double md_face_bound(double q, double o, double cs, int C, int c0, int c1, double gmax) {
@@ -134,11 +128,6 @@ __host__ __device__ __forceinline__ double md_face_d2(double qx, double qy, doub
                       (double)f.c[1], (double)f.c[2], x, y, z);
 }
 
-// a NaN never wins (both comparisons are false for it); of equal values the smaller index
-__host__ __device__ __forceinline__ void md_take(double d, int k, double& bd, int& bi) {
-    if (d < bd || (d == bd && k < bi)) { bd = d; bi = k; }
-}
-
 __host__ __device__ __forceinline__ bool md_degenerate(double ax, double ay, double az, double bx, double by, double bz, double cx, double cy, double cz,
                                               double& n2) {
     const double abx = bx - ax, aby = by - ay, abz = bz - az, acx = cx - ax, acy = cy - ay, acz = cz - az;
@@ -184,9 +173,9 @@ struct MdFaceKey {
         double n2;
         if (md_degenerate(ax, ay, az, bx, by, bz, cx, cy, cz, n2)) return large + 1;
         if (all_large) return large;
-        const int x0 = md_cell(fmin(fmin(ax, bx), cx), g.ox, g.cs, C), x1 = md_cell(fmax(fmax(ax, bx), cx), g.ox, g.cs, C);
-        const int y0 = md_cell(fmin(fmin(ay, by), cy), g.oy, g.cs, C), y1 = md_cell(fmax(fmax(ay, by), cy), g.oy, g.cs, C);
-        const int z0 = md_cell(fmin(fmin(az, bz), cz), g.oz, g.cs, C), z1 = md_cell(fmax(fmax(az, bz), cz), g.oz, g.cs, C);
+        const int x0 = g.cell(fmin(fmin(ax, bx), cx), g.ox), x1 = g.cell(fmax(fmax(ax, bx), cx), g.ox);
+        const int y0 = g.cell(fmin(fmin(ay, by), cy), g.oy), y1 = g.cell(fmax(fmax(ay, by), cy), g.oy);
+        const int z0 = g.cell(fmin(fmin(az, bz), cz), g.oz), z1 = g.cell(fmax(fmax(az, bz), cz), g.oz);
         if (x1 - x0 > 1 || y1 - y0 > 1 || z1 - z0 > 1) return large;
         // conditioning of the closest-point arithmetic (header comment)
         const double l1 = md_dot(bx - ax, by - ay, bz - az, bx - ax, by - ay, bz - az), l2 = md_dot(cx - ax, cy - ay, cz - az, cx - ax, cy - ay, cz - az),
@@ -211,17 +200,6 @@ __global__ void k_md_gather(const int* __restrict__ val, const float* __restrict
     sf[p] = f;
 }
 
-// c. the key of the cell that point i of P falls (or is clamped) into
-struct MdPointKey {
-    const float* P;
-    MdGrid g;
-    __device__ uint64_t operator()(int i) const {
-        const int cx = md_cell((double)P[3 * (size_t)i], g.ox, g.cs, g.C), cy = md_cell((double)P[3 * (size_t)i + 1], g.oy, g.cs, g.C),
-                  cz = md_cell((double)P[3 * (size_t)i + 2], g.oz, g.cs, g.C);
-        return (uint64_t)((cz * g.C + cy) * g.C + cx);
-    }
-};
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // d. one query against the large list and the rings of the cell list.  cstart[nc] / cstart[nc + 1]: where the large / the degenerate faces start in
 // sf.  True: (bd, bi) is the result.  False: the query goes to the all-faces scan.  (Host code as well, like the functions it calls: a host program can run the very cull against the oracle without a device.)
@@ -235,10 +213,10 @@ __host__ __device__ __forceinline__ bool md_ring_query(double qx, double qy, dou
     bi = INT_MAX;
     for (int p = lb; p < le; ++p) {
         const MdFace f = sf[p];
-        md_take(md_face_d2(qx, qy, qz, f), f.idx, bd, bi);
+        take_min(md_face_d2(qx, qy, qz, f), f.idx, bd, bi);
     }
     if (lb == 0) return true;                                      // no small face: every live face has been scanned
-    const int cx = md_cell(qx, g.ox, g.cs, C), cy = md_cell(qy, g.oy, g.cs, C), cz = md_cell(qz, g.oz, g.cs, C);
+    const int cx = g.cell(qx, g.ox), cy = g.cell(qy, g.oy), cz = g.cell(qz, g.oz);
     for (int r = 1;; r *= 2) {
         // the cells [c - r, c + r] the certificate speaks about; a face that can reach them has a key in [c - r - 1, c + r]
         const int x0 = md_imax(cx - r, 0), x1 = md_imin(cx + r, C - 1), y0 = md_imax(cy - r, 0), y1 = md_imin(cy + r, C - 1), z0 = md_imax(cz - r, 0),
@@ -254,7 +232,7 @@ __host__ __device__ __forceinline__ bool md_ring_query(double qx, double qy, dou
                 if (work > MD_RING_WORK) return false;             // crowded cells
                 for (int p = b; p < e; ++p) {
                     const MdFace f = sf[p];
-                    md_take(md_face_d2(qx, qy, qz, f), f.idx, bd, bi);
+                    take_min(md_face_d2(qx, qy, qz, f), f.idx, bd, bi);
                 }
             }
         const double b = fmin(fmin(md_face_bound(qx, g.ox, g.cs, C, x0, x1, g.gmax), md_face_bound(qy, g.oy, g.cs, C, y0, y1, g.gmax)),
@@ -282,56 +260,18 @@ __global__ __launch_bounds__(MD_P2_T) void k_md_ring_scan(const float4* __restri
     face[o] = bi == INT_MAX ? -1 : bi;
 }
 
-// e. every live face against every query of the list.  Workgroup (tile, slab): MD_T queries against one slab of sf[0 .. cstart[nc + 1]), staged in LDS
-__global__ __launch_bounds__(MD_T) void k_md_far_scan(const float4* __restrict__ sq, const int* __restrict__ far_list, const int* __restrict__ far_n,
-                                                      int Q, const MdFace* __restrict__ sf, const int* __restrict__ n_live, int F,
-                                                      double* __restrict__ part_d2, int* __restrict__ part_idx) {
-    __shared__ MdFace s_f[MD_CHUNK];
-    const int t = threadIdx.x;
-    const int n = min(*far_n, Q);
-    if ((int)blockIdx.x * MD_T >= n) return;                       // (the whole workgroup)
-    const int i = blockIdx.x * MD_T + t;
-    const bool have = i < n;
-    double qx = 0.0, qy = 0.0, qz = 0.0;
-    if (have) {
-        const float4 me = sq[far_list[i]];
-        qx = (double)me.x; qy = (double)me.y; qz = (double)me.z;
+// e. every live face sf[0 .. cstart[nc + 1]) against every query of the list (cell_list.h's k_far_scan / k_far_pick)
+struct MdFar {
+    const int* n_live;
+    int F;
+    __device__ int live() const { return min(max(*n_live, 0), F); }
+    __device__ double d2(double qx, double qy, double qz, const MdFace& f, int& k) const {
+        k = f.idx;
+        return md_face_d2(qx, qy, qz, f);
     }
-    const int M = min(max(*n_live, 0), F);
-    const int per = (M + MD_FAR_SLABS - 1) / MD_FAR_SLABS;
-    const int b0 = min(M, (int)blockIdx.y * per), e0 = min(M, b0 + per);
-    double bd = INFINITY;
-    int bi = INT_MAX;
-    for (int base = b0; base < e0; base += MD_CHUNK) {
-        const int nc = min(MD_CHUNK, e0 - base);
-        __syncthreads();
-        for (int j = t; j < nc; j += MD_T) s_f[j] = sf[base + j];
-        __syncthreads();
-        if (have) {
-            for (int j = 0; j < nc; ++j) {
-                const MdFace f = s_f[j];
-                md_take(md_face_d2(qx, qy, qz, f), f.idx, bd, bi);
-            }
-        }
-    }
-    if (have) {
-        part_d2[(size_t)blockIdx.y * Q + i] = bd;
-        part_idx[(size_t)blockIdx.y * Q + i] = bi;
-    }
-}
-
-__global__ __launch_bounds__(MD_T) void k_md_far_pick(const float4* __restrict__ sq, const int* __restrict__ far_list, const int* __restrict__ far_n,
-                                                      int Q, const double* __restrict__ part_d2, const int* __restrict__ part_idx,
-                                                      double* __restrict__ d2, int* __restrict__ face) {
-    const int i = blockIdx.x * MD_T + threadIdx.x;
-    if (i >= min(*far_n, Q)) return;
-    double bd = INFINITY;
-    int bi = INT_MAX;
-    for (int sl = 0; sl < MD_FAR_SLABS; ++sl) md_take(part_d2[(size_t)sl * Q + i], part_idx[(size_t)sl * Q + i], bd, bi);
-    const int o = __float_as_int(sq[far_list[i]].w);
-    d2[o] = bd;
-    face[o] = bi == INT_MAX ? -1 : bi;
-}
+    static __device__ double none() { return INFINITY; }
+    static __device__ int index(int bi) { return bi == INT_MAX ? -1 : bi; }
+};
 
 // f. the winner's closest point, from the caller's arrays
 __global__ __launch_bounds__(MD_T) void k_md_closest(const float* __restrict__ V, const int64_t* __restrict__ faces, const float* __restrict__ P, int Q,
@@ -429,29 +369,21 @@ extern "C" int pdhip_closest_on_mesh(const float* vertices, int Vn, const int64_
         PD_HIP(hipMemsetAsync(counts, 0, 4 * sizeof(int32_t), s));
         return PDHIP_OK;
     }
-    MdGrid g;
-    double ext = 0.0;
-    g.gmax = 0.0;
-    for (int a = 0; a < 3; ++a) {
-        ext = std::max(ext, box[0].mx[a] - box[0].mn[a]);
-        g.gmax = std::max(g.gmax, std::max(fabs(box[0].mn[a]), fabs(box[0].mx[a])));
-    }
-    g.C = ext > 0.0 ? (g_md_cells > 0 ? g_md_cells : cells_axis(F)) : 1;
-    g.cs = ext > 0.0 ? ext / g.C * (1.0 + 1.0e-6) : 1.0;
-    g.ox = box[0].mn[0]; g.oy = box[0].mn[1]; g.oz = box[0].mn[2];
+    MdGrid g{grid_over(box[0].mn, box_extent(box[0].mn, box[0].mx), g_md_cells > 0 ? g_md_cells : cells_axis(F)), 0.0};
+    for (int a = 0; a < 3; ++a) g.gmax = std::max(g.gmax, std::max(fabs(box[0].mn[a]), fabs(box[0].mx[a])));
     const int nc = g.C * g.C * g.C;
     // b. the faces: [small by cell | large | degenerate]
     int cur = sort_by_cell(w.sb, F, MdFaceKey{vertices, faces, g, g_md_path == 1}, (unsigned long long)nc + 1, w.cstart, s);
     k_md_gather<<<cdiv(F, CL_T), CL_T, 0, s>>>(w.sb.v[cur], vertices, faces, F, w.sf);
     // c. the queries in cell order
-    cur = sort_by_cell(w.sb, Q, MdPointKey{points, g}, (unsigned long long)nc, nullptr, s);
+    cur = sort_by_cell(w.sb, Q, GridPointKey{points, g}, (unsigned long long)nc, nullptr, s);
     k_gather_xyzi<<<cdiv(Q, CL_T), CL_T, 0, s>>>(w.sb.v[cur], points, Q, w.sq);
     PD_LAUNCH_CHECK();
     // d, e, f.
     int* far_n = reinterpret_cast<int*>(w.misc + MISC_FAR);
     k_md_ring_scan<<<cdiv(Q, MD_P2_T), MD_P2_T, 0, s>>>(w.sq, Q, w.sf, w.cstart, g, g_md_path == 2, d2, face, w.far_list, far_n);
-    k_md_far_scan<<<dim3(cdiv(Q, MD_T), MD_FAR_SLABS), MD_T, 0, s>>>(w.sq, w.far_list, far_n, Q, w.sf, w.cstart + nc + 1, F, w.part_d2, w.part_idx);
-    k_md_far_pick<<<cdiv(Q, MD_T), MD_T, 0, s>>>(w.sq, w.far_list, far_n, Q, w.part_d2, w.part_idx, d2, face);
+    k_far_scan<MD_T, MD_CHUNK, MD_FAR_SLABS><<<dim3(cdiv(Q, MD_T), MD_FAR_SLABS), MD_T, 0, s>>>(w.sq, w.far_list, far_n, Q, w.sf, MdFar{w.cstart + nc + 1, F}, w.part_d2, w.part_idx);
+    k_far_pick<MD_T, MD_FAR_SLABS, MdFar><<<cdiv(Q, MD_T), MD_T, 0, s>>>(w.sq, w.far_list, far_n, Q, w.part_d2, w.part_idx, d2, face);
     if (closest != nullptr) k_md_closest<<<cdiv(Q, MD_T), MD_T, 0, s>>>(vertices, faces, points, Q, face, closest);
     k_md_counts<<<1, 1, 0, s>>>(far_n, w.cstart, nc, Q, F, counts);
     PD_LAUNCH_CHECK();

@@ -5,7 +5,7 @@
 //   pdhip_fps        idx[0] = start, min_d2[0] = +inf; after pick k every unselected point i carries mind[i] = min over the picks so far of d2(i, pick),
 //                    d2 = (dx dx + dy dy) + dz dz with the f32 inputs widened to f64, op by op (pdhip_nearest_points' convention); pick k + 1 is the
 //                    unselected point with the largest mind (the smallest original index on a tie), min_d2[k + 1] that value.
-//     a. the box and a finiteness test (cell_list.h; one small read that synchronises the stream); a uniform grid of C^3 cells, C ~ cbrt(N / 32) <= 40;
+//     a. the box and a finiteness test (cell_list.h; one small read that synchronises the stream); a uniform grid of C^3 cells (cell_list.h's Grid3), C ~ cbrt(N / 32) <= 40;
 //     b. the points sorted by cell key, cstart, the sorted (x, y, z, index) copy (cell_list.h);
 //     c. k_fps_init: mind against `start` (-1 marks a selected point); k_fps_cells, a wave per cell: the TIGHT box of the cell's own points and the
 //        cell's entry (largest mind among its unselected points, tag = original index << 32 | sorted position of the smallest index that attains it);
@@ -40,25 +40,6 @@ constexpr int FPS_CELLS_MAX = 40;             // cells per axis: 40^3 cells are 
 constexpr double FPS_OCC = 32.0;              // C = cbrt(N / FPS_OCC)
 constexpr int OMC_NMAX = 1 << 26;
 enum { MISC_OCC = BOX_WORDS, MISC_WORDS = 16 };               // behind the box (cell_list.h)
-
-struct FpsGrid {
-    double ox, oy, oz, cs;
-    int C;
-};
-
-__device__ __forceinline__ int fps_cell(double x, double o, double cs, int C) {
-    return (int)fmin(fmax(floor((x - o) / cs), 0.0), (double)(C - 1));
-}
-
-struct FpsKey {
-    const float* P;
-    FpsGrid g;
-    __device__ uint64_t operator()(int i) const {
-        const int cx = fps_cell((double)P[3 * (size_t)i], g.ox, g.cs, g.C), cy = fps_cell((double)P[3 * (size_t)i + 1], g.oy, g.cs, g.C),
-                  cz = fps_cell((double)P[3 * (size_t)i + 2], g.oz, g.cs, g.C);
-        return (uint64_t)((cz * g.C + cy) * g.C + cx);
-    }
-};
 
 // an entry: the largest value, and of those that attain it the smallest tag.  (-1, ~0) is the entry of nothing: every mind is >= 0
 struct Entry {
@@ -141,7 +122,7 @@ __global__ __launch_bounds__(CL_T) void k_fps_cells(const float4* __restrict__ s
 // ---------------------------------------------------------------------------------------------------------------------------
 // d. the pick loop.  mind, cmax and ctag are written by one wave and read by another after a __syncthreads: no __restrict__ on them
 __global__ __launch_bounds__(FPS_T) void k_fps_picks(const float4* __restrict__ sp, int N, int M, int start, const int* __restrict__ cstart,
-                                                     const float4* __restrict__ cbox, FpsGrid g, int ng, double* mind, double* cmax,
+                                                     const float4* __restrict__ cbox, Grid3 g, int ng, double* mind, double* cmax,
                                                      unsigned long long* ctag, const uint32_t* __restrict__ misc, int32_t* __restrict__ idx,
                                                      double* __restrict__ min_d2, int32_t* __restrict__ counts) {
     __shared__ double s_gv[FPS_T];
@@ -200,13 +181,13 @@ __global__ __launch_bounds__(FPS_T) void k_fps_picks(const float4* __restrict__ 
         const double sx = (double)sf.x, sy = (double)sf.y, sz = (double)sf.z;
         __syncthreads();
         // the cube of cells that [s - R, s + R] reaches.  A point that changes has fl(dx dx) <= d2 < R^2 (adding non-negative terms is monotone), so its
-        // |x - s| is below R (1 + 2^-52); R is widened by 1e-9 of itself, far more, and fps_cell is monotone in x: no such point's cell is left out.
+        // |x - s| is below R (1 + 2^-52); R is widened by 1e-9 of itself, far more, and Grid3::cell is monotone in x: no such point's cell is left out.
         // A cell too many costs one bound test
         const double R = sqrt(pick.v) * (1.0 + 1.0e-9) + 1.0e-300;
-        const int x0 = fps_cell(sx - R, g.ox, g.cs, C), x1 = fps_cell(sx + R, g.ox, g.cs, C);
-        const int y0 = fps_cell(sy - R, g.oy, g.cs, C), y1 = fps_cell(sy + R, g.oy, g.cs, C);
-        const int z0 = fps_cell(sz - R, g.oz, g.cs, C), z1 = fps_cell(sz + R, g.oz, g.cs, C);
-        const int cs_ = (fps_cell(sz, g.oz, g.cs, C) * C + fps_cell(sy, g.oy, g.cs, C)) * C + fps_cell(sx, g.ox, g.cs, C);
+        const int x0 = g.cell(sx - R, g.ox), x1 = g.cell(sx + R, g.ox);
+        const int y0 = g.cell(sy - R, g.oy), y1 = g.cell(sy + R, g.oy);
+        const int z0 = g.cell(sz - R, g.oz), z1 = g.cell(sz + R, g.oz);
+        const int cs_ = (g.cell(sz, g.oz) * C + g.cell(sy, g.oy)) * C + g.cell(sx, g.ox);
         const int nx = x1 - x0 + 1, ny = y1 - y0 + 1, ncube = nx * ny * (z1 - z0 + 1);
         for (int base = 0; base < ncube; base += FPS_T) {           // (cell j of the cube goes to wave j % 16: neighbouring cells, which pass the
             const int j = base + lane * FPS_WAVES + wave;          // test together, are updated by different waves at the same time)
@@ -364,21 +345,16 @@ extern "C" int pdhip_fps(const float* points, int N, int M, int start, int32_t* 
     // a. the box, finiteness
     int rc = clear_boxes(w.misc, 1, MISC_WORDS, s);
     if (rc) return rc;
-    k_point_box<<<std::min(cdiv(N, CL_T), 1024), CL_T, 0, s>>>(points, N, nullptr, N, 1, w.misc);
+    launch_point_box(points, N, w.misc, s);
     PD_LAUNCH_CHECK();
     HostBox box[1];
     rc = read_boxes(w.misc, box, s);
     if (rc) return rc;
     PD_REQUIRE(box[0].bad == 0, "pdhip_fps: %u point(s) with a non-finite coordinate", box[0].bad);
-    double ext = 0.0;
-    for (int a = 0; a < 3; ++a) ext = std::max(ext, box[0].mx[a] - box[0].mn[a]);
-    FpsGrid g;
-    g.C = ext <= 0.0 ? 1 : (g_fps_cells >= 1 && g_fps_cells <= FPS_CELLS_MAX ? g_fps_cells : cells_axis(N));      // (a box without extent: one cell)
-    g.cs = ext > 0.0 ? ext / g.C * (1.0 + 1.0e-6) : 1.0;
-    g.ox = box[0].mn[0]; g.oy = box[0].mn[1]; g.oz = box[0].mn[2];
+    const Grid3 g = grid_over(box[0].mn, box_extent(box[0].mn, box[0].mx), g_fps_cells >= 1 && g_fps_cells <= FPS_CELLS_MAX ? g_fps_cells : cells_axis(N));
     const int nc = g.C * g.C * g.C, ng = cdiv(nc, FPS_G), ncp = ng * FPS_G;
     // b. the points in cell order
-    const int cur = sort_by_cell(w.sb, N, FpsKey{points, g}, (unsigned long long)nc, w.cstart, s);
+    const int cur = sort_by_cell(w.sb, N, GridPointKey{points, g}, (unsigned long long)nc, w.cstart, s);
     k_gather_xyzi<<<cdiv(N, CL_T), CL_T, 0, s>>>(w.sb.v[cur], points, N, w.sp);
     // c. mind against `start`, the cells' boxes and entries
     k_fps_init<<<cdiv(N, CL_T), CL_T, 0, s>>>(w.sp, N, points, start, w.mind);

@@ -146,11 +146,12 @@ def test_no_scratch_on_the_mesh_distance_kernels():
         _lib()
     pytest.importorskip('msgpack')                          # (as tests/test_code_objects_cpu.py: the metadata note is msgpack)
     from tools import code_object_notes
-    mine = [k for k in code_object_notes.kernels(LIB) if 'k_md_' in k['name'] or 'MdFaceKey' in k['name'] or 'MdPointKey' in k['name']]
-    names = ' '.join(k['name'] for k in mine)
-    for must in ('k_md_degenerate', 'MdFaceKey', 'MdPointKey', 'k_md_gather', 'k_md_ring_scan', 'k_md_far_scan', 'k_md_far_pick', 'k_md_closest',
-                 'k_md_counts'):
-        assert must in names, must
+    # (GridPointKey: csrc/cell_list.h's key of the shared f64 grid, every including unit's copy; MdFar: its far scan pair instantiated for this unit)
+    mine = [k for k in code_object_notes.kernels(LIB)
+            if 'k_md_' in k['name'] or 'MdFaceKey' in k['name'] or 'GridPointKey' in k['name'] or 'MdFar' in k['name']]
+    for must in (('k_md_degenerate',), ('MdFaceKey',), ('k_cell_keys', 'GridPointKey'), ('k_md_gather',), ('k_md_ring_scan',), ('k_far_scan', 'MdFar'),
+                 ('k_far_pick', 'MdFar'), ('k_md_closest',), ('k_md_counts',)):
+        assert any(all(m in k['name'] for m in must) for k in mine), must            # (both parts in ONE kernel's name)
     for k in mine:
         print(k['name'], 'vgprs', k['vgpr_count'], 'lds', k['group_segment_fixed_size'], 'scratch', k['private_segment_fixed_size'])
         assert k['arch'] == 'gfx950'

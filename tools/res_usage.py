@@ -10,6 +10,7 @@ for b in re.split(r'remark: [^\n]*Function Name: ', t)[1:]:
     except Exception:
         pass
     g = lambda k: int(re.search(k + r': (\d+)', b).group(1))
-    v, sg, sp, sc, occ = g('VGPRs'), g('SGPRs'), g('VGPRs Spill'), g(r'ScratchSize \[bytes/lane\]'), g(r'Occupancy \[waves/SIMD\]')
+    v, sg, sp, sc, occ, lds = (g('VGPRs'), g('SGPRs'), g('VGPRs Spill'), g(r'ScratchSize \[bytes/lane\]'), g(r'Occupancy \[waves/SIMD\]'),
+                               g(r'LDS Size \[bytes/block\]'))
     if show_all or sp or sc:
-        print(f"{name[-90:]:90s} VGPR {v:3d} SGPR {sg:3d} spill {sp:3d} scratch {sc:4d} occ {occ}")
+        print(f"{name[-90:]:90s} VGPR {v:3d} SGPR {sg:3d} spill {sp:3d} scratch {sc:4d} occ {occ} LDS {lds:6d}")
