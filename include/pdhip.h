@@ -871,6 +871,46 @@ int pdhip_mesh_boundary_vertices(const int64_t* faces, int F, int Vn, const int3
 int pdhip_smooth_mesh(const float* vertices, int Vn, const int32_t* rowptr, const int32_t* colidx, const uint8_t* held_or_null, int steps,
                       double lambda, double mu, double* state_a, double* state_b, float* out_vertices, int32_t* counts, void* stream);
 
+/* ---- welding of close vertices and cleaning of a face list (csrc/mesh_clean.hip; the reference gets both from trimesh's merge_vertices and
+ * pymeshlab's "Merge Close Vertices", "Remove Duplicate Faces", "Remove Unreferenced Vertices").  The first step of the mesh chain for SUPPLIED meshes:
+ * clean -> components -> smooth -> decimate -> unwrap -> texture.  EVERY buffer is an argument the caller allocates: there is no workspace and no size
+ * query; each entry is told the length of every temporary and refuses a short one by name.
+ * pdhip_weld_vertices: vertices (device [Vn,3] f32), tol (a finite double >= 0) -> rep (device [Vn] i32).  Vertices i and j are CLOSE when
+ * d2(i, j) <= tol * tol, with d2 = (dx dx + dy dy) + dz dz on the f32 coordinates widened to f64, one rounding per operation, none fused (so
+ * d2(i, j) == d2(j, i) bit for bit), and tol * tol one f64 product.  tol == 0 merges exactly equal coordinates; -0.0 equals +0.0.  A CLASS is a connected
+ * component of the closeness graph (single linkage: a chain of close pairs is one class however long), rep[v] the smallest index of v's class.  rep
+ * is a function of the vertex array alone -- not of the grid, the scan order or the threads' order -- and equals the all-pairs definition bit for bit
+ * (mesh_clean.hip's header has the proof); two calls give equal bytes.  counts (device [4] i32): classes, vertices merged away (Vn - classes), cells per
+ * axis of the grid, vertices whose scan needed more than the 27 cells around their own.  The grid: C^3 cubic cells over the vertices' box, C = min(
+ * pdhip_weld_cells_axis(Vn) = clamp(floor(sqrt(Vn / 8)), 1, 256), floor(ext / (1.001 tol + 4e-12 max|coordinate|))), at least 1, ext = the box's
+ * longest edge, cell edge ext / C * (1 + 1e-6): always larger than tol.  Temporaries (device; their contents before and after mean nothing):
+ *   keys_a, keys_b [sort_len] u64 and vals_a, vals_b [sort_len] i32, sort_len >= Vn;  hist [hist_words] i32, hist_words >= 512 * ceil(Vn / 2048);
+ *   cstart [cstart_len] i32, cstart_len >= pdhip_weld_cells_axis(Vn)^3 + 1;  sorted_xyzi [sorted_len, 4] f32, sorted_len >= Vn rows, 16-byte aligned;
+ *   parent [parent_len] i32, parent_len >= Vn;  misc [misc_len] i32, misc_len >= 64.
+ * Cost: every vertex visits the vertices of the cells around it, so n vertices in one cell cost n^2 steps or more (all vertices at one point:
+ * Vn^2); nothing but Vn bounds it.  PDHIP_E_ARG with the cause, rep and counts untouched: a null pointer (named), Vn < 1, Vn > 2^26, tol negative,
+ * NaN or infinite, a temporary that is too short (named, with both lengths), sorted_xyzi not 16-byte aligned, vertices with a non-finite coordinate
+ * (their number is named).  SYNCHRONISES the stream twice: the read of the box (32 bytes), and the read of the check words after the last launch.
+ * A union-find walk is bounded by 2 Vn + 64 steps; should one use them up, PDHIP_E_STATE.
+ * pdhip_clean_faces: faces (device [F,3] i64) and rep (device [Vn] i32, pdhip_weld_vertices' output; the identity cleans without welding) ->
+ * out_faces (device [F,3] i64): EVERY face with each index replaced by its representative, winding and corner order kept; keep (device [F] u8): 1 for
+ * the faces that stay.  A face is DEGENERATE when two of its three new indices are equal; two non-degenerate faces are DUPLICATES when their sorted
+ * index triples are equal (orientation ignored, as MeshLab does), and of each set of duplicates the smallest face index stays.  counts (device [4]
+ * i32): degenerate, duplicate, kept, 0 (they add up to F).  pdhip_compact_mesh(vertices, out_faces, keep) then gives the cleaned mesh: surviving
+ * faces in input order, the vertices they name -- representatives all -- in input order, the rest dropped.  Duplicates are found by a stable radix
+ * sort of the key (lo, mid, hi), 21 bits each at most, with the face index as value.  Temporaries: keys_a, keys_b [sort_len] u64, vals_a, vals_b
+ * [sort_len] i32, sort_len >= F; hist [hist_words] i32, hist_words >= 512 * ceil(F / 2048); misc [misc_len] i32, misc_len >= 64.  PDHIP_E_ARG with
+ * the cause: a null pointer (named), Vn < 1, F < 1, Vn > 2^21 (both sizes named), F > 2^23, a short temporary (named); and from the device, out_faces
+ * and keep untouched (counts is cleared): faces with an index outside [0, Vn), or whose rep lies outside [0, Vn) (their number is named).
+ * SYNCHRONISES once, after the last launch (8 bytes).  Equal bytes on repeats. */
+int pdhip_weld_cells_axis(int Vn);
+int pdhip_weld_vertices(const float* vertices, int Vn, double tol, int32_t* rep, int32_t* counts, uint64_t* keys_a, uint64_t* keys_b, int32_t* vals_a,
+                        int32_t* vals_b, size_t sort_len, int32_t* hist, size_t hist_words, int32_t* cstart, size_t cstart_len, float* sorted_xyzi,
+                        size_t sorted_len, int32_t* parent, size_t parent_len, int32_t* misc, size_t misc_len, void* stream);
+int pdhip_clean_faces(const int64_t* faces, int F, const int32_t* rep, int Vn, int64_t* out_faces, uint8_t* keep, int32_t* counts, uint64_t* keys_a,
+                      uint64_t* keys_b, int32_t* vals_a, int32_t* vals_b, size_t sort_len, int32_t* hist, size_t hist_words, int32_t* misc,
+                      size_t misc_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

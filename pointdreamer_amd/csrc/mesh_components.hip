@@ -14,8 +14,10 @@
 //   k_mc_flatten   one thread per vertex: root[v], read-only on parent[]
 // No thread waits for another; every loop is bounded by a budget (2 Vn + 64 steps per face, Vn per vertex) that strictly decreasing walks
 // cannot use up (M_CAP says if one did).  Inside k_mc_union parent[] is shared between workgroups on different XCDs, so every access to it
-// there is an agent-scope atomic (relaxed: an ancestor is all a walk needs).  The other passes read it across a kernel boundary.
+// there is an agent-scope atomic (relaxed: an ancestor is all a walk needs).  The other passes read it across a kernel boundary.  find_root and
+// unite live in union_find.h, which mesh_clean.hip shares.
 #include "radix_sort.h"
+#include "union_find.h"
 
 namespace pdhip {
 namespace {
@@ -27,8 +29,6 @@ enum { M_ERR = 0, M_CAP, M_C, M_NREF, M_WORDS = 8 };
 constexpr int MISC_LINE = 256 / sizeof(int);                        // carve_compact: misc as one whole 256-byte line (M_WORDS of it used)
 enum { ERR_INDEX = 1, ERR_NONFINITE = 2 };
 
-__device__ __forceinline__ int ld_agent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ bool bad_index(int64_t a, int64_t b, int64_t c, int Vn) { return a < 0 || a >= Vn || b < 0 || b >= Vn || c < 0 || c >= Vn; }
 
 static void scan_flags(const int* in, int* out, int n, int* tsum, int* toff, hipStream_t s) {
@@ -67,34 +67,6 @@ __global__ void k_mc_compress(int* parent, int Vn, int* __restrict__ misc) {
         if (--steps < 0) { atomicOr(&misc[M_CAP], 4); return; }
     }
     parent[v] = r;
-}
-
-// representative of x; halves the path on the way (parent[prev] = its grandparent, an ancestor and < prev).  -1: the budget ran out
-__device__ __forceinline__ int find_root(int* parent, int x, long long& budget) {
-    int cur = ld_agent(parent + x);
-    if (cur == x) return x;
-    int prev = x, next = ld_agent(parent + cur);
-    while (next < cur) {
-        if (--budget < 0) return -1;
-        st_agent(parent + prev, next);
-        prev = cur; cur = next; next = ld_agent(parent + cur);
-    }
-    return cur;
-}
-
-// one component for the trees of ra and rb (representatives when they were found).  The CAS hooks a vertex that is its own parent below a
-// smaller vertex of the other tree (a root or not: either keeps parent[v] <= v); if it finds the vertex hooked already, the walk goes on
-// from the parent it read (< hi).  Returns the smaller representative, -1 when the budget ran out
-__device__ __forceinline__ int unite(int* parent, int ra, int rb, long long& budget) {
-    while (ra >= 0 && rb >= 0 && ra != rb) {
-        if (--budget < 0) return -1;
-        const int hi = ra > rb ? ra : rb, lo = ra > rb ? rb : ra;
-        int seen = hi;
-        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return lo;
-        ra = find_root(parent, seen, budget);
-        rb = lo;
-    }
-    return (ra < 0 || rb < 0) ? -1 : ra;
 }
 
 __global__ __launch_bounds__(TB) void k_mc_union(const int64_t* __restrict__ faces, int F, int Vn, int* parent, int* __restrict__ misc) {

@@ -69,6 +69,11 @@ COMPONENT_KEYS = ('spr_components', 'spr_min_component_share')
 # smooth the vertices of the reconstructed mesh, with spr_smooth_lambda (default 0.5) and spr_smooth_mu (default -0.53; 0: the plain Laplacian).
 # The cached geometry OBJ is the smoothed mesh; without spr_smooth nothing is smoothed
 SMOOTH_KEYS = ('spr_smooth', 'spr_smooth_lambda', 'spr_smooth_mu')
+# opt-in stage in front of everything a SUPPLIED `<pc>_untextured_mesh.obj` goes through (not the SPR mesh, which marching cubes welds): mesh_clean:
+# 'weld' merges its close vertices and drops degenerate faces, duplicate faces and unreferenced vertices (mesh_clean.py) after loading and before
+# the normalisation; mesh_weld_tolerance (default 0: exactly equal coordinates) is the welding distance as a share of the mesh's box diagonal, in
+# [0, 0.1], as MeshLab's percentage is.  The atlas cache of such a run is xatlas_<res>_weld.pth: it never shares one with a run without the key
+CLEAN_KEYS = ('mesh_clean', 'mesh_weld_tolerance')
 
 
 class Cfg(dict):
@@ -109,7 +114,7 @@ def load_config(cfg_file, overrides=None):
     cfg = Cfg(yaml.safe_load(open(cfg_file)))
     cfg.update(overrides or {})
     unknown = [k for k in cfg if k not in SUPPORTED_KEYS and k not in UPSTREAM_KEYS and k not in GEOMETRY_KEYS and k not in RENDER_KEYS
-               and k not in SUBSAMPLE_KEYS and k not in OUTLIER_KEYS and k not in COMPONENT_KEYS and k not in SMOOTH_KEYS]
+               and k not in SUBSAMPLE_KEYS and k not in OUTLIER_KEYS and k not in COMPONENT_KEYS and k not in SMOOTH_KEYS and k not in CLEAN_KEYS]
     if unknown:
         raise KeyError(f"{cfg_file}: unknown config keys {unknown}")
     if 'texture_gen_method' not in cfg:
@@ -162,6 +167,15 @@ def load_config(cfg_file, overrides=None):
         except ValueError as e:
             raise ValueError(f"spr_smooth={cfg.spr_smooth!r}, spr_smooth_lambda={cfg.get('spr_smooth_lambda')!r}, "
                              f"spr_smooth_mu={cfg.get('spr_smooth_mu')!r}: {e}") from None
+    if 'mesh_clean' in cfg and cfg.mesh_clean not in ('weld',):
+        raise ValueError(f"mesh_clean={cfg.mesh_clean!r}: the cleaning of a supplied mesh is 'weld' (merge close vertices, drop degenerate and "
+                         "duplicate faces and unreferenced vertices)")
+    if 'mesh_weld_tolerance' in cfg:
+        if 'mesh_clean' not in cfg:
+            raise ValueError("mesh_weld_tolerance steers the welding that mesh_clean: weld asks for: mesh_clean is missing")
+        t = cfg.mesh_weld_tolerance
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not 0.0 <= t <= 0.1:
+            raise ValueError(f"mesh_weld_tolerance={t!r}: the welding distance is a share of the mesh's box diagonal in [0, 0.1]")
     if cfg.optimize_from == 'None':                      # YAML `None` is the string 'None' (demo.py:213 treats both alike)
         cfg['optimize_from'] = None
     return cfg
@@ -281,6 +295,22 @@ def _smooth_rules(cfg):
                             mu=float(cfg.get('spr_smooth_mu', mesh_smooth.DEFAULT_MU))))
 
 
+def _clean_supplied(cfg, vertices, faces, ft, logger):
+    """The opt-in CLEAN_KEYS on a supplied mesh: (vertices, faces, ft) welded and cleaned; the `ft` rows (numpy, or None) follow the kept faces."""
+    from . import mesh_clean
+    box = (vertices.max(0)[0] - vertices.min(0)[0]).double()
+    tol = float(cfg.get('mesh_weld_tolerance', 0.0)) * float((box * box).sum().sqrt())
+    v, f, fidx, c = mesh_clean.clean_mesh(vertices, faces, tolerance=tol, return_face_index=True, return_counts=True)
+    rep = mesh_clean.mesh_report(v, f)
+    logger.info(f'mesh_clean: weld at tolerance {tol:.6g}: vertices {c["vertices_before"]} -> {c["vertices_after"]} ({c["merged"]} merged, '
+                f'{c["unreferenced"]} unreferenced), faces {c["faces_before"]} -> {c["faces_after"]} ({c["degenerate"]} degenerate, {c["duplicate"]} '
+                f'duplicate); after cleaning: {rep["boundary_edges"]} boundary edges, {rep["nonmanifold_pairs"]} non-manifold edges, '
+                f'{rep["components"]} components')
+    if ft is not None:
+        ft = np.ascontiguousarray(ft[fidx.cpu().numpy()])
+    return v, f, ft
+
+
 def _load_shape(cfg, pc_file, name, device, logger):
     """demo.py:359-452: cloud, mesh and atlas of one shape, normalised as the reference does."""
     out = os.path.join(cfg.output_path, name)
@@ -310,7 +340,8 @@ def _load_shape(cfg, pc_file, name, device, logger):
                     f'{cfg.get("subsample_colors", "point")}; {time.time() - start} s)')
     io_utils.save_colored_pc_ply(xyz.cpu().numpy(), rgb.cpu().numpy(), os.path.join(out, 'input_pc.ply'))
     geo_path = pc_file.replace('.ply', '_untextured_mesh.obj')
-    xatlas_file = os.path.join(out, 'geo', f'xatlas_{cfg.xatlas_texture_res}.pth')
+    weld = 'mesh_clean' in cfg and os.path.exists(geo_path)       # (the key touches a supplied mesh only)
+    xatlas_file = os.path.join(out, 'geo', f'xatlas_{cfg.xatlas_texture_res}{"_weld" if weld else ""}.pth')
     cached_geo = os.path.join(out, 'geo', f'{name}_untextured', 'models', 'model_normalized.obj')
     if not os.path.exists(geo_path) and not os.path.exists(cached_geo) and cfg.get('geo_from') == 'SPR':
         # baselines/spr.py:recon_one_shape_SPR on the normalised cloud (demo.py:411-416), on the device; the mesh goes to the
@@ -337,6 +368,8 @@ def _load_shape(cfg, pc_file, name, device, logger):
         v, f, vt, ft = io_utils.load_obj_mesh(geo_path if supplied else cached_geo, with_uv=True)
         vertices = torch.from_numpy(v).to(device)
         faces = torch.from_numpy(f).to(device)
+        if weld:
+            vertices, faces, ft = _clean_supplied(cfg, vertices, faces, ft if vt is not None else None, logger)
         if supplied:                                     # (the cached mesh was made from the normalised cloud: demo.py:401-406)
             vertices -= (vmax + vmin) / 2.
             vertices /= (vmax - vmin).max()
