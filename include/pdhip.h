@@ -911,6 +911,29 @@ int pdhip_clean_faces(const int64_t* faces, int F, const int32_t* rep, int Vn, i
                       uint64_t* keys_b, int32_t* vals_a, int32_t* vals_b, size_t sort_len, int32_t* hist, size_t hist_words, int32_t* misc,
                       size_t misc_len, void* stream);
 
+/* ---- test-only entries onto the shared device primitives (csrc/prims_debug.hip): the radix sort and the scans of csrc/radix_sort.h and the sort
+ * half of csrc/cell_list.h, which every geometry unit that sorts or scans includes.  The kernels have internal linkage, so these entries run
+ * prims_debug.hip's copy: the same source and the same flags as every consumer's.  Nothing the product calls (tests/test_gpu_prims.py).
+ * pdhip_debug_prims_workspace_bytes(n, nc): the bytes of ONE layout that all three entries carve: the two key and the two value buffers of n elements
+ * and the digit histograms of the sort, cstart [nc + 1] i32, and the tile sums / tile offsets of a tiled scan of n elements (8 bytes each).  0 for
+ * n < 1, n > 2^26, nc < 1 or nc > 2^26.
+ * pdhip_debug_radix_sort: keys (device [n] u64), vals (device [n] i32) -> keys_out, vals_out: radix_sort(bits) on copies of the inputs in the
+ * workspace.  The order is STABLE and by the key bits [0, 8 * ceil(bits / 8)): whole 8-bit digits; bits above that are carried along unread, and
+ * bits == 0 copies the inputs through.  0 <= bits <= 64.  ws: pdhip_debug_prims_workspace_bytes(n, 1) bytes.
+ * pdhip_debug_sort_by_cell: keys (device [n] u64, key[i] = the cell of point i, < 2^bits_for(nc); a key >= nc is a point outside every cell) ->
+ * keys_out [n] (the sorted keys), idx_out [n] i32 (the points' indices in that order: the stable argsort of keys), cstart_out [nc + 1] i32
+ * (cstart[c] = the first sorted position whose key is >= c), as sort_by_cell gives them to its consumers.  ws: pdhip_debug_prims_workspace_bytes(n, nc).
+ * pdhip_debug_scan: in -> out (device [n], elem_bytes 4 = int, 8 = uint64_t; the entry works on the caller's arrays themselves and writes out[0 .. n)
+ * only).  mode 0: the one-workgroup k_scan; 1: the tiled scan_exclusive / scan_inclusive.  inclusive != 0: out[i] = in[0] + ... + in[i], else
+ * ... + in[i - 1], sums modulo 2^32 / 2^64.  nc: the nc the workspace was sized with (cstart lies in front of the tile sums);
+ * ws: pdhip_debug_prims_workspace_bytes(n, nc).
+ * Every entry enqueues on `stream` and does not synchronise.  PDHIP_E_ARG with the cause, nothing launched: a null pointer (named), n < 1 or
+ * n > 2^26, nc outside [1, 2^26], bits outside [0, 64], elem_bytes other than 4 and 8, mode other than 0 and 1. */
+size_t pdhip_debug_prims_workspace_bytes(int n, int nc);
+int pdhip_debug_radix_sort(const uint64_t* keys, const int32_t* vals, int n, int bits, uint64_t* keys_out, int32_t* vals_out, void* ws, void* stream);
+int pdhip_debug_sort_by_cell(const uint64_t* keys, int n, int nc, uint64_t* keys_out, int32_t* idx_out, int32_t* cstart_out, void* ws, void* stream);
+int pdhip_debug_scan(const void* in, void* out, int n, int elem_bytes, int mode, int inclusive, int nc, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@
 // operation, its face bound and its refusal messages: their arithmetic differs and goldens pin it; and by cloud_metrics.hip, knn.hip, subsample.hip
 // and mesh_distance.hip, which share the f64 3-D grid of the last section: the grid, the key, the certificate's face bound, the (d2, index)
 // minimum and the staged scan of everything for the queries the certificate leaves.  Internal linkage: each including unit gets its own copy.
-// Zero scratch.
+// Zero scratch.  tests/test_gpu_prims.py holds the sort half (k_cell_keys, k_cell_starts, sort_by_cell) to exact references, through the copy in
+// prims_debug.hip.
 #pragma once
 #include "radix_sort.h"
 #include <string.h>

@@ -3,6 +3,7 @@
 // surface_recon.hip, cloud_metrics.hip and occupancy.hip; uv_atlas.hip: edge keys, packing order, UV entries; surface_recon.hip: vertex / triangle
 // offsets; neighbor_mesh.hip: edge and pair keys; simplify_mesh.hip: directed-edge keys, adjacency / winner / face offsets).  Written
 // here because rocPRIM's sort carries scratch on gfx950.  Every kernel has internal linkage: each including unit gets its own copy.
+// tests/test_gpu_prims.py holds the sort and the scans to exact references at the tile edges, through the copy in prims_debug.hip.
 #pragma once
 #include "common.h"
 
@@ -166,7 +167,9 @@ static int bits_for(unsigned long long maxkey) {
     return b;
 }
 
-// sorts keys / values k[0] / v[0] (n elements) by bits [0, bits); returns the index (0 / 1) of the buffer pair holding the result
+// sorts keys / values k[0] / v[0] (n > 0 elements), stably, by bits [0, 8 * ceil(bits / 8)): whole 8-bit digits, so the bits of a partial top
+// digit above `bits` take part in the order; callers keep their keys < 2^bits.  Bits above the last digit are carried along unread; bits == 0
+// sorts nothing.  Returns the index (0 / 1) of the buffer pair holding the result
 static int radix_sort(SortBufs& sb, int n, int bits, hipStream_t s) {
     const int nblk = cdiv(n, RS_TILE);
     int cur = 0;

@@ -476,6 +476,24 @@ def b_linear(pd, L, B, H, W, local=1, Cn=3):
     return run
 
 
+def b_prims(pd, L, n, nc):
+    """The shared primitives through their test entries (csrc/prims_debug.hip), one after the other on the one workspace: sort_by_cell (keys
+    over [0, nc], nc itself -- a point outside every cell -- included), then a tiled uint64_t inclusive scan, then a tiled int exclusive scan."""
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    rng = np.random.default_rng(n + nc)
+    keys = T(rng.integers(0, nc + 1 if nc > 1 else 1, n).astype(np.uint64).view(np.int64))
+    a64, a32 = T(rng.integers(0, 1 << 40, n, dtype=np.int64)), T(rng.integers(0, 4, n).astype(np.int32))
+
+    def run(ws):
+        ko, io, cs = full((n,), -77, torch.int64), full((n,), -77, torch.int32), full((nc + 1,), -77, torch.int32)
+        o64, o32 = full((n,), -77, torch.int64), full((n,), -77, torch.int32)
+        ok(L.pdhip_debug_sort_by_cell(P(keys), n, nc, P(ko), P(io), P(cs), P(ws), S()))
+        ok(L.pdhip_debug_scan(P(a64), P(o64), n, 8, 1, 1, nc, P(ws), S()))
+        ok(L.pdhip_debug_scan(P(a32), P(o32), n, 4, 1, 0, nc, P(ws), S()))
+        return [ko, io, cs, o64, o32]
+    return run
+
+
 # entry -> (size query, builder, {row: extra builder arguments}); the shapes are workspace_common.SHAPES[query][row name up to '+']
 ENTRIES = {
     'knn_points': ('pdhip_knn_points_workspace_bytes', b_knn, {'ragged': {}, 'tile': {}, 'min': {}, 'ragged+sweep': dict(hook=(0, 1)),
@@ -504,6 +522,7 @@ ENTRIES = {
     'raster_mesh_ws': ('pdhip_raster_mesh_ws_bytes', b_raster, {'ragged': {}, 'tile': {}, 'min': {}, 'ragged+atomic': dict(path=1),
                                                                'tile+atomic': dict(path=1)}),
     'nearest_fill': ('pdhip_nearest_fill_ws_ints', b_nearest_fill, {'ragged': {}, 'tile': {}, 'min': {}}),
+    'prims': ('pdhip_debug_prims_workspace_bytes', b_prims, {'ragged': {}, 'tile': {}, 'min': {}}),
     # the six existing cases (HPR: one level up to 4 * 1024 points, two levels above)
     'hpr_one_level': ('pdhip_hpr_ws_bytes', b_hpr, {'one_level': {}, 'tile': {}, 'min': {}}),
     'hpr_two_level': ('pdhip_hpr_ws_bytes', b_hpr, {'two_level': {}, 'ragged': {}, 'two_tiles': {}}),
@@ -583,9 +602,9 @@ def run_guarded(pd, entry, row, spoil=None):
     return len(cover), slack, nbytes
 
 
-def test_the_table_has_three_rows_for_each_of_the_28_entries():
+def test_the_table_has_three_rows_for_each_of_the_29_entries():
     """(no GPU needed)"""
-    assert len(ENTRIES) == 28 and all(len(rows) >= 3 for _, _, rows in ENTRIES.values())
+    assert len(ENTRIES) == 29 and all(len(rows) >= 3 for _, _, rows in ENTRIES.values())
     assert len({(q, wc.SHAPES[q][row.split('+')[0]], tuple(sorted(kw.items()))) for _, (q, _, rows) in ENTRIES.items() for row, kw in rows.items()}) \
         == len(ROWS)                                               # no row twice
     from pointdreamer_amd import _lib

@@ -40,9 +40,9 @@ def logged_query(name, args):
     return size * UNIT.get(name, 1), carved, triples
 
 
-def test_all_27_queries_have_shapes():
+def test_all_28_queries_have_shapes():
     q = queries()
-    assert len(q) == 27 and q == sorted(wc.SHAPES)
+    assert len(q) == 28 and q == sorted(wc.SHAPES)
     assert set(TABLE) <= set(q)
     for name in q:
         assert len(set(argument_sets(name))) >= 3, name

@@ -153,5 +153,6 @@ SHAPES = {
     'pdhip_optimize_color_ws_bytes': {'parent': (2, 32, 32), 'ragged': (3, 47, 45), 'tile': (2, 64, 32), 'min': (1, 8, 8)},
     'pdhip_sparse_views_ws_bytes': {'parent': (2, 500, 32), 'ragged': (3, 2113, 47), 'tile': (2, 2048, 64), 'min': (1, 1, 8)},
     'pdhip_linear_fill_ws_bytes': {'parent': (2, 40, 40), 'ragged': (3, 47, 45), 'tile': (2, 64, 32), 'min': (1, 1, 1)},
+    'pdhip_debug_prims_workspace_bytes': {'ragged': (2113, 300), 'tile': (2048, 256), 'min': (1, 1)},
     'pdhip_unet_head_ws_floats': {'ragged': (3, 24, 40, 64, 6), 'tile': (2, 64, 64, 32, 3), 'min': (1, 8, 8, 32, 3)},
 }
