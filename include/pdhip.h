@@ -927,12 +927,20 @@ int pdhip_clean_faces(const int64_t* faces, int F, const int32_t* rep, int Vn, i
  * only).  mode 0: the one-workgroup k_scan; 1: the tiled scan_exclusive / scan_inclusive.  inclusive != 0: out[i] = in[0] + ... + in[i], else
  * ... + in[i - 1], sums modulo 2^32 / 2^64.  nc: the nc the workspace was sized with (cstart lies in front of the tile sums);
  * ws: pdhip_debug_prims_workspace_bytes(n, nc).
- * Every entry enqueues on `stream` and does not synchronise.  PDHIP_E_ARG with the cause, nothing launched: a null pointer (named), n < 1 or
- * n > 2^26, nc outside [1, 2^26], bits outside [0, 64], elem_bytes other than 4 and 8, mode other than 0 and 1. */
+ * These three entries enqueue on `stream` and do not synchronise.  PDHIP_E_ARG with the cause, nothing launched: a null pointer (named), n < 1 or
+ * n > 2^26, nc outside [1, 2^26], bits outside [0, 64], elem_bytes other than 4 and 8, mode other than 0 and 1.
+ * pdhip_debug_union_pairs: the union-find of csrc/union_find.h, which mesh_components.hip, mesh_clean.hip and uv_atlas.hip share.  pairs (device
+ * [n_pairs, 2] i32, indices in [0, n); may be NULL with n_pairs == 0) -> parent (device [n] i32, the caller's: the forest, left as the unions
+ * made it), root (device [n] i32: the smallest index of the class of every vertex), status (device [1] i32: 0, or the OR of 1 = a union and
+ * 2 = a walk used up its budget of steps; root then holds -1 where a walk ended).  Three steps: k_uf_identity; one thread per pair,
+ * unite(find_root, find_root) with a budget of 2 n + 64 steps; one thread per vertex, walk_root with n steps.  1 <= n <= 2^26,
+ * 0 <= n_pairs <= 2^26; no workspace.  With n_pairs > 0 it SYNCHRONISES once before the unions (4 bytes: the pairs with an index outside
+ * [0, n) are counted on the device, and any is PDHIP_E_ARG before parent is touched). */
 size_t pdhip_debug_prims_workspace_bytes(int n, int nc);
 int pdhip_debug_radix_sort(const uint64_t* keys, const int32_t* vals, int n, int bits, uint64_t* keys_out, int32_t* vals_out, void* ws, void* stream);
 int pdhip_debug_sort_by_cell(const uint64_t* keys, int n, int nc, uint64_t* keys_out, int32_t* idx_out, int32_t* cstart_out, void* ws, void* stream);
 int pdhip_debug_scan(const void* in, void* out, int n, int elem_bytes, int mode, int inclusive, int nc, void* ws, void* stream);
+int pdhip_debug_union_pairs(const int32_t* pairs, int n_pairs, int n, int32_t* parent, int32_t* root, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

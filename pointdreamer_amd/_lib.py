@@ -89,6 +89,7 @@ _SIGS = {
     'pdhip_debug_radix_sort': (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp]),
     'pdhip_debug_sort_by_cell': (C.c_int, [vp, i32, i32, vp, vp, vp, vp, vp]),
     'pdhip_debug_scan': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+    'pdhip_debug_union_pairs': (C.c_int, [vp, i32, i32, vp, vp, vp, vp]),
     'pdhip_rescale_vertices':(C.c_int, [vp, i32, i32, vp, vp, vp, f64, vp]),
     'pdhip_optimize_color_ws_bytes': (sz, [i32, i32, i32]),
     'pdhip_optimize_color': (C.c_int, [vp, i32, vp, vp, i32, i32, vp, i32, vp, f64, i32, vp, vp, vp]),
@@ -210,6 +211,21 @@ def ptr(t, dtype=None, allow_none=False):
     if dtype is not None and t.dtype != dtype:
         raise PdhipError(f"expected dtype {dtype}, got {t.dtype}")
     return C.c_void_p(t.data_ptr())
+
+
+def ptr_or_null(t):
+    """ptr(t), or a null pointer for None and for an empty tensor (whose data pointer means nothing)."""
+    return ptr(t) if t is not None and t.numel() else C.c_void_p(0)
+
+
+def rows(x, what, label, cols, dtype):
+    """x, a GPU tensor of shape [n, cols], detached, cast to `dtype` and contiguous.  `what` names the caller and `label` the expected form
+    ('faces [F,3]') in the PdhipError raised otherwise."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise PdhipError(f"{what} needs tensors on the GPU (cuda:N == HIP device); there is no CPU path")
+    if x.dim() != 2 or x.shape[1] != cols:
+        raise PdhipError(f"{what}: expected {label}, got {tuple(x.shape)}")
+    return x.detach().to(dtype).contiguous()
 
 
 def as_u8(t):

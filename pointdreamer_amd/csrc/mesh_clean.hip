@@ -39,13 +39,13 @@
 // index.  k_mcf_out: out_faces, keep, counts.
 // Integer atomics only, no floating-point atomics, zero scratch; two calls give equal bytes.  Every temporary is a typed array of the caller's.
 #include "cell_list.h"
+#include "mesh_common.h"
 #include "union_find.h"
 
 namespace pdhip {
 namespace {
 
 constexpr int TB = 256;
-constexpr int MAX_V = 1 << 26, MAX_F = 1 << 23;                    // the limits of the neighbouring entries (pdhip_mesh_components)
 constexpr int MAX_V_FACES = 1 << 21;                               // pdhip_clean_faces: three indices of 21 bits in one key
 constexpr int CELLS_MAX = 256;
 constexpr int MISC_WORDS = 64;                                     // one 256-byte line
@@ -56,18 +56,7 @@ enum { C_DEGENERATE = 0, C_DUPLICATE, C_KEPT };
 static int cells_axis_for(int Vn) { return std::max(1, std::min(CELLS_MAX, (int)floor(sqrt((double)Vn / 8.0)))); }
 static size_t hist_len(size_t n) { return 2 * 256 * (size_t)cdiv((long long)n, RS_TILE); }
 
-// the active lanes of a wave add one each: one atomic per wave.  Every lane of the wave calls this
-__device__ __forceinline__ void wave_count(int32_t* p, bool pred, int lane) {
-    const unsigned long long m = __ballot(pred);
-    if (lane == 0 && m) atomicAdd(p, __popcll(m));
-}
-
 // ---- welding
-__global__ void k_mw_init(int* __restrict__ parent, int Vn) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v < Vn) parent[v] = v;
-}
-
 __global__ __launch_bounds__(TB) void k_mw_scan(const float4* __restrict__ sp, int Vn, const int* __restrict__ cstart, Grid3 g, double tol2, int* parent,
                                                 int* __restrict__ misc) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
@@ -111,11 +100,9 @@ __global__ __launch_bounds__(TB) void k_mw_flatten(const int* __restrict__ paren
     const int v = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
     bool root = false;
     if (v < Vn && !misc[W_CAP]) {
-        int r = v, steps = Vn;
-        for (int p = parent[r]; p < r; p = parent[r]) {
-            r = p;
-            if (--steps < 0) { atomicOr(&misc[W_CAP], 2); break; }
-        }
+        int steps = Vn;
+        int r = walk_root(parent, v, steps);
+        if (r < 0) { atomicOr(&misc[W_CAP], 2); r = v; }
         rep[v] = r;
         root = r == v;
     }
@@ -128,19 +115,17 @@ __global__ void k_mw_counts(const int* __restrict__ misc, int Vn, int C, int32_t
 }
 
 // ---- faces
-__device__ __forceinline__ bool outside(int64_t a, int Vn) { return a < 0 || a >= Vn; }
-
 __global__ __launch_bounds__(TB) void k_mcf_keys(const int64_t* __restrict__ faces, int F, int Vn, const int32_t* __restrict__ rep, int bits,
                                                  uint64_t* __restrict__ key, int* __restrict__ val, int* __restrict__ misc) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= F) return;
     const int64_t a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
     uint64_t k = 1ull << (3 * bits);                               // a degenerate face (and a refused one: nothing reads its key then)
-    if (outside(a, Vn) || outside(b, Vn) || outside(c, Vn)) {
+    if (!(index_ok(a, Vn) && index_ok(b, Vn) && index_ok(c, Vn))) {
         atomicAdd(&misc[F_BADIDX], 1);
     } else {
         const int ra = rep[a], rb = rep[b], rc = rep[c];
-        if (outside(ra, Vn) || outside(rb, Vn) || outside(rc, Vn)) {
+        if (!(index_ok(ra, Vn) && index_ok(rb, Vn) && index_ok(rc, Vn))) {
             atomicAdd(&misc[F_BADREP], 1);
         } else if (ra != rb && rb != rc && ra != rc) {
             const int lo = min(ra, min(rb, rc)), hi = max(ra, max(rb, rc)), mid = ra + rb + rc - lo - hi;
@@ -179,7 +164,7 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 using namespace pdhip;
 
-extern "C" int pdhip_weld_cells_axis(int Vn) { return Vn >= 1 && Vn <= MAX_V ? cells_axis_for(Vn) : 0; }
+extern "C" int pdhip_weld_cells_axis(int Vn) { return Vn >= 1 && Vn <= MESH_MAX_V ? cells_axis_for(Vn) : 0; }
 
 extern "C" int pdhip_weld_vertices(const float* vertices, int Vn, double tol, int32_t* rep, int32_t* counts, uint64_t* keys_a, uint64_t* keys_b,
                                    int32_t* vals_a, int32_t* vals_b, size_t sort_len, int32_t* hist, size_t hist_words, int32_t* cstart,
@@ -189,7 +174,7 @@ extern "C" int pdhip_weld_vertices(const float* vertices, int Vn, double tol, in
     WV_PTR(vertices); WV_PTR(rep); WV_PTR(counts); WV_PTR(keys_a); WV_PTR(keys_b); WV_PTR(vals_a); WV_PTR(vals_b); WV_PTR(hist); WV_PTR(cstart);
     WV_PTR(sorted_xyzi); WV_PTR(parent); WV_PTR(misc);
 #undef WV_PTR
-    PD_REQUIRE(Vn >= 1 && Vn <= MAX_V, "pdhip_weld_vertices: Vn=%d: at least one vertex, at most 2^26", Vn);
+    PD_REQUIRE(Vn >= 1 && Vn <= MESH_MAX_V, "pdhip_weld_vertices: Vn=%d: at least one vertex, at most 2^26", Vn);
     PD_REQUIRE(tol >= 0.0 && tol <= 1.7976931348623157e308, "pdhip_weld_vertices: tol=%g: a finite number >= 0", tol);
     const size_t nv = (size_t)Vn, cmax = (size_t)cells_axis_for(Vn);
 #define WV_LEN(have, need, name) PD_REQUIRE((have) >= (need), "pdhip_weld_vertices: " name " holds %zu elements, Vn=%d needs %zu", (size_t)(have), Vn, (size_t)(need))
@@ -207,7 +192,7 @@ extern "C" int pdhip_weld_vertices(const float* vertices, int Vn, double tol, in
     int rc = clear_boxes(words, 1, MISC_WORDS, s);
     if (rc) return rc;
     launch_point_box(vertices, Vn, words, s);
-    k_mw_init<<<cdiv(Vn, TB), TB, 0, s>>>(parent, Vn);
+    k_uf_identity<<<cdiv(Vn, TB), TB, 0, s>>>(parent, Vn);
     PD_LAUNCH_CHECK();
     HostBox box[1];
     rc = read_boxes(words, box, s);
@@ -233,8 +218,8 @@ extern "C" int pdhip_weld_vertices(const float* vertices, int Vn, double tol, in
     k_mw_counts<<<1, 1, 0, s>>>(misc, Vn, g.C, counts);
     PD_LAUNCH_CHECK();
     int h[MISC_WORDS];
-    PD_HIP(hipMemcpyAsync(h, misc, sizeof(h), hipMemcpyDeviceToHost, s));
-    PD_HIP(hipStreamSynchronize(s));
+    rc = read_words(misc, h, MISC_WORDS, s);
+    if (rc) return rc;
     if (h[W_CAP]) {
         set_error("pdhip_weld_vertices: a union-find walk used up its budget of steps (word %d): the forest is not the descending one the kernels "
                   "keep; rep and counts are not valid", h[W_CAP]);
@@ -253,7 +238,7 @@ extern "C" int pdhip_clean_faces(const int64_t* faces, int F, const int32_t* rep
     PD_REQUIRE(Vn >= 1 && F >= 1, "pdhip_clean_faces: Vn=%d F=%d: at least one vertex and one face", Vn, F);
     PD_REQUIRE(Vn <= MAX_V_FACES, "pdhip_clean_faces: Vn=%d exceeds 2^21 = %d: the three indices of a face share one 64-bit sort key, 21 bits each", Vn,
                MAX_V_FACES);
-    PD_REQUIRE(F <= MAX_F, "pdhip_clean_faces: F=%d exceeds the limit (F <= 2^23)", F);
+    PD_REQUIRE(F <= MESH_MAX_F, "pdhip_clean_faces: F=%d exceeds the limit (F <= 2^23)", F);
     const size_t nf = (size_t)F;
 #define CF_LEN(have, need, name) PD_REQUIRE((have) >= (need), "pdhip_clean_faces: " name " holds %zu elements, F=%d needs %zu", (size_t)(have), F, (size_t)(need))
     CF_LEN(sort_len, nf, "keys_a / keys_b / vals_a / vals_b");
@@ -271,8 +256,8 @@ extern "C" int pdhip_clean_faces(const int64_t* faces, int F, const int32_t* rep
     k_mcf_out<<<cdiv(F, TB), TB, 0, s>>>(faces, F, rep, bits, sb.k[cur], sb.v[cur], out_faces, keep, counts, misc);
     PD_LAUNCH_CHECK();
     int h[2];
-    PD_HIP(hipMemcpyAsync(h, misc, sizeof(h), hipMemcpyDeviceToHost, s));
-    PD_HIP(hipStreamSynchronize(s));
+    const int rc = read_words(misc, h, 2, s);
+    if (rc) return rc;
     PD_REQUIRE(h[F_BADIDX] == 0, "pdhip_clean_faces: %d face(s) with an index outside [0, Vn=%d)", h[F_BADIDX], Vn);
     PD_REQUIRE(h[F_BADREP] == 0, "pdhip_clean_faces: %d face(s) whose vertices' rep lies outside [0, Vn=%d): rep is not pdhip_weld_vertices' output "
                "for these vertices", h[F_BADREP], Vn);

@@ -2,34 +2,26 @@
 // contracts; DESIGN.md section 6, "Connected components").  No reference counterpart: the reference reconstructs by POCO and never meets
 // the floating pieces a Poisson solve leaves; MeshLab's "Remove isolated pieces" is the filter built on top (mesh_components.py).
 //
-// Components: a lock-free union-find over the vertices.  parent[v] <= v at every moment, and every value parent[v] ever holds is v or a
-// vertex connected to v, so the forest is acyclic whatever the threads' order, every walk goes to strictly smaller indices, and the one
-// root a component ends with is its smallest index -- the partition AND its labels are functions of the mesh alone.  Four launches:
+// Components: the lock-free union-find of union_find.h over the vertices (its header has the invariant: the partition AND its labels are
+// functions of the mesh alone).  Four launches:
 //   k_mc_hook      one thread per face: atomicMin(parent[v], smallest index of the face) for its vertices -- a first forest for free
-//   k_mc_compress  one thread per vertex: parent[v] = the root of that forest (plain loads and stores: whichever of the two values another
-//                  thread reads, it is an ancestor of v; the roots themselves are not written, so their hot lines stay in the caches)
+//   k_mc_compress  one thread per vertex: parent[v] = the root of that forest (walk_root; the roots themselves are not written, so their
+//                  hot lines stay in the caches)
 //   k_mc_union     one thread per face: nothing to do when its three vertices show one parent (nearly every face of a mesh numbered with
-//                  some locality); otherwise unite (a, b) and (b, c): find both representatives with path halving, atomicCAS the larger
-//                  one's parent from itself to the smaller one, on failure go on from the value the CAS read
+//                  some locality); otherwise unite (a, b) and (b, c)
 //   k_mc_flatten   one thread per vertex: root[v], read-only on parent[]
-// No thread waits for another; every loop is bounded by a budget (2 Vn + 64 steps per face, Vn per vertex) that strictly decreasing walks
-// cannot use up (M_CAP says if one did).  Inside k_mc_union parent[] is shared between workgroups on different XCDs, so every access to it
-// there is an agent-scope atomic (relaxed: an ancestor is all a walk needs).  The other passes read it across a kernel boundary.  find_root and
-// unite live in union_find.h, which mesh_clean.hip shares.
-#include "radix_sort.h"
+// The budgets are 2 Vn + 64 steps per face and Vn per vertex; M_CAP says if a walk used one up.
+#include "mesh_common.h"
 #include "union_find.h"
 
 namespace pdhip {
 namespace {
 
 constexpr int TB = 256;
-constexpr int MAX_V = 1 << 26, MAX_F = 1 << 23;                    // the limits of the neighbouring entries (pdhip_knn_points, pdhip_simplify_mesh)
 constexpr int SMALL_SCAN = 16384;                                  // up to here the one-workgroup scan of radix_sort.h: one launch, not three
 enum { M_ERR = 0, M_CAP, M_C, M_NREF, M_WORDS = 8 };
 constexpr int MISC_LINE = 256 / sizeof(int);                        // carve_compact: misc as one whole 256-byte line (M_WORDS of it used)
 enum { ERR_INDEX = 1, ERR_NONFINITE = 2 };
-
-__device__ __forceinline__ bool bad_index(int64_t a, int64_t b, int64_t c, int Vn) { return a < 0 || a >= Vn || b < 0 || b >= Vn || c < 0 || c >= Vn; }
 
 static void scan_flags(const int* in, int* out, int n, int* tsum, int* toff, hipStream_t s) {
     if (n <= SMALL_SCAN) k_scan<int><<<1, SC_T, 0, s>>>(in, out, n, 1);
@@ -49,7 +41,7 @@ __global__ void k_mc_hook(const int64_t* __restrict__ faces, int F, int Vn, int*
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= F) return;
     const int64_t a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-    if (bad_index(a, b, c, Vn)) { atomicOr(&misc[M_ERR], ERR_INDEX); return; }
+    if (!(index_ok(a, Vn) && index_ok(b, Vn) && index_ok(c, Vn))) { atomicOr(&misc[M_ERR], ERR_INDEX); return; }
     ref[a] = 1; ref[b] = 1; ref[c] = 1;
     const int m = (int)(a < b ? (a < c ? a : c) : (b < c ? b : c));
     if (a != m) atomicMin(&parent[a], m);
@@ -60,13 +52,10 @@ __global__ void k_mc_hook(const int64_t* __restrict__ faces, int F, int Vn, int*
 __global__ void k_mc_compress(int* parent, int Vn, int* __restrict__ misc) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= Vn || misc[M_ERR]) return;
-    int r = parent[v], steps = Vn;                                 // (a strictly decreasing walk has at most Vn - 1 steps)
-    if (r == v) return;
-    for (int p = parent[r]; p < r; p = parent[r]) {
-        r = p;
-        if (--steps < 0) { atomicOr(&misc[M_CAP], 4); return; }
-    }
-    parent[v] = r;
+    int steps = Vn;                                                // (a strictly decreasing walk has at most Vn - 1 steps)
+    const int r = walk_root(parent, v, steps);
+    if (r < 0) atomicOr(&misc[M_CAP], 4);
+    else if (r != v) parent[v] = r;
 }
 
 __global__ __launch_bounds__(TB) void k_mc_union(const int64_t* __restrict__ faces, int F, int Vn, int* parent, int* __restrict__ misc) {
@@ -90,14 +79,9 @@ __global__ void k_mc_flatten(const int* __restrict__ parent, const int* __restri
     if (v >= Vn) return;
     int r = v, steps = Vn;
     if (!(misc[M_ERR] & ERR_INDEX) && !misc[M_CAP]) {
-        for (int p = parent[r]; p < r; p = parent[r]) {
-            r = p;
-            if (--steps < 0) { atomicOr(&misc[M_CAP], 2); break; }
-        }
-        if (P && ref[v]) {
-            const float x = P[3 * (size_t)v], y = P[3 * (size_t)v + 1], z = P[3 * (size_t)v + 2];
-            if (!(fabsf(x) <= 3.402823466e38f && fabsf(y) <= 3.402823466e38f && fabsf(z) <= 3.402823466e38f)) atomicOr(&misc[M_ERR], ERR_NONFINITE);
-        }
+        r = walk_root(parent, v, steps);
+        if (r < 0) { atomicOr(&misc[M_CAP], 2); r = v; }
+        if (P && ref[v] && !finite3(P[3 * (size_t)v], P[3 * (size_t)v + 1], P[3 * (size_t)v + 2])) atomicOr(&misc[M_ERR], ERR_NONFINITE);
     }
     root[v] = r;
     isroot[v] = (ref[v] && r == v) ? 1 : 0;
@@ -233,7 +217,7 @@ __global__ void k_mc_pack_mark(const int64_t* __restrict__ faces, int F, int Vn,
     const int64_t a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
     const bool k = keep[f] != 0;
     fflag[f] = k ? 1 : 0;
-    if (bad_index(a, b, c, Vn)) { atomicOr(&misc[M_ERR], ERR_INDEX); return; }
+    if (!(index_ok(a, Vn) && index_ok(b, Vn) && index_ok(c, Vn))) { atomicOr(&misc[M_ERR], ERR_INDEX); return; }
     if (k) { vflag[a] = 1; vflag[b] = 1; vflag[c] = 1; }
 }
 
@@ -285,13 +269,7 @@ static size_t carve_compact(CompactWs& w, void* base, int Vn, int F) {
     return c.off + 256;
 }
 
-static bool sizes_ok(int Vn, int F) { return Vn >= 1 && F >= 0 && Vn <= MAX_V && F <= MAX_F; }
-
-static int read_misc(const int* misc, int* h, hipStream_t s) {
-    PD_HIP(hipMemcpyAsync(h, misc, M_WORDS * sizeof(int), hipMemcpyDeviceToHost, s));
-    PD_HIP(hipStreamSynchronize(s));
-    return PDHIP_OK;
-}
+static bool sizes_ok(int Vn, int F) { return Vn >= 1 && F >= 0 && Vn <= MESH_MAX_V && F <= MESH_MAX_F; }
 
 }  // namespace
 }  // namespace pdhip
@@ -312,7 +290,7 @@ extern "C" int pdhip_mesh_components(const int64_t* faces, int F, const float* v
 #undef MC_PTR
     PD_REQUIRE(!comp_box || vertices, "pdhip_mesh_components: null pointer (vertices): the boxes (comp_box) are taken over the vertices");
     PD_REQUIRE(Vn >= 1 && F >= 0, "pdhip_mesh_components: Vn=%d F=%d: at least one vertex, no negative face count", Vn, F);
-    PD_REQUIRE(Vn <= MAX_V && F <= MAX_F, "pdhip_mesh_components: Vn=%d F=%d exceed the limits (Vn <= 2^26, F <= 2^23)", Vn, F);
+    PD_REQUIRE(Vn <= MESH_MAX_V && F <= MESH_MAX_F, "pdhip_mesh_components: Vn=%d F=%d exceed the limits (Vn <= 2^26, F <= 2^23)", Vn, F);
     PD_REQUIRE(comp_capacity >= 0, "pdhip_mesh_components: comp_capacity=%d is negative", comp_capacity);
     hipStream_t s = as_stream(stream);
     if (F == 0) {                                                   // no face: no component, every vertex unreferenced
@@ -336,7 +314,7 @@ extern "C" int pdhip_mesh_components(const int64_t* faces, int F, const float* v
     k_mc_face_out<<<cdiv(decode > F ? decode : F, TB), TB, 0, s>>>(faces, F, Vn, w.root, w.cid, cap, face_comp, comp_faces, box, counts, w.misc);
     PD_LAUNCH_CHECK();
     int h[M_WORDS];
-    const int rc = read_misc(w.misc, h, s);
+    const int rc = read_words(w.misc, h, M_WORDS, s);
     if (rc != PDHIP_OK) return rc;
     PD_REQUIRE(!(h[M_ERR] & ERR_INDEX), "pdhip_mesh_components: a face index outside [0, Vn=%d)", Vn);
     PD_REQUIRE(!(h[M_ERR] & ERR_NONFINITE), "pdhip_mesh_components: a referenced vertex is not finite (the boxes need finite coordinates)");
@@ -362,7 +340,7 @@ extern "C" int pdhip_compact_mesh(const float* vertices, int Vn, const int64_t* 
 #undef CM_PTR
     PD_REQUIRE((colors != nullptr) == (out_colors != nullptr), "pdhip_compact_mesh: colors and out_colors go together");
     PD_REQUIRE(Vn >= 1 && F >= 0, "pdhip_compact_mesh: Vn=%d F=%d: at least one vertex, no negative face count", Vn, F);
-    PD_REQUIRE(Vn <= MAX_V && F <= MAX_F, "pdhip_compact_mesh: Vn=%d F=%d exceed the limits (Vn <= 2^26, F <= 2^23)", Vn, F);
+    PD_REQUIRE(Vn <= MESH_MAX_V && F <= MESH_MAX_F, "pdhip_compact_mesh: Vn=%d F=%d exceed the limits (Vn <= 2^26, F <= 2^23)", Vn, F);
     hipStream_t s = as_stream(stream);
     CompactWs w;
     carve_compact(w, ws, Vn, F);
@@ -377,7 +355,7 @@ extern "C" int pdhip_compact_mesh(const float* vertices, int Vn, const int64_t* 
     if (F > 0) k_mc_pack_faces<<<gf, TB, 0, s>>>(faces, F, w.fflag, w.fexcl, w.vexcl, out_faces, counts, w.misc);
     PD_LAUNCH_CHECK();
     int h[M_WORDS];
-    const int rc = read_misc(w.misc, h, s);
+    const int rc = read_words(w.misc, h, M_WORDS, s);
     if (rc != PDHIP_OK) return rc;
     PD_REQUIRE(!(h[M_ERR] & ERR_INDEX), "pdhip_compact_mesh: a face index outside [0, Vn=%d)", Vn);
     return PDHIP_OK;

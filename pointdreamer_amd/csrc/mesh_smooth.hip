@@ -13,27 +13,16 @@
 //   k_msm_pass    one thread per vertex, the row walked by a plain loop (a row of any length); writes nothing when the check word is set
 // Boundary: pair_faces[pos] = the faces on the ordered pair (row a, colidx[pos] = b), found by a binary search in the ascending row a
 // and an integer atomicAdd; a vertex is a boundary vertex when one of its pairs lies on exactly one face.  No sort, integer atomics only.
-#include "common.h"
+#include "mesh_common.h"
 
 namespace pdhip {
 namespace {
 
 constexpr int TB = 256;
-constexpr int MAX_V = 1 << 26, MAX_F = 1 << 23;                    // the limits of the neighbouring entries (pdhip_mesh_components)
 constexpr int MAX_STEPS = 10000;
 enum { C_MOVED = 0, C_HELD, C_ISOLATED, C_CHECK };                 // pdhip_smooth_mesh's counts
 enum { B_VERTICES = 0, B_EDGES, B_NONMANIFOLD, B_CHECK };          // pdhip_mesh_boundary_vertices' counts
 enum { ERR_ROWPTR = 1, ERR_COLIDX = 2, ERR_NONFINITE = 4, ERR_FACE = 8, ERR_PAIR = 16 };
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    return fabsf(x) <= 3.402823466e38f && fabsf(y) <= 3.402823466e38f && fabsf(z) <= 3.402823466e38f;
-}
-
-// the active lanes of a wave add one each: one atomic per wave.  Every lane of the wave calls this
-__device__ __forceinline__ void wave_count(int32_t* p, bool pred, int lane) {
-    const unsigned long long m = __ballot(pred);
-    if (lane == 0 && m) atomicAdd(p, __popcll(m));
-}
 
 // row v is [rowptr[v], rowptr[v + 1]) inside [0, nnz = rowptr[Vn]): false sets nothing -- the caller flags it.  Only a row that passes is
 // walked, so no index outside colidx[0, nnz) is ever formed
@@ -52,7 +41,7 @@ __global__ __launch_bounds__(TB) void k_msm_check(const float* __restrict__ P, i
         if (!row_ok(rowptr, v, rowptr[Vn], r0, r1)) { err = ERR_ROWPTR; r1 = r0; }
         for (int k = r0; k < r1; ++k) {
             const int j = colidx[k];
-            if (j < 0 || j >= Vn) err |= ERR_COLIDX;
+            if (!index_ok(j, Vn)) err |= ERR_COLIDX;
         }
         if (r1 > r0 && !finite3(P[3 * (size_t)v], P[3 * (size_t)v + 1], P[3 * (size_t)v + 2])) err |= ERR_NONFINITE;
     }
@@ -124,7 +113,7 @@ __global__ __launch_bounds__(TB) void k_msm_pair_count(const int64_t* __restrict
     if (i >= 6ll * F) return;
     const int f = (int)(i / 6), p = (int)(i % 6), e = p >> 1;
     int64_t a = faces[3 * (size_t)f + e], b = faces[3 * (size_t)f + (e + 1) % 3];
-    if (a < 0 || a >= Vn || b < 0 || b >= Vn) { atomicOr(&counts[B_CHECK], ERR_FACE); return; }
+    if (!(index_ok(a, Vn) && index_ok(b, Vn))) { atomicOr(&counts[B_CHECK], ERR_FACE); return; }
     if (a == b) return;
     if (p & 1) { const int64_t t = a; a = b; b = t; }
     int lo = rowptr[a], hi = rowptr[a + 1];                        // (a monotone rowptr inside [0, nnz]: k_msm_pair_zero)
@@ -174,7 +163,7 @@ extern "C" int pdhip_mesh_boundary_vertices(const int64_t* faces, int F, int Vn,
     MB_PTR(faces); MB_PTR(rowptr); MB_PTR(colidx); MB_PTR(pair_faces); MB_PTR(boundary); MB_PTR(counts);
 #undef MB_PTR
     PD_REQUIRE(Vn >= 1 && F >= 1, "pdhip_mesh_boundary_vertices: Vn=%d F=%d: at least one vertex and one face", Vn, F);
-    PD_REQUIRE(Vn <= MAX_V && F <= MAX_F, "pdhip_mesh_boundary_vertices: Vn=%d F=%d exceed the limits (Vn <= 2^26, F <= 2^23)", Vn, F);
+    PD_REQUIRE(Vn <= MESH_MAX_V && F <= MESH_MAX_F, "pdhip_mesh_boundary_vertices: Vn=%d F=%d exceed the limits (Vn <= 2^26, F <= 2^23)", Vn, F);
     hipStream_t s = as_stream(stream);
     const long long pairs = 6ll * F;
     PD_HIP(hipMemsetAsync(counts, 0, 4 * sizeof(int32_t), s));
@@ -183,8 +172,8 @@ extern "C" int pdhip_mesh_boundary_vertices(const int64_t* faces, int F, int Vn,
     k_msm_boundary<<<cdiv(Vn, TB), TB, 0, s>>>(Vn, rowptr, colidx, pair_faces, boundary, counts);
     PD_LAUNCH_CHECK();
     int32_t h[4];
-    PD_HIP(hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, s));
-    PD_HIP(hipStreamSynchronize(s));
+    const int rc = read_words(counts, h, 4, s);
+    if (rc) return rc;
     PD_REQUIRE(!(h[B_CHECK] & ERR_ROWPTR), "pdhip_mesh_boundary_vertices: rowptr is not a CSR of these faces (rowptr[0] == 0, ascending, "
                "rowptr[Vn=%d] <= 6 F)", Vn);
     PD_REQUIRE(!(h[B_CHECK] & ERR_FACE), "pdhip_mesh_boundary_vertices: a face index outside [0, Vn=%d)", Vn);
@@ -198,7 +187,7 @@ extern "C" int pdhip_smooth_mesh(const float* vertices, int Vn, const int32_t* r
 #define SM_PTR(p) PD_REQUIRE(p, "pdhip_smooth_mesh: null pointer (" #p ")")
     SM_PTR(vertices); SM_PTR(rowptr); SM_PTR(colidx); SM_PTR(state_a); SM_PTR(state_b); SM_PTR(out_vertices); SM_PTR(counts);
 #undef SM_PTR
-    PD_REQUIRE(Vn >= 1 && Vn <= MAX_V, "pdhip_smooth_mesh: Vn=%d: at least one vertex, at most 2^26", Vn);
+    PD_REQUIRE(Vn >= 1 && Vn <= MESH_MAX_V, "pdhip_smooth_mesh: Vn=%d: at least one vertex, at most 2^26", Vn);
     PD_REQUIRE(steps >= 1 && steps <= MAX_STEPS, "pdhip_smooth_mesh: steps=%d: 1 .. %d", steps, MAX_STEPS);
     PD_REQUIRE(lambda > 0.0 && lambda <= 1.0, "pdhip_smooth_mesh: lambda=%g is not in (0, 1]", lambda);
     PD_REQUIRE(mu <= 0.0 && mu >= -1.7976931348623157e308, "pdhip_smooth_mesh: mu=%g: a finite number <= 0 (0: the plain Laplacian)", mu);
@@ -226,8 +215,8 @@ extern "C" int pdhip_smooth_mesh(const float* vertices, int Vn, const int32_t* r
     }
     PD_LAUNCH_CHECK();
     int32_t h[4];
-    PD_HIP(hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, s));
-    PD_HIP(hipStreamSynchronize(s));
+    const int rc = read_words(counts, h, 4, s);
+    if (rc) return rc;
     PD_REQUIRE(!(h[C_CHECK] & ERR_ROWPTR), "pdhip_smooth_mesh: rowptr is not monotone from rowptr[0] == 0 to rowptr[Vn=%d]; nothing was written", Vn);
     PD_REQUIRE(!(h[C_CHECK] & ERR_COLIDX), "pdhip_smooth_mesh: a colidx outside [0, Vn=%d); nothing was written", Vn);
     PD_REQUIRE(!(h[C_CHECK] & ERR_NONFINITE), "pdhip_smooth_mesh: a vertex with neighbours is not finite; nothing was written");

@@ -3,7 +3,7 @@
 //   pdhip_subdivide_with_uv    one round of midpoint subdivision of the picked faces, positions and UVs
 //     k_nm_pick / k_nm_fill      picked-face flags from the index list (duplicates collapse), or all faces
 //     k_nm_edge_keys             one key (larger endpoint, smaller endpoint) per corner of a picked face, in picked-face order
-//     k_nm_unique_flags          first entry of every run of equal sorted keys  -> scan -> id of the run's midpoint
+//     k_run_heads                first entry of every run of equal sorted keys  -> scan -> id of the run's midpoint
 //     k_nm_midpoints             midpoint id per corner; the first entry of a run writes (x[lo] + x[hi]) / 2
 //     k_nm_children              untouched faces first, then (v0 m01 m20) (m01 v1 m12) (m20 m12 v2) (m01 m12 m20) per picked face
 //   pdhip_vertex_uv_table      k_nm_best_uv (atomicMax of the UV index per vertex) / k_nm_uv_gather
@@ -12,7 +12,7 @@
 // Ordering comes from the stable radix sort and the scans of radix_sort.h only; the atomics used (max of an index, add of a count) are
 // order-independent, so two runs give equal bytes.  All sizes are int32 and checked on entry.  Each entry reads its counts and error
 // flags back ONCE, at its end (one stream synchronisation), and hands the same read to the caller through counts_host.
-#include "radix_sort.h"
+#include "mesh_common.h"
 using namespace pdhip;
 
 namespace {
@@ -20,7 +20,8 @@ namespace {
 constexpr int TB = 256;
 constexpr int ERR_PICK = 1, ERR_FACE = 2, ERR_TEX = 4;
 // misc words
-constexpr int M_ERR = 0, M_C0 = 1, M_WORDS = 8;                    // M_C0 .. M_C0 + 3: the counts as the host reads them
+constexpr int M_ERR = 0, M_C0 = 1, M_LIVE = 5, M_WORDS = 8;        // M_C0 .. M_C0 + 3: the counts as the host reads them; M_LIVE: the 3 T edge keys
+constexpr int M_READ = 5;                                          // the one read of an entry: misc[0 .. 4] = error flags + counts
 
 // ---- subdivision -------------------------------------------------------------------------------------------------------------
 __global__ void k_nm_fill(int* __restrict__ p, int n, int value) {
@@ -32,18 +33,19 @@ __global__ void k_nm_pick(const int64_t* __restrict__ face_index, int K, int F, 
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= K) return;
     const int64_t f = face_index[k];
-    if (f < 0 || f >= F) atomicOr(&misc[M_ERR], ERR_PICK);
+    if (!index_ok(f, F)) atomicOr(&misc[M_ERR], ERR_PICK);
     else pick[f] = 1;
 }
 
-// thread i < F: the three edge keys of face i if it is picked (slot 3 * rank + corner); thread i in [3T, N): padding that sorts last
+// thread i < F: the three edge keys of face i if it is picked (slot 3 * rank + corner); thread i in [3T, N): padding that sorts last;
+// thread 0 leaves 3 T, the number of keys that are edges, in misc[M_LIVE] for k_run_heads
 __global__ void k_nm_edge_keys(const int64_t* __restrict__ tri, int F, int n_index, int err_bit, const int* __restrict__ pinc, int N,
                                uint64_t* __restrict__ keys, int* __restrict__ vals, int* __restrict__ misc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int T = pinc[F - 1];
-    const uint64_t nv = (uint64_t)n_index;
+    if (i == 0) misc[M_LIVE] = 3 * T;
     if (i < N && i >= 3 * T) {
-        keys[i] = nv * nv - 1ull;
+        keys[i] = pair_key(n_index - 1, n_index - 1, n_index);
         vals[i] = i;
     }
     if (i >= F) return;
@@ -54,22 +56,15 @@ __global__ void k_nm_edge_keys(const int64_t* __restrict__ tri, int F, int n_ind
     bool bad = false;
 #pragma unroll
     for (int c = 0; c < 3; ++c)
-        if (a[c] < 0 || a[c] >= n_index) { bad = true; a[c] = 0; }
+        if (!index_ok(a[c], n_index)) { bad = true; a[c] = 0; }
     if (bad) atomicOr(&misc[M_ERR], err_bit);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const uint64_t p = (uint64_t)a[c], q = (uint64_t)a[c == 2 ? 0 : c + 1];
         const uint64_t lo = p < q ? p : q, hi = p < q ? q : p;
-        keys[3 * r + c] = hi * nv + lo;
+        keys[3 * r + c] = pair_key(hi, lo, n_index);
         vals[3 * r + c] = 3 * r + c;
     }
-}
-
-__global__ void k_nm_unique_flags(const uint64_t* __restrict__ keys, int N, const int* __restrict__ pinc, int F, int* __restrict__ flag) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    const int n = 3 * pinc[F - 1];
-    flag[i] = (i < n && (i == 0 || keys[i] != keys[i - 1])) ? 1 : 0;
 }
 
 template <int C>
@@ -82,7 +77,7 @@ __global__ void k_nm_midpoints(const uint64_t* __restrict__ keys, const int* __r
     mid[vals[i]] = id;
     if (!flag[i]) return;
     const uint64_t key = keys[i];
-    const size_t hi = (size_t)(key / (uint64_t)n_index), lo = (size_t)(key % (uint64_t)n_index);
+    const size_t hi = (size_t)pair_first(key, n_index), lo = (size_t)pair_second(key, n_index);
 #pragma unroll
     for (int c = 0; c < C; ++c) out[(size_t)id * C + c] = (x[lo * C + c] + x[hi * C + c]) / 2.0f;
 }
@@ -154,7 +149,7 @@ static int midpoints(SubWs& w, const int64_t* tri, int F, int n_index, int err_b
     const int g = cdiv(F > N ? F : N, TB), gN = cdiv(N, TB);
     k_nm_edge_keys<<<g, TB, 0, s>>>(tri, F, n_index, err_bit, w.pinc, N, w.sb.k[0], w.sb.v[0], w.misc);
     const int cur = radix_sort(w.sb, N, bits_for((unsigned long long)n_index * (unsigned long long)n_index - 1ull), s);
-    k_nm_unique_flags<<<gN, TB, 0, s>>>(w.sb.k[cur], N, w.pinc, F, w.flag);
+    k_run_heads<uint64_t><<<gN, TB, 0, s>>>(w.sb.k[cur], N, w.misc + M_LIVE, ~0ull, w.flag);
     k_scan<<<1, SC_T, 0, s>>>(w.flag, w.incl, N, 0);
     k_nm_midpoints<C><<<gN, TB, 0, s>>>(w.sb.k[cur], w.sb.v[cur], w.flag, w.incl, N, w.pinc, F, n_index, x, out, mid);
     k_nm_keep<<<1, 1, 0, s>>>(w.incl, N, keep);
@@ -168,7 +163,7 @@ __global__ void k_nm_best_uv(const int64_t* __restrict__ faces, const int64_t* _
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int64_t v = faces[i], t = fuv[i];
-    if (v < 0 || v >= V || t < 0 || t >= U) atomicAdd(skipped, 1);
+    if (!(index_ok(v, V) && index_ok(t, U))) atomicAdd(skipped, 1);
     else atomicMax(&best[v], (int)t);
 }
 
@@ -190,19 +185,11 @@ __global__ void k_nm_pair_keys(const int64_t* __restrict__ faces, int F, int V, 
     const int f = i / 6, p = i - 6 * f, c = p < 3 ? p : p - 3;
     int64_t a = faces[3 * (size_t)f + c], b = faces[3 * (size_t)f + (c == 2 ? 0 : c + 1)];
     if (p >= 3) { const int64_t t = a; a = b; b = t; }
-    const uint64_t nv = (uint64_t)V;
-    uint64_t key = nv * nv - 1ull;
-    if (a < 0 || a >= V || b < 0 || b >= V) atomicOr(&misc[M_ERR], ERR_FACE);
-    else if (a != b) key = (uint64_t)a * nv + (uint64_t)b;
+    uint64_t key = pair_key(V - 1, V - 1, V);
+    if (!(index_ok(a, V) && index_ok(b, V))) atomicOr(&misc[M_ERR], ERR_FACE);
+    else if (a != b) key = pair_key(a, b, V);
     keys[i] = key;
     vals[i] = i;
-}
-
-__global__ void k_nm_pair_flags(const uint64_t* __restrict__ keys, int N, int V, int* __restrict__ flag) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    const uint64_t none = (uint64_t)V * (uint64_t)V - 1ull;
-    flag[i] = (keys[i] != none && (i == 0 || keys[i] != keys[i - 1])) ? 1 : 0;
 }
 
 __global__ void k_nm_csr_write(const uint64_t* __restrict__ keys, const int* __restrict__ flag, const int* __restrict__ incl, int N, int V,
@@ -210,8 +197,8 @@ __global__ void k_nm_csr_write(const uint64_t* __restrict__ keys, const int* __r
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N || !flag[i]) return;
     const uint64_t key = keys[i];
-    const int row = (int)(key / (uint64_t)V);
-    colidx[incl[i] - 1] = (int32_t)(key % (uint64_t)V);
+    const int row = (int)pair_first(key, V);
+    colidx[incl[i] - 1] = (int32_t)pair_second(key, V);
     atomicAdd(&deg[row + 1], 1);
 }
 
@@ -243,13 +230,6 @@ __global__ void k_nm_zero_flags(const float* __restrict__ count, int V, int* __r
 __global__ void k_nm_compact(const int* __restrict__ flag, const int* __restrict__ incl, int V, int32_t* __restrict__ out) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v < V && flag[v]) out[incl[v] - 1] = v;
-}
-
-// the one read of an entry: misc[0 .. 4] = error flags + counts
-static int read_misc(const int* misc, int* h, hipStream_t s) {
-    PD_HIP(hipMemcpyAsync(h, misc, 5 * sizeof(int), hipMemcpyDeviceToHost, s));
-    PD_HIP(hipStreamSynchronize(s));
-    return PDHIP_OK;
 }
 
 }  // namespace
@@ -295,8 +275,8 @@ extern "C" int pdhip_subdivide_with_uv(const float* vertices, int V, const int64
     k_nm_children<<<gF, TB, 0, s>>>(faces, face_uv_idx, F, w.pinc, w.mid, w.mid_uv, out_faces, out_face_uv_idx);
     k_nm_sub_counts<<<1, 1, 0, s>>>(V, U, F, w.pinc, w.misc, counts);
     PD_LAUNCH_CHECK();
-    int h[5];
-    const int rc = read_misc(w.misc, h, s);
+    int h[M_READ];
+    const int rc = read_words(w.misc, h, M_READ, s);
     if (rc != PDHIP_OK) return rc;
     PD_REQUIRE(!(h[M_ERR] & ERR_PICK), "pdhip_subdivide_with_uv: a face_index entry lies outside [0, F=%d)", F);
     PD_REQUIRE(!(h[M_ERR] & ERR_FACE), "pdhip_subdivide_with_uv: a picked face has a vertex index outside [0, V=%d)", V);
@@ -346,14 +326,14 @@ extern "C" int pdhip_neighbour_csr(int V, const int64_t* faces, int F, int32_t* 
     PD_HIP(hipMemsetAsync(w.deg, 0, ((size_t)V + 1) * sizeof(int), s));
     k_nm_pair_keys<<<gN, TB, 0, s>>>(faces, F, V, w.sb.k[0], w.sb.v[0], w.misc);
     const int cur = radix_sort(w.sb, N, bits_for((unsigned long long)V * (unsigned long long)V - 1ull), s);
-    k_nm_pair_flags<<<gN, TB, 0, s>>>(w.sb.k[cur], N, V, w.flag);
+    k_run_heads<uint64_t><<<gN, TB, 0, s>>>(w.sb.k[cur], N, nullptr, (uint64_t)V * (uint64_t)V - 1ull, w.flag);
     k_scan<<<1, SC_T, 0, s>>>(w.flag, w.incl, N, 0);
     k_nm_csr_write<<<gN, TB, 0, s>>>(w.sb.k[cur], w.flag, w.incl, N, V, w.deg, colidx);
     k_scan<<<1, SC_T, 0, s>>>(w.deg, rowptr, V + 1, 0);
     k_nm_one_count<<<1, 1, 0, s>>>(w.incl, N, w.misc, counts);
     PD_LAUNCH_CHECK();
-    int h[5];
-    const int rc = read_misc(w.misc, h, s);
+    int h[M_READ];
+    const int rc = read_words(w.misc, h, M_READ, s);
     if (rc != PDHIP_OK) return rc;
     PD_REQUIRE(!(h[M_ERR] & ERR_FACE), "pdhip_neighbour_csr: a face has a vertex index outside [0, V=%d)", V);
     if (counts_host) counts_host[0] = h[M_C0];
@@ -383,8 +363,8 @@ extern "C" int pdhip_compact_zero_count(const float* count, int V, int32_t* inva
     k_nm_compact<<<g, TB, 0, s>>>(flag, incl, V, invalid);
     k_nm_one_count<<<1, 1, 0, s>>>(incl, V, misc, counts);
     PD_LAUNCH_CHECK();
-    int h[5];
-    const int rc = read_misc(misc, h, s);
+    int h[M_READ];
+    const int rc = read_words(misc, h, M_READ, s);
     if (rc != PDHIP_OK) return rc;
     if (counts_host) counts_host[0] = h[M_C0];
     return PDHIP_OK;

@@ -1,17 +1,45 @@
-// Test-only entries onto the shared device primitives: the radix sort, the one-workgroup scan and the tiled scans of radix_sort.h, and the sort
-// half of cell_list.h (k_cell_keys, k_cell_starts, sort_by_cell).  include/pdhip.h has the contracts; tests/test_gpu_prims.py holds each of them
-// to an exact numpy reference at the tile edges, tests/test_prims_cpu.py the references, the size query and the refusals.  Nothing the product
-// calls.
+// Test-only entries onto the shared device primitives: the radix sort, the one-workgroup scan and the tiled scans of radix_sort.h, the sort
+// half of cell_list.h (k_cell_keys, k_cell_starts, sort_by_cell), and the union-find of union_find.h.  include/pdhip.h has the contracts;
+// tests/test_gpu_prims.py holds each of them to an exact numpy reference at the tile edges, tests/test_prims_cpu.py the references, the size
+// query and the refusals.  Nothing the product calls.
 //
-// Every kernel of the two headers has internal linkage, so each including unit carries a copy of its own, and no test can run the copy inside
+// Every kernel of the headers has internal linkage, so each including unit carries a copy of its own, and no test can run the copy inside
 // uv_atlas.hip or knn.hip.  What the tests run is THIS unit's copy: compiled from the same source with the same flags (GEO_SRC of the Makefile)
-// as every consumer's.  The unit adds no kernel of its own except the key functor below, which k_cell_keys instantiates.
+// as every consumer's.  The unit's own kernels are the key functor below, which k_cell_keys instantiates, and the three of the union-find
+// entry, which only call the header's device functions the way the product's kernels do.
 #include "cell_list.h"
+#include "mesh_common.h"
+#include "union_find.h"
 
 namespace pdhip {
 namespace {
 
 constexpr int MAX_N = 1 << 26, MAX_NC = 1 << 26;                   // the limits of the neighbouring entries (pdhip_knn_points)
+constexpr int UF_T = 256;
+enum { UF_UNITE = 1, UF_WALK = 2 };                                // pdhip_debug_union_pairs' status: which budget ran out
+
+__global__ void k_ufd_check(const int32_t* __restrict__ pairs, int n_pairs, int n, int32_t* __restrict__ bad) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n_pairs && !(index_ok(pairs[2 * (size_t)p], n) && index_ok(pairs[2 * (size_t)p + 1], n))) atomicAdd(bad, 1);
+}
+
+// one thread per pair, the budget mesh_components.hip gives a face
+__global__ __launch_bounds__(UF_T) void k_ufd_unite(const int32_t* __restrict__ pairs, int n_pairs, int n, int* parent, int32_t* __restrict__ status) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs) return;
+    long long budget = 2ll * n + 64;
+    const int a = pairs[2 * (size_t)p], b = pairs[2 * (size_t)p + 1];
+    if (unite(parent, find_root(parent, a, budget), find_root(parent, b, budget), budget) < 0) atomicOr(status, UF_UNITE);
+}
+
+__global__ void k_ufd_roots(const int* __restrict__ parent, int n, int32_t* __restrict__ root, int32_t* __restrict__ status) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    int steps = n;
+    const int r = walk_root(parent, v, steps);
+    if (r < 0) atomicOr(status, UF_WALK);
+    root[v] = r;
+}
 
 // KeyFn of sort_by_cell: the key of point i, read from an array
 struct ArrayKey {
@@ -103,6 +131,31 @@ extern "C" int pdhip_debug_scan(const void* in, void* out, int n, int elem_bytes
     carve_prims(w, ws, n, nc);
     if (elem_bytes == 4) launch_scan<int>(in, out, n, mode, inclusive, w, s);
     else launch_scan<uint64_t>(in, out, n, mode, inclusive, w, s);
+    PD_LAUNCH_CHECK();
+    return PDHIP_OK;
+}
+
+extern "C" int pdhip_debug_union_pairs(const int32_t* pairs, int n_pairs, int n, int32_t* parent, int32_t* root, int32_t* status, void* stream) {
+#define PR_PTR(p) PD_REQUIRE(p, "pdhip_debug_union_pairs: null pointer (" #p ")")
+    PR_PTR(parent); PR_PTR(root); PR_PTR(status);
+#undef PR_PTR
+    PD_REQUIRE(n >= 1 && n <= MAX_N, "pdhip_debug_union_pairs: n=%d outside [1, 2^26]", n);
+    PD_REQUIRE(n_pairs >= 0 && n_pairs <= MAX_N, "pdhip_debug_union_pairs: n_pairs=%d outside [0, 2^26]", n_pairs);
+    PD_REQUIRE(pairs || n_pairs == 0, "pdhip_debug_union_pairs: null pointer (pairs) with n_pairs=%d", n_pairs);
+    hipStream_t s = as_stream(stream);
+    const int gp = cdiv(n_pairs, UF_T), gn = cdiv(n, UF_T);
+    PD_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    if (n_pairs > 0) {                                              // no index outside [0, n) reaches parent[]: counted before the unions start
+        k_ufd_check<<<gp, UF_T, 0, s>>>(pairs, n_pairs, n, status);
+        PD_LAUNCH_CHECK();
+        int bad = 0;
+        const int rc = read_words(status, &bad, 1, s);
+        if (rc) return rc;
+        PD_REQUIRE(bad == 0, "pdhip_debug_union_pairs: %d pair(s) with an index outside [0, n=%d)", bad, n);
+    }
+    k_uf_identity<<<gn, UF_T, 0, s>>>(parent, n);
+    if (n_pairs > 0) k_ufd_unite<<<gp, UF_T, 0, s>>>(pairs, n_pairs, n, parent, status);
+    k_ufd_roots<<<gn, UF_T, 0, s>>>(parent, n, root, status);
     PD_LAUNCH_CHECK();
     return PDHIP_OK;
 }

@@ -1,7 +1,9 @@
 // Radix sort (LSD, 8-bit digits, stable) of 64-bit keys with int32 values, a one-workgroup scan and a tiled scan over many
-// workgroups (both templated on the element type): shared by the geometry units that sort or scan on the device (cell_list.h: the cell keys of
-// surface_recon.hip, cloud_metrics.hip and occupancy.hip; uv_atlas.hip: edge keys, packing order, UV entries; surface_recon.hip: vertex / triangle
-// offsets; neighbor_mesh.hip: edge and pair keys; simplify_mesh.hip: directed-edge keys, adjacency / winner / face offsets).  Written
+// workgroups (both templated on the element type): shared by the geometry units that sort or scan on the device.  Through cell_list.h: the
+// cell keys of surface_recon.hip (and its vertex / triangle offsets), cloud_metrics.hip, occupancy.hip, mesh_distance.hip, subsample.hip,
+// knn.hip and mesh_clean.hip (and its face triples).  Through mesh_common.h: uv_atlas.hip (edge keys, packing order, UV entries),
+// neighbor_mesh.hip (edge and pair keys), simplify_mesh.hip (directed-edge keys, adjacency / winner / face offsets), mesh_components.hip (root
+// and compaction offsets); mesh_smooth.hip includes it that way and launches none of it.  Directly: sample_mesh.hip (the uint64 CDF).  Written
 // here because rocPRIM's sort carries scratch on gfx950.  Every kernel has internal linkage: each including unit gets its own copy.
 // tests/test_gpu_prims.py holds the sort and the scans to exact references at the tile edges, through the copy in prims_debug.hip.
 #pragma once

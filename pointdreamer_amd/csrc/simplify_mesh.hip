@@ -14,18 +14,18 @@
 // Quadrics, costs and positions are f64 (positions are rounded to f32 BEFORE cost and validity, so what is judged is what is stored).
 // Nothing depends on the order the CSR rows were filled in or on the order atomics arrive (integer add / sub / min only): two calls give
 // equal bytes.  The host reads the status words once per BATCH rounds; kernels launched after the stop return at once.
-#include "radix_sort.h"
+#include "mesh_common.h"
 using namespace pdhip;
 
 namespace {
 
 constexpr int TB = 256;
 constexpr int ID_BITS = 22;                                       // vertex id width inside the 64-bit claim key (hash 20 | u 22 | v 22)
-constexpr int MAX_V = 1 << ID_BITS, MAX_F = 1 << 23;              // 3F < 2^31
+constexpr int MAX_V = 1 << ID_BITS, MAX_F = MESH_MAX_F;           // (MAX_V: the key width, not MESH_MAX_V)
 constexpr int MAX_ROUNDS = 1024, BATCH = 8;
 constexpr int NBIN = 4096;                                        // cost bins: 256 binary exponents x 16 mantissa steps
 constexpr int FLAG_STALLED = 1, FLAG_BAD_INPUT = 2;
-constexpr int M_ERR = 0, M_F = 1, M_ROUND = 2, M_STOP = 3, M_FLAGS = 4, M_TAU = 5, M_W = 6, M_WORDS = 16;
+constexpr int M_ERR = 0, M_F = 1, M_ROUND = 2, M_STOP = 3, M_FLAGS = 4, M_TAU = 5, M_W = 6, M_READ = 8, M_WORDS = 16;   // the host reads M_READ
 constexpr uint64_t INVALID = ~0ull;
 
 struct Quad { double a00, a01, a02, a11, a12, a22, b0, b1, b2, c; };
@@ -62,11 +62,11 @@ __global__ void k_sm_edge_keys(const int64_t* __restrict__ faces, int F, int V, 
     if (i >= 3 * F) return;
     const int f = i / 3, c = i - 3 * f;
     int64_t a = faces[i], b = faces[3 * (size_t)f + (c == 2 ? 0 : c + 1)];
-    if (a < 0 || a >= V || b < 0 || b >= V || a == b) {
+    if (!(index_ok(a, V) && index_ok(b, V)) || a == b) {
         atomicOr(&misc[M_ERR], FLAG_BAD_INPUT);
         a = 0; b = 0;
     }
-    keys[i] = (uint64_t)a * (uint64_t)V + (uint64_t)b;
+    keys[i] = pair_key(a, b, V);
     vals[i] = i;
     face32[i] = (int)a;
 }
@@ -83,8 +83,8 @@ __device__ __forceinline__ int lower_bound(const uint64_t* __restrict__ keys, in
 __global__ void k_sm_check(const uint64_t* __restrict__ keys, int N, int V, int* __restrict__ misc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
-    const uint64_t key = keys[i], nv = (uint64_t)V;
-    const uint64_t rev = (key % nv) * nv + key / nv;
+    const uint64_t key = keys[i];
+    const uint64_t rev = pair_key(pair_second(key, V), pair_first(key, V), V);
     bool bad = i > 0 && keys[i - 1] == key;
     const int j = lower_bound(keys, N, rev);
     bad = bad || j >= N || keys[j] != rev;
@@ -109,9 +109,9 @@ __global__ void k_sm_quadrics(const uint64_t* __restrict__ keys, const int* __re
                               const float* __restrict__ P, double* __restrict__ Q) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= V) return;
-    const uint64_t nv = (uint64_t)V, end = ((uint64_t)v + 1ull) * nv;
+    const uint64_t end = pair_key(v + 1, 0, V);
     Quad k{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = lower_bound(keys, N, (uint64_t)v * nv); i < N && keys[i] < end; ++i) {
+    for (int i = lower_bound(keys, N, pair_key(v, 0, V)); i < N && keys[i] < end; ++i) {
         const int g = vals[i] / 3;
         const int a = face[3 * (size_t)g], b = face[3 * (size_t)g + 1], c = face[3 * (size_t)g + 2];
         const double ax = P[3 * (size_t)a], ay = P[3 * (size_t)a + 1], az = P[3 * (size_t)a + 2];
@@ -456,12 +456,6 @@ static size_t carve_sim(SimWs& w, void* base, int V, int F) {
 
 static bool sizes_ok(int V, int F) { return V >= 4 && F >= 4 && V <= MAX_V && F <= MAX_F; }
 
-static int read_misc(const int* misc, int* h, hipStream_t s) {
-    PD_HIP(hipMemcpyAsync(h, misc, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
-    PD_HIP(hipStreamSynchronize(s));
-    return PDHIP_OK;
-}
-
 }  // namespace
 
 extern "C" size_t pdhip_simplify_mesh_workspace_bytes(int Vn, int F) {
@@ -489,7 +483,7 @@ extern "C" int pdhip_simplify_mesh(const float* vertices, int Vn, const int64_t*
     }
     SimWs w;
     carve_sim(w, ws, V, F);
-    int h[8];
+    int h[M_READ];
     // ---- input check: one sort of the directed edges
     PD_HIP(hipMemsetAsync(w.misc, 0, M_WORDS * sizeof(int), s));
     PD_HIP(hipMemsetAsync(w.deg, 0, ((size_t)V + 1) * sizeof(int), s));
@@ -500,7 +494,7 @@ extern "C" int pdhip_simplify_mesh(const float* vertices, int Vn, const int64_t*
     k_sm_init<<<cdiv(V, TB), TB, 0, s>>>(vertices, vertex_colors, V, F, w.P, w.C, w.remap, w.misc);
     k_sm_quadrics<<<cdiv(V, TB), TB, 0, s>>>(w.sb.k[cur], w.sb.v[cur], N, V, w.face[0], w.P, w.Q);
     PD_LAUNCH_CHECK();
-    int rc = read_misc(w.misc, h, s);
+    int rc = read_words(w.misc, h, M_READ, s);
     if (rc != PDHIP_OK) return rc;
     if (h[M_ERR]) {
         k_sm_counts<<<1, 1, 0, s>>>(counts, 0, 0, 0, 0, FLAG_BAD_INPUT);
@@ -532,7 +526,7 @@ extern "C" int pdhip_simplify_mesh(const float* vertices, int Vn, const int64_t*
             k_sm_round_end<<<1, 1, 0, s>>>(w.kflag, w.kexcl, target_faces, w.misc);
         }
         PD_LAUNCH_CHECK();
-        rc = read_misc(w.misc, h, s);
+        rc = read_words(w.misc, h, M_READ, s);
         if (rc != PDHIP_OK) return rc;
         stop = h[M_STOP] != 0;
         Fh = h[M_F];

@@ -1,9 +1,11 @@
-// The lock-free union-find of mesh_components.hip (connected components of a face list) and mesh_clean.hip (classes of close vertices): the device
-// functions of one walk and one union.  parent[v] <= v at every moment, and every value parent[v] ever holds is v or a vertex connected to v, so the
-// forest is acyclic whatever the threads' order, every walk goes to strictly smaller indices, and the one root a class ends with is its smallest
-// index.  parent[] is shared between workgroups on different XCDs while unions run, so every access here is an agent-scope atomic (relaxed: an
-// ancestor is all a walk needs).  No thread waits for another; every loop spends a budget of the caller's that strictly decreasing walks cannot
-// use up.  Internal linkage: each including unit gets its own copy.
+// The lock-free union-find of mesh_components.hip (connected components of a face list, over the vertices), mesh_clean.hip (classes of close
+// vertices) and uv_atlas.hip (charts: components of equally labelled faces, over the faces): one walk, one union, one read-only walk, and the
+// identity forest.  parent[v] <= v at every moment, and every value parent[v] ever holds is v or a vertex connected to v, so the forest is
+// acyclic whatever the threads' order, every walk goes to strictly smaller indices, and the one root a class ends with is its smallest index:
+// the partition AND its roots are functions of the united pairs alone.  parent[] is shared between workgroups on different XCDs while unions
+// run, so find_root and unite access it by agent-scope atomics (relaxed: an ancestor is all a walk needs).  No thread waits for another;
+// every loop spends a budget of the caller's that strictly decreasing walks cannot use up (a caller that sees -1 reports it: the forest is not
+// the one described here).  Internal linkage: each including unit gets its own copy; tests/test_gpu_prims.py runs the copy in prims_debug.hip.
 #pragma once
 #include "common.h"
 
@@ -12,6 +14,11 @@ namespace {
 
 __device__ __forceinline__ int ld_agent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_agent(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ void k_uf_identity(int* __restrict__ parent, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) parent[i] = i;
+}
 
 // representative of x; halves the path on the way (parent[prev] = its grandparent, an ancestor and < prev).  -1: the budget ran out
 __device__ __forceinline__ int find_root(int* parent, int x, long long& budget) {
@@ -39,6 +46,18 @@ __device__ __forceinline__ int unite(int* parent, int ra, int rb, long long& bud
         rb = lo;
     }
     return (ra < 0 || rb < 0) ? -1 : ra;
+}
+
+// the root of v in a forest that an EARLIER launch finished, or -1 when `steps` ran out (a strictly decreasing walk from v has at most v
+// steps).  Plain loads suffice across a kernel boundary: the launch that wrote parent[] has completed, and a launch that rewrites it while it
+// walks (k_mc_compress) stores only ancestors, so whichever of the two values a thread reads, it is an ancestor of v.
+__device__ __forceinline__ int walk_root(const int* parent, int v, int& steps) {
+    int r = v;
+    for (int p = parent[r]; p < r; p = parent[r]) {
+        r = p;
+        if (--steps < 0) return -1;
+    }
+    return r;
 }
 
 }  // namespace

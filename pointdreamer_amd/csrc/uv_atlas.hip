@@ -6,8 +6,8 @@
 //      area, or an index outside [0, Vn)) get label 6;
 //   b. edge adjacency: edge keys min * Vn + max, radix-sorted; a key held by exactly two faces joins them;
 //   c. label smoothing: Jacobi passes, a face takes the label two of its neighbours share if n.axis >= cos 70;
-//   d. charts = connected components of equal labels (union-find hooked towards the smaller index with atomicCAS);
-//      the chart id is the smallest face index of the component;
+//   d. charts = connected components of equal labels (union_find.h, over the faces); the chart id is the smallest face index of the
+//      component;
 //   e. charts of fewer than MERGE_K faces take the label of an adjacent chart whose axis all their faces accept, then d again;
 //   f. per-chart projection onto the axis plane, one UV entry per (chart, vertex);
 //   g. shelf packing at the largest common scale that fits (one workgroup, one candidate scale per thread), then a coverage
@@ -16,9 +16,9 @@
 // No float atomics: bounding boxes are order-preserving integer keys, counts are integer adds, every result is independent of
 // scheduling (two calls give identical bytes).  The host reads one word per packing round (overlap / error flags).
 // Compiled with -ffp-contract=off.
-#include "common.h"
 #include "raster_rules.h"
-#include "radix_sort.h"
+#include "mesh_common.h"
+#include "union_find.h"
 #include <algorithm>
 using namespace pdhip;
 
@@ -32,10 +32,8 @@ constexpr int MERGE_ROUNDS = 6;
 constexpr int SPLIT_ROUNDS = 8;
 constexpr int SINGLE_ROUNDS = 4;     // after SPLIT_ROUNDS: overlapping charts become one chart per face (a re-pack at a smaller scale can
                                      // expose an overlap in a chart checked at the larger one, so the check goes on)
-constexpr int FLAG_OVERLAP = 1, ERR_INDEX = 2, ERR_PACK = 4;
+constexpr int FLAG_OVERLAP = 1, ERR_INDEX = 2, ERR_PACK = 4, ERR_STATE = 8;
 enum { M_FLAG = 0, M_CHARTS = 1, M_SCALE = 2, M_WORDS = 64 };
-
-__device__ __forceinline__ int ald(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // orientation-preserving orthographic projection onto the plane of axis `lab` (u x v = the axis)
 __device__ __forceinline__ void axis_proj(int lab, float x, float y, float z, float& u, float& v) {
@@ -64,7 +62,7 @@ __global__ void k_uva_faces(const float* __restrict__ V, int Vn, const int64_t* 
     bool ok = true;
     for (int k = 0; k < 3; ++k) {
         const int64_t a = faces[3 * (size_t)f + k];
-        const bool in = a >= 0 && a < (int64_t)Vn;
+        const bool in = index_ok(a, Vn);
         ok = ok && in;
         id[k] = in ? (int)a : 0;
         idx[3 * f + k] = id[k];
@@ -88,7 +86,7 @@ __global__ void k_uva_faces(const float* __restrict__ V, int Vn, const int64_t* 
     lab[f] = L;
     for (int k = 0; k < 3; ++k) {
         const int a = id[k], b = id[(k + 1) % 3];
-        ekey[3 * f + k] = ok ? (uint64_t)min(a, b) * (uint64_t)Vn + (uint64_t)max(a, b) : (uint64_t)Vn * (uint64_t)Vn;   // (Vn^2: joins nothing)
+        ekey[3 * f + k] = ok ? pair_key(min(a, b), max(a, b), Vn) : (uint64_t)Vn * (uint64_t)Vn;   // (Vn^2: joins nothing)
         eval[3 * f + k] = 3 * f + k;
     }
 }
@@ -125,50 +123,28 @@ __global__ void k_uva_smooth(const int* __restrict__ adj, const float* __restric
     lout[f] = out;
 }
 
-// d. connected components of equal labels
-__device__ int uf_find(int* par, int x) {
-    while (true) {
-        const int p = ald(&par[x]);
-        if (p == x) return x;
-        const int gp = ald(&par[p]);
-        if (gp == p) return p;
-        atomicMin(&par[x], gp);                                   // path halving: only ever lowers a pointer to an ancestor
-        x = gp;
-    }
-}
-__global__ void k_uva_cc_init(int* __restrict__ par, int F) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f < F) par[f] = f;
-}
-__global__ void k_uva_cc_hook(const int* __restrict__ adj, const int* __restrict__ lab, int* par, int F) {
+// d. connected components of equal labels: the union-find of union_find.h over the faces.  Every union keeps par[f] <= f and ends each
+// component with its smallest face index as the one root, whatever the threads' order, so chart[] is a function of adj and lab alone (any
+// union-find with these two properties, however it hooks and halves, gives the same bytes).  A spent budget (the forest is not the descending one)
+// leaves chart[f] = f, an index in range for every later kernel, and sets ERR_STATE, which the entry reads with the packing round's flags
+__global__ void k_uva_cc_hook(const int* __restrict__ adj, const int* __restrict__ lab, int* par, int F, int* __restrict__ misc) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= F) return;
     const int l = lab[f];
+    long long budget = 2ll * F + 64;
     for (int k = 0; k < 3; ++k) {
         const int g = adj[3 * f + k];
         if (g <= f || lab[g] != l) continue;
-        int a = f, b = g;
-        while (true) {
-            a = uf_find(par, a);
-            b = uf_find(par, b);
-            if (a == b) break;
-            const int hi = max(a, b), lo = min(a, b);
-            const int old = atomicCAS(&par[hi], hi, lo);          // hook the larger root under the smaller one
-            if (old == hi) break;
-            if (hi == a) a = old; else b = old;
-        }
+        if (unite(par, find_root(par, f, budget), find_root(par, g, budget), budget) < 0) atomicOr(&misc[M_FLAG], ERR_STATE);
     }
 }
-__global__ void k_uva_cc_flatten(int* par, int* __restrict__ chart, int F) {
+__global__ void k_uva_cc_flatten(const int* __restrict__ par, int* __restrict__ chart, int F, int* __restrict__ misc) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= F) return;
-    int r = f;
-    while (true) {
-        const int p = par[r];
-        if (p == r) break;
-        r = p;
-    }
-    chart[f] = r;                                                // = the smallest face index of the component
+    int steps = F;
+    int r = walk_root(par, f, steps);                            // = the smallest face index of the component
+    if (r < 0) { atomicOr(&misc[M_FLAG], ERR_STATE); r = f; }
+    chart[f] = r;
 }
 
 // e. small-chart merge
@@ -479,12 +455,8 @@ __global__ void k_uva_entry_keys(const int* __restrict__ chart, const int* __res
                                  int* __restrict__ val, int n) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n) return;
-    key[c] = (uint64_t)(unsigned)chart[c / 3] * (uint64_t)Vn + (uint64_t)(unsigned)idx[c];
+    key[c] = pair_key((unsigned)chart[c / 3], (unsigned)idx[c], Vn);
     val[c] = c;
-}
-__global__ void k_uva_entry_flags(const uint64_t* __restrict__ key, int* __restrict__ flag, int n) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n) flag[p] = (p == 0 || key[p] != key[p - 1]) ? 1 : 0;
 }
 __global__ void k_uva_entry_write(const float* __restrict__ V, const int* __restrict__ idx, const int* __restrict__ chart, const int* __restrict__ lab,
                                   const unsigned* __restrict__ box, const int* __restrict__ cpos, const int* __restrict__ misc, int gutter, int R,
@@ -571,9 +543,9 @@ extern "C" int pdhip_uv_atlas(const float* vertices, int Vn, const int64_t* face
     for (int it = 0; it < SMOOTH_PASSES; ++it, L ^= 1) k_uva_smooth<<<gF, TB, 0, s>>>(w.adj, w.nrm, w.lab[L], w.lab[L ^ 1], F);
     // d, e
     auto components = [&]() {
-        k_uva_cc_init<<<gF, TB, 0, s>>>(w.par, F);
-        k_uva_cc_hook<<<gF, TB, 0, s>>>(w.adj, w.lab[L], w.par, F);
-        k_uva_cc_flatten<<<gF, TB, 0, s>>>(w.par, w.chart, F);
+        k_uf_identity<<<gF, TB, 0, s>>>(w.par, F);
+        k_uva_cc_hook<<<gF, TB, 0, s>>>(w.adj, w.lab[L], w.par, F, w.misc);
+        k_uva_cc_flatten<<<gF, TB, 0, s>>>(w.par, w.chart, F, w.misc);
     };
     components();
     for (int m = 0; m < MERGE_ROUNDS; ++m) {
@@ -606,8 +578,13 @@ extern "C" int pdhip_uv_atlas(const float* vertices, int Vn, const int64_t* face
         }
         PD_LAUNCH_CHECK();
         int word = 0;
-        PD_HIP(hipMemcpyAsync(&word, w.misc + M_FLAG, sizeof(int), hipMemcpyDeviceToHost, s));
-        PD_HIP(hipStreamSynchronize(s));
+        const int rc = read_words(w.misc + M_FLAG, &word, 1, s);
+        if (rc != PDHIP_OK) return rc;
+        if (word & ERR_STATE) {
+            set_error("pdhip_uv_atlas: a union-find walk used up its budget of steps: the forest is not the descending one the kernels keep; "
+                      "nothing was written");
+            return PDHIP_E_STATE;
+        }
         PD_REQUIRE(!(word & ERR_INDEX), "pdhip_uv_atlas: a face index lies outside [0, Vn=%d)", Vn);
         PD_REQUIRE(!(word & ERR_PACK), "pdhip_uv_atlas: the charts do not fit a %d x %d atlas with gutter %d", R, R, gutter);
         if (!check || !(word & FLAG_OVERLAP)) break;
@@ -627,7 +604,7 @@ extern "C" int pdhip_uv_atlas(const float* vertices, int Vn, const int64_t* face
     // f: UV entries
     k_uva_entry_keys<<<gN, TB, 0, s>>>(w.chart, w.idx, Vn, w.sb.k[0], w.sb.v[0], N);
     cur = radix_sort(w.sb, N, bits_for((unsigned long long)F * (unsigned long long)Vn), s);
-    k_uva_entry_flags<<<gN, TB, 0, s>>>(w.sb.k[cur], w.flag, N);
+    k_run_heads<uint64_t><<<gN, TB, 0, s>>>(w.sb.k[cur], N, nullptr, ~0ull, w.flag);
     k_scan<<<1, SC_T, 0, s>>>(w.flag, w.incl, N, 0);
     k_uva_entry_write<<<gN, TB, 0, s>>>(vertices, w.idx, w.chart, lab, w.box, w.cpos, w.misc, gutter, R, w.sb.v[cur], w.flag, w.incl, uvs,
                                         tex_idx, N);

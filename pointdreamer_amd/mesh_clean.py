@@ -26,20 +26,7 @@ MAX_VERTICES_FACES = 1 << 21               # pdhip_clean_faces: three indices of
 MISC_WORDS = 64
 
 
-def _gpu(x, what, shape_name, dtype_fn):
-    if not (torch.is_tensor(x) and x.is_cuda):
-        raise PdhipError(f"{what} needs tensors on the GPU (cuda:N == HIP device); there is no CPU path")
-    if x.dim() != 2 or x.shape[1] != 3:
-        raise PdhipError(f"{what}: expected {shape_name}, got {tuple(x.shape)}")
-    return dtype_fn(x.detach()).contiguous()
-
-
-def _vertices(x, what, name='vertices'):
-    return _gpu(x, what, f'{name} [Vn,3]', lambda t: t.float())
-
-
-def _faces(x, what):
-    return _gpu(x, what, 'faces [F,3]', lambda t: t.long())
+_vertices, _faces = mesh_components._vertices, mesh_components._faces
 
 
 def _tolerance(tolerance):

@@ -12,30 +12,18 @@ CPU path."""
 import torch
 
 from . import _lib
-from ._lib import ptr, stream, check, PdhipError
+from ._lib import ptr, ptr_or_null, rows, stream, check, PdhipError
 
 DEFAULT_CAPACITY = 4096                # components the first call has room for; a mesh with more is labelled once more with exactly C
 RULES = ('keep', 'min_faces', 'min_face_share', 'min_diameter_share')
 
 
 def _faces(faces, what):
-    if not (torch.is_tensor(faces) and faces.is_cuda):
-        raise PdhipError(f"{what} needs tensors on the GPU (cuda:N == HIP device); there is no CPU path")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise PdhipError(f"{what}: expected faces [F,3], got {tuple(faces.shape)}")
-    return faces.detach().long().contiguous()
+    return rows(faces, what, 'faces [F,3]', 3, torch.int64)
 
 
 def _vertices(x, what, name='vertices'):
-    if not (torch.is_tensor(x) and x.is_cuda):
-        raise PdhipError(f"{what} needs tensors on the GPU (cuda:N == HIP device); there is no CPU path")
-    if x.dim() != 2 or x.shape[1] != 3:
-        raise PdhipError(f"{what}: expected {name} [Vn,3], got {tuple(x.shape)}")
-    return x.detach().float().contiguous()
-
-
-def _opt(t):
-    return ptr(t) if t is not None and t.numel() else ptr(None, allow_none=True)
+    return rows(x, what, f'{name} [Vn,3]', 3, torch.float32)
 
 
 def label_components(faces, n_vertices=None, vertices=None, return_stats=False):
@@ -61,7 +49,7 @@ def label_components(faces, n_vertices=None, vertices=None, return_stats=False):
     while True:
         root, nv, nf = (torch.empty((cap,), dtype=torch.int32, device=dev) for _ in range(3))
         box = torch.empty((cap, 6), dtype=torch.float32, device=dev) if v is not None else None
-        check(L.pdhip_mesh_components(ptr(f) if F else ptr(one), F, _opt(v), Vn, _opt(vcomp), ptr(fcomp) if F else ptr(one), ptr(root), ptr(nv), ptr(nf),
+        check(L.pdhip_mesh_components(ptr(f) if F else ptr(one), F, ptr_or_null(v), Vn, ptr_or_null(vcomp), ptr(fcomp) if F else ptr(one), ptr(root), ptr(nv), ptr(nf),
                                       ptr(box, allow_none=True), cap, ptr(counts), ptr(ws), stream()), 'pdhip_mesh_components')
         C, referenced, unreferenced, _ = counts.tolist()
         if C <= cap:
@@ -98,7 +86,7 @@ def compact_mesh(vertices, faces, face_keep, colors=None, return_map=False):
     vmap = torch.empty((Vn,), dtype=torch.int32, device=dev) if return_map else None
     counts = torch.empty((4,), dtype=torch.int32, device=dev)
     one = None if F else torch.zeros((8,), dtype=torch.int64, device=dev)      # (a non-null pointer for the arrays of an empty face list)
-    check(L.pdhip_compact_mesh(_opt(v), Vn, ptr(f) if F else ptr(one), F, ptr(c, allow_none=True), ptr(k) if F else ptr(one), _opt(ov),
+    check(L.pdhip_compact_mesh(ptr_or_null(v), Vn, ptr(f) if F else ptr(one), F, ptr(c, allow_none=True), ptr(k) if F else ptr(one), ptr_or_null(ov),
                                ptr(of) if F else ptr(one), ptr(oc, allow_none=True), ptr(vmap, allow_none=True), ptr(counts), ptr(ws), stream()),
           'pdhip_compact_mesh')
     nv, nf = counts.tolist()[:2]

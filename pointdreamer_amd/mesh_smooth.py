@@ -14,7 +14,7 @@ import math
 import torch
 
 from . import _lib, mesh_utils
-from ._lib import ptr, stream, check, PdhipError
+from ._lib import ptr, rows, stream, check, PdhipError
 
 DEFAULT_STEPS, DEFAULT_LAMBDA, DEFAULT_MU = 10, 0.5, -0.53             # MeshLab's "Taubin Smooth" defaults
 MAX_STEPS = 10000
@@ -41,11 +41,7 @@ def check_params(steps, lam, mu):
 
 
 def _faces(faces, what):
-    if not (torch.is_tensor(faces) and faces.is_cuda):
-        raise PdhipError(f"{what} needs tensors on the GPU (cuda:N == HIP device); there is no CPU path")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise PdhipError(f"{what}: expected faces [F,3], got {tuple(faces.shape)}")
-    return faces.detach().long().contiguous()
+    return rows(faces, what, 'faces [F,3]', 3, torch.int64)
 
 
 def _csr(num_vertices, f):
@@ -87,11 +83,9 @@ def taubin_smooth(vertices, faces, steps=DEFAULT_STEPS, lam=DEFAULT_LAMBDA, mu=D
     if boundary not in ('fixed', 'free'):
         raise ValueError(f"boundary={boundary!r}: 'fixed' (boundary vertices stay) or 'free'")
     f = _faces(faces, what)
-    if not (torch.is_tensor(vertices) and vertices.is_cuda) or (fixed is not None and not (torch.is_tensor(fixed) and fixed.is_cuda)):
+    if fixed is not None and not (torch.is_tensor(fixed) and fixed.is_cuda):
         raise PdhipError(f"{what} needs tensors on the GPU (cuda:N == HIP device); there is no CPU path")
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise PdhipError(f"{what}: expected vertices [Vn,3], got {tuple(vertices.shape)}")
-    v = vertices.detach().float().contiguous()
+    v = rows(vertices, what, 'vertices [Vn,3]', 3, torch.float32)
     Vn, dev = v.shape[0], v.device
     if fixed is not None and tuple(fixed.shape) != (Vn,):
         raise PdhipError(f"{what}: fixed {tuple(fixed.shape)} for {Vn} vertices")

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ptr, stream, check, PdhipError
+from ._lib import ptr, rows, stream, check, PdhipError
 
 DEPTHS = (6, 7, 8)
 DEFAULT_DEPTH = 6                    # 7-36 k faces, the size the stages downstream were tuned at (DESIGN, surface reconstruction)
@@ -19,11 +19,7 @@ EYE_RADIUS = 1.6                     # the cameras' distance (demo.py:337), in u
 
 
 def _points(points, what):
-    if not torch.is_tensor(points) or not points.is_cuda:
-        raise PdhipError(f"{what} needs tensors on the GPU (cuda:N == HIP device); there is no CPU path")
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise PdhipError(f"{what}: expected [N,3], got {tuple(points.shape)}")
-    return points.detach().float().contiguous()
+    return rows(points, what, '[N,3]', 3, torch.float32)
 
 
 def estimate_normals(points, k=DEFAULT_KNN, n_eyes=32, return_counts=False, eye_radius=EYE_RADIUS):
@@ -103,11 +99,7 @@ def simplify_mesh(vertices, faces, target_faces, colors=None, return_counts=Fals
     colour of the collapsed endpoint nearer to it.  return_counts: a last result, dict(vertices, faces, rounds, stalled); stalled = no
     further collapse keeps the topology and the shape, the mesh has more faces than asked for.  target_faces >= F returns the input."""
     v = _points(vertices, 'simplify_mesh')
-    if not torch.is_tensor(faces) or not faces.is_cuda:
-        raise PdhipError("simplify_mesh needs tensors on the GPU (cuda:N == HIP device); there is no CPU path")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise PdhipError(f"simplify_mesh: expected faces [F,3], got {tuple(faces.shape)}")
-    f = faces.detach().long().contiguous()
+    f = rows(faces, 'simplify_mesh', 'faces [F,3]', 3, torch.int64)
     c = None
     if colors is not None:
         c = _points(colors, 'simplify_mesh')

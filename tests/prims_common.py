@@ -1,6 +1,6 @@
 """Shared by tests/test_prims_cpu.py and tests/test_gpu_prims.py: exact numpy references of the shared device primitives (csrc/radix_sort.h, the
-sort half of csrc/cell_list.h), the key generators and case tables the GPU tests run, and checkers that compare bit for bit.  Plain numpy, no
-GPU; nothing here is imported by the product.  All of it is integer work: no tolerance anywhere."""
+sort half of csrc/cell_list.h, the union-find of csrc/union_find.h), the key generators and case tables the GPU tests run, and checkers that
+compare bit for bit.  Plain numpy, no GPU; nothing here is imported by the product.  All of it is integer work: no tolerance anywhere."""
 import numpy as np
 
 TILE = 2048                                                        # RS_TILE and SCB_TILE: the elements one workgroup of the sort / the tiled scan takes
@@ -233,6 +233,48 @@ KSCAN_SIZES = (1, 2, 1023, 1024, 1025, 2047, 2048, 2049, 5000, 37893)
 TILED_SIZES = (1, 7, 8, 9, 2047, 2048, 2049, 4096, 4097, 6145, 2048 * 1024, 2048 * 1025 + 3)
 TILED_LARGE = TILED_SIZES[-2:]                                     # nt == SC_T and nt == SC_T + 1: (int, exclusive) and (uint64_t, inclusive) only
 SCAN_FORMS = (('int', 0), ('int', 1), ('uint64', 0), ('uint64', 1))                             # (element type, inclusive)
+
+
+# ---- the union-find of csrc/union_find.h: union_case(name) -> (n, pairs int32 [P, 2]); the reference is mesh_clean_common.union_find
+UNION_N = 4096                                                     # 16 workgroups of 256 pairs; a chain of it gives the longest walks there are
+UNION_CASES = ('single', 'self_pair', 'chain_ascending', 'chain_descending', 'chain_shuffled', 'star_on_first', 'star_on_last', 'chain_four_times',
+               'random_3000_on_1000', 'pairs_255', 'pairs_256', 'pairs_257')
+
+
+def union_case(name):
+    rng = np.random.default_rng(_seed('union', name))
+    n = UNION_N
+    i = np.arange(n - 1)
+    chain = np.stack([i, i + 1], 1)
+    if name == 'single':
+        n, p = 1, np.zeros((0, 2))
+    elif name == 'self_pair':
+        n, p = 1, np.zeros((1, 2))
+    elif name == 'chain_ascending':
+        p = chain
+    elif name == 'chain_descending':
+        p = chain[::-1]
+    elif name == 'chain_shuffled':
+        p = chain[rng.permutation(n - 1)]
+    elif name == 'star_on_first':                                   # every thread's CAS meets the one root
+        p = np.stack([np.zeros(n - 1, np.int64), i + 1], 1)
+    elif name == 'star_on_last':
+        p = np.stack([np.full(n - 1, n - 1), i], 1)
+    elif name == 'chain_four_times':                                # every pair listed four times, both ways round
+        p = np.concatenate([chain, chain[:, ::-1], chain, chain[:, ::-1]])[rng.permutation(4 * (n - 1))]
+    elif name == 'random_3000_on_1000':
+        n, p = 1000, rng.integers(0, 1000, (3000, 2))
+    elif name.startswith('pairs_'):                                 # the workgroup edge of the one-thread-per-pair launch
+        n, p = 600, rng.integers(0, 600, (int(name[6:]), 2))
+    else:
+        raise KeyError(name)
+    return n, np.ascontiguousarray(p).astype(np.int32)
+
+
+def ref_union(n, pairs):
+    """root [n] int32: the smallest index of every class (a sequential union-find, the smaller index staying the root)."""
+    from mesh_clean_common import union_find
+    return union_find(n, pairs)
 
 
 def scan_inputs(elem, n, tiled):

@@ -6,7 +6,11 @@ size the query reports.
 
 The sizes are the ones at which these kernels change path: one wave (64), one item round (256), one tile (2048) and one element either side of
 each; more than 8192 elements, where the digit histograms outgrow one k_scan chunk per thread (11017: 6 tiles, 300001: 147); key widths with a
-partial top digit; 1024 and 1025 tiles of the tiled scan, where the scan of the tile sums goes from one element per thread to two."""
+partial top digit; 1024 and 1025 tiles of the tiled scan, where the scan of the tile sums goes from one element per thread to two.
+
+The union-find of csrc/union_find.h (find_root, unite, walk_root, k_uf_identity) is held to a sequential union-find: chains of 4096 in three
+orders (the longest walks), stars onto the first and the last vertex (every CAS meets one root), repeated pairs, a random graph, and 255 / 256 /
+257 pairs, the workgroup edge of the one-thread-per-pair launch."""
 import numpy as np
 import pytest
 import torch
@@ -112,3 +116,36 @@ def test_tiled_scan(pd, elem, inclusive, n):
     for x in pc.scan_inputs(elem, n, tiled=True).values():
         assert x.dtype == NP[elem]
         run_scan(pd, x, 1, inclusive)
+
+
+# ---- the union-find of csrc/union_find.h: k_uf_identity, unite(find_root, find_root) per pair, walk_root per vertex
+def run_union(pd, n, pairs):
+    P, S = pd['lib'].ptr, pd['lib'].stream
+    p = dev(pairs) if len(pairs) else None
+    parent, root, status = sentinel(n + PAD, np.int32), sentinel(n + PAD, np.int32), sentinel(1 + PAD, np.int32)
+    rc = pd['L'].pdhip_debug_union_pairs(P(p, allow_none=True), len(pairs), n, P(parent), P(root), P(status), S())
+    parent, root, status = host(parent, np.int32), host(root, np.int32), host(status, np.int32)
+    for o, m in ((parent, n), (root, n), (status, 1)):
+        assert np.all(o[m:].view(np.uint8) == pc.SENTINEL), "written behind an output"
+    return rc, parent[:n], root[:n], int(status[0])
+
+
+@pytest.mark.parametrize("name", pc.UNION_CASES)
+def test_union_pairs(pd, name):
+    n, pairs = pc.union_case(name)
+    rc, parent, root, status = run_union(pd, n, pairs)
+    ok(pd, rc)
+    assert status == 0, f"a budget ran out (status {status})"
+    pc.check_equal(root, pc.ref_union(n, pairs), f"union-find roots ({name}, n={n}, {len(pairs)} pairs)")
+    assert np.all(parent <= np.arange(n)), "parent[v] > v: the forest does not descend"
+    assert np.array_equal(root[parent], root), "a vertex and its parent in different classes"
+
+
+def test_union_pairs_refuses_an_index_outside(pd):
+    n, pairs = pc.union_case('pairs_257')
+    for where, value in ((0, -1), (256, n), (100, 1 << 30)):
+        bad = pairs.copy()
+        bad[where, 1] = value
+        rc, parent, _, _ = run_union(pd, n, bad)
+        assert rc == -1 and b'outside [0, n=600)' in pd['L'].pdhip_last_error() and b'1 pair(s)' in pd['L'].pdhip_last_error()
+        assert np.all(parent.view(np.uint8) == pc.SENTINEL), "parent was touched before the refusal"

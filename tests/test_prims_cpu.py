@@ -1,6 +1,7 @@
 """The shared device primitives without a GPU: the references of tests/prims_common.py against slower independent ones, the checkers shown to
-fail on the faults they are there for, the key generators' promises, the size query pdhip_debug_prims_workspace_bytes and the refusals of the three test
-entries (include/pdhip.h; they return before any HIP call).  tests/test_gpu_prims.py runs the kernels."""
+fail on the faults they are there for, the key generators' promises, the union-find's reference and cases, the size query
+pdhip_debug_prims_workspace_bytes and the refusals of the four test entries (include/pdhip.h; they return before any HIP call).
+tests/test_gpu_prims.py runs the kernels."""
 import ctypes
 
 import numpy as np
@@ -186,6 +187,32 @@ def test_checker_sees_cstart_off_by_one_in_an_empty_cell():
         pc.check_sort_by_cell(keys, 300, k, idx, bad)
 
 
+# ---- the union-find reference and its cases
+@pytest.mark.parametrize("name", pc.UNION_CASES)
+def test_union_reference_against_connected_components(name):
+    """The sequential union-find against scipy's connected components of the same graph, relabelled to each class's smallest index."""
+    import mesh_clean_common as cc
+    n, pairs = pc.union_case(name)
+    assert pairs.dtype == np.int32 and pairs.shape[1:] == (2,) and (len(pairs) == 0 or (pairs.min() >= 0 and pairs.max() < n))
+    root = pc.ref_union(n, pairs)
+    assert root.dtype == np.int32 and root.shape == (n,)
+    assert np.array_equal(root, cc.rep_of_labels(cc.graph_labels(n, pairs.astype(np.int64))))
+    assert np.all(root <= np.arange(n)) and np.array_equal(root[root], root)       # the smallest index of the class, itself a root
+
+
+def test_union_cases_are_what_they_say():
+    sizes = {name: (pc.union_case(name)[0], len(pc.union_case(name)[1])) for name in pc.UNION_CASES}
+    assert sizes['single'] == (1, 0) and sizes['self_pair'] == (1, 1) and pc.union_case('self_pair')[1].tolist() == [[0, 0]]
+    for name in ('chain_ascending', 'chain_descending', 'chain_shuffled', 'star_on_first', 'star_on_last'):
+        assert sizes[name] == (4096, 4095)
+        assert not pc.ref_union(*pc.union_case(name)).any()                        # one class: every root is 0
+    assert pc.union_case('chain_ascending')[1][:2].tolist() == [[0, 1], [1, 2]] and pc.union_case('chain_descending')[1][0].tolist() == [4094, 4095]
+    assert np.all(pc.union_case('star_on_last')[1][:, 0] == 4095) and np.all(pc.union_case('star_on_first')[1][:, 0] == 0)
+    assert sizes['chain_four_times'] == (4096, 4 * 4095) and sizes['random_3000_on_1000'] == (1000, 3000)
+    assert [sizes[f'pairs_{k}'][1] for k in (255, 256, 257)] == [255, 256, 257]
+    assert len(np.unique(pc.ref_union(*pc.union_case('random_3000_on_1000')))) > 1  # more than one class: the labels matter
+
+
 # ---- the size query
 def test_size_query_domain(L):
     q = L.pdhip_debug_prims_workspace_bytes
@@ -237,3 +264,12 @@ def test_entries_refuse_bad_arguments(L):
         refused(scan(None, p, 8, 8, mode, 1, 1, p, None), b'pdhip_debug_scan', b'null pointer (in)')
         refused(scan(p, p, 8, 8, mode, 1, 0, p, None), b'pdhip_debug_scan', b'nc=0')
     refused(scan(p, p, 8, 4, 2, 0, 1, p, None), b'pdhip_debug_scan', b'mode=2')
+    union = L.pdhip_debug_union_pairs                               # (pairs, n_pairs, n, parent, root, status, stream)
+    refused(union(p, 4, 0, p, p, p, None), b'pdhip_debug_union_pairs', b'n=0')
+    refused(union(p, 4, (1 << 26) + 1, p, p, p, None), b'pdhip_debug_union_pairs', b'n=')
+    refused(union(p, -1, 8, p, p, p, None), b'pdhip_debug_union_pairs', b'n_pairs=-1')
+    refused(union(p, (1 << 26) + 1, 8, p, p, p, None), b'pdhip_debug_union_pairs', b'n_pairs=')
+    refused(union(None, 4, 8, p, p, p, None), b'pdhip_debug_union_pairs', b'null pointer (pairs)', b'n_pairs=4')
+    refused(union(p, 4, 8, None, p, p, None), b'pdhip_debug_union_pairs', b'null pointer (parent)')
+    refused(union(p, 4, 8, p, None, p, None), b'pdhip_debug_union_pairs', b'null pointer (root)')
+    refused(union(p, 4, 8, p, p, None, None), b'pdhip_debug_union_pairs', b'null pointer (status)')
