@@ -181,6 +181,25 @@ size_t pdhip_surface_recon_ws_bytes(int N, int depth);
 int pdhip_surface_recon(const float* points /*[N,3]*/, const float* normals /*[N,3]*/, const float* colors /*[N,3] or NULL*/, int N, int depth,
                         float* vertices, int vertex_capacity, int64_t* faces, int face_capacity, float* vertex_colors /*or NULL*/,
                         int32_t* counts /*device [4]*/, float* info /*device [8]*/, void* ws, void* stream);
+/* test hooks (csrc/surface_recon.hip; tests/test_gpu_spr_stages.py holds every stage to oracle/spr_stages.py through them).  Both entries above
+ * carve every intermediate from the caller's workspace, and most of it is still there when they return; the two layout hooks say where: byte
+ * offsets from `ws`, taken from the same carve functions on a base that is never dereferenced.  Host code only, no device work; PDHIP_E_ARG for a null pointer or for
+ * sizes whose size query returns 0.
+ * pdhip_debug_estimate_normals_layout: off [6] = cstart (i32, cells^3 + 1 used), spos ([N] float4: x, y, z in sorted order, w = the bits of the
+ *   point's index), knn ([N,k] i32, original indices, row i = the neighbours of point i), eyes ([n_eyes,3] f64), vis ([n_eyes,N] u8),
+ *   pdhip_estimate_normals_ws_bytes(N, k, n_eyes).
+ * pdhip_debug_surface_recon_layout: off [8] = cstart, spos (as above, of the reconstruction's own cell list), snrm ([N] float4, sorted order: the
+ *   normal times the sample weight, w = 0), chi ([M^3] f32, M = 2^depth + 1, x fastest: the solution), eflag ([M^3] u8: bit a set = the grid edge
+ *   that leaves the node along axis a crosses the iso value), misc ([64] i32: vertices, faces, iterations, -, -, the bits of the iso value, the
+ *   bits of the residual), f ([M^3] f32: OVERWRITTEN by the marching-cubes counts, hence the entry below), pdhip_surface_recon_ws_bytes(N, depth).
+ * pdhip_debug_surface_recon_rhs: the front half of pdhip_surface_recon, through the same function -- box, grid, splat radius, cell list, sample
+ *   weights, right-hand side -- then f -> f_out (device [M^3] f32).  info (device, 8 x f32): h, grid origin x y z, cell size and cells per axis of
+ *   the cell list, splat radius, nodes per axis.  ws: pdhip_surface_recon_ws_bytes(N, depth); spos, cstart and snrm are left in it as the layout
+ *   hook says.  Synchronises `stream`.  PDHIP_E_ARG before any device work: a null pointer, N outside 16 .. 2^24, depth outside 6 .. 8. */
+int pdhip_debug_estimate_normals_layout(int N, int k, int n_eyes, uint64_t* off /*host [6]*/);
+int pdhip_debug_surface_recon_layout(int N, int depth, uint64_t* off /*host [8]*/);
+int pdhip_debug_surface_recon_rhs(const float* points /*[N,3]*/, const float* normals /*[N,3]*/, int N, int depth, float* f_out /*[M^3]*/,
+                                  float* info /*device [8]*/, void* ws, void* stream);
 
 /* ---- Mesh decimation to a target face count (baselines/spr.py:63-64 asks pymeshlab's meshing_decimation_quadric_edge_collapse(
  *      targetfacenum, preservetopology=True) on the CPU; here quadric-error edge collapses in rounds of mutually independent collapses

@@ -47,6 +47,9 @@ _SIGS = {
     'pdhip_estimate_normals': (C.c_int, [vp, i32, i32, i32, f64, vp, vp, vp, vp]),
     'pdhip_surface_recon_ws_bytes': (sz, [i32, i32]),
     'pdhip_surface_recon': (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
+    'pdhip_debug_estimate_normals_layout': (C.c_int, [i32, i32, i32, vp]),
+    'pdhip_debug_surface_recon_layout': (C.c_int, [i32, i32, vp]),
+    'pdhip_debug_surface_recon_rhs': (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp]),
     'pdhip_simplify_mesh_workspace_bytes': (sz, [i32, i32]),
     'pdhip_simplify_mesh': (C.c_int, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
     'pdhip_sample_mesh_workspace_bytes': (sz, [i32, i32]),

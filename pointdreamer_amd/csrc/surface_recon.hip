@@ -107,6 +107,29 @@ __device__ __forceinline__ float ring_bound(float q, float o, float cs, int C, i
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // a, b. k nearest neighbours (the point itself included) and the unoriented normal
+// unit eigenvector of A for its eigenvalue lam: orthogonal to the three rows of A - lam I, the largest of their three cross products.
+// false: all three vanish
+__device__ __forceinline__ bool null_direction(double a00, double a01, double a02, double a11, double a12, double a22, double lam, double& nx,
+                                               double& ny, double& nz) {
+    const double r0x = a00 - lam, r0y = a01, r0z = a02, r1x = a01, r1y = a11 - lam, r1z = a12, r2x = a02, r2y = a12, r2z = a22 - lam;
+    const double ax = r0y * r1z - r0z * r1y, ay = r0z * r1x - r0x * r1z, az = r0x * r1y - r0y * r1x;
+    const double bx = r0y * r2z - r0z * r2y, by = r0z * r2x - r0x * r2z, bz = r0x * r2y - r0y * r2x;
+    const double cx = r1y * r2z - r1z * r2y, cy = r1z * r2x - r1x * r2z, cz = r1x * r2y - r1y * r2x;
+    const double la = ax * ax + ay * ay + az * az, lb = bx * bx + by * by + bz * bz, lc = cx * cx + cy * cy + cz * cz;
+    double vx = ax, vy = ay, vz = az, l = la;
+    if (lb > l) { vx = bx; vy = by; vz = bz; l = lb; }
+    if (lc > l) { vx = cx; vy = cy; vz = cz; l = lc; }
+    if (!(l > 0.0)) return false;
+    const double s = 1.0 / sqrt(l);
+    nx = vx * s; ny = vy * s; nz = vz * s;
+    return true;
+}
+
+// Eigenvalues of A in closed form: q + 2 p cos(phi + 2 pi k / 3), phi = acos(r) / 3, r = half the determinant of (A - q I) / p.  The eigenvalue
+// asked for directly is good to a few ulp of p while it is the isolated one (r <= 0: the two LARGEST are the close pair, a surface patch).  For
+// r > 0 the two SMALLEST are the close pair (a neighbourhood stretched along a line) and acos is ill-conditioned towards 1: the error of the direct
+// form grows with (lambda_2 / (lambda_1 - lambda_0))^2.  There the isolated, largest eigenvalue gives its eigenvector first, and the smallest one
+// comes from the symmetric 2 x 2 problem in the plane orthogonal to it, whose error grows with lambda_2 / (lambda_1 - lambda_0) only.
 __device__ __forceinline__ void smallest_eigvec(double a00, double a01, double a02, double a11, double a12, double a22, double& nx, double& ny,
                                                 double& nz) {
     const double p1 = a01 * a01 + a02 * a02 + a12 * a12;
@@ -120,21 +143,37 @@ __device__ __forceinline__ void smallest_eigvec(double a00, double a01, double a
         double r = 0.5 * (c00 * (c11 * c22 - c12 * c12) - c01 * (c01 * c22 - c12 * c02) + c02 * (c01 * c12 - c11 * c02));
         r = fmin(1.0, fmax(-1.0, r));
         const double phi = acos(r) / 3.0;
+        double ex, ey, ez;
+        if (r > 0.0 && null_direction(a00, a01, a02, a11, a12, a22, q + 2.0 * p * cos(phi), ex, ey, ez)) {
+            // u, w: an orthonormal basis of the plane orthogonal to e
+            double ux, uy, uz;
+            if (fabs(ex) > fabs(ey)) {
+                const double s = 1.0 / sqrt(ex * ex + ez * ez);
+                ux = -ez * s; uy = 0.0; uz = ex * s;
+            } else {
+                const double s = 1.0 / sqrt(ey * ey + ez * ez);
+                ux = 0.0; uy = ez * s; uz = -ey * s;
+            }
+            const double wx = ey * uz - ez * uy, wy = ez * ux - ex * uz, wz = ex * uy - ey * ux;
+            const double aux = a00 * ux + a01 * uy + a02 * uz, auy = a01 * ux + a11 * uy + a12 * uz, auz = a02 * ux + a12 * uy + a22 * uz;
+            const double awx = a00 * wx + a01 * wy + a02 * wz, awy = a01 * wx + a11 * wy + a12 * wz, awz = a02 * wx + a12 * wy + a22 * wz;
+            const double m00 = ux * aux + uy * auy + uz * auz, m01 = wx * aux + wy * auy + wz * auz, m11 = wx * awx + wy * awy + wz * awz;
+            // the smaller eigenvalue of (m00 m01; m01 m11) is (m00 + m11) / 2 - h; its eigenvector is orthogonal to the row of M - lambda I whose
+            // diagonal entry, hd + h or h - hd, is a sum of two non-negative numbers
+            const double hd = 0.5 * (m00 - m11), h = sqrt(hd * hd + m01 * m01);
+            double c = 1.0, s = 0.0;
+            if (h > 0.0) {
+                if (hd >= 0.0) { c = -m01; s = hd + h; }
+                else { c = h - hd; s = -m01; }
+            }
+            const double tx = c * ux + s * wx, ty = c * uy + s * wy, tz = c * uz + s * wz;
+            const double t = 1.0 / sqrt(tx * tx + ty * ty + tz * tz);
+            nx = tx * t; ny = ty * t; nz = tz * t;
+            return;
+        }
         lam = q + 2.0 * p * cos(phi + 2.0943951023931954923);      // the smallest eigenvalue
     }
-    // rows of A - lam I; the eigenvector is orthogonal to all of them: the largest of the three cross products
-    const double r0x = a00 - lam, r0y = a01, r0z = a02, r1x = a01, r1y = a11 - lam, r1z = a12, r2x = a02, r2y = a12, r2z = a22 - lam;
-    const double ax = r0y * r1z - r0z * r1y, ay = r0z * r1x - r0x * r1z, az = r0x * r1y - r0y * r1x;
-    const double bx = r0y * r2z - r0z * r2y, by = r0z * r2x - r0x * r2z, bz = r0x * r2y - r0y * r2x;
-    const double cx = r1y * r2z - r1z * r2y, cy = r1z * r2x - r1x * r2z, cz = r1x * r2y - r1y * r2x;
-    const double la = ax * ax + ay * ay + az * az, lb = bx * bx + by * by + bz * bz, lc = cx * cx + cy * cy + cz * cz;
-    double vx = ax, vy = ay, vz = az, l = la;
-    if (lb > l) { vx = bx; vy = by; vz = bz; l = lb; }
-    if (lc > l) { vx = cx; vy = cy; vz = cz; l = lc; }
-    if (l > 0.0) {
-        const double s = 1.0 / sqrt(l);
-        nx = vx * s; ny = vy * s; nz = vz * s;
-    } else {                                                       // isotropic neighbourhood: no direction is preferred
+    if (!null_direction(a00, a01, a02, a11, a12, a22, lam, nx, ny, nz)) {      // isotropic neighbourhood: no direction is preferred
         nx = 0.0; ny = 0.0; nz = 1.0;
     }
 }
@@ -724,6 +763,31 @@ static size_t carve_recon(ReconWs& w, void* base, int N, int depth) {
     return c.off + 256;
 }
 
+// the front half of pdhip_surface_recon, which pdhip_debug_surface_recon_rhs runs alone: the box, the grid, the splat radius, the cell list, the
+// sample weights and the right-hand side in w.f
+static int recon_rhs(const char* who, const float* points, const float* normals, int N, int depth, ReconWs& w, Grid& G, CellGrid& g, float& R,
+                     hipStream_t s) {
+    Box b;
+    int rc = cloud_box(who, points, N, w.cells.mom, s, b);
+    if (rc) return rc;
+    // grid: 2^depth cells per axis, the cloud's bounding cube in the middle with 2^depth / 8 cells of margin on every side
+    const int Gc = 1 << depth, M = Gc + 1, margin = Gc / 8;
+    G.M = M;
+    G.h = (float)(b.ext / (double)(Gc - 2 * margin));
+    G.ox = (float)(0.5 * (b.mn[0] + b.mx[0]) - 0.5 * Gc * (double)G.h);
+    G.oy = (float)(0.5 * (b.mn[1] + b.mx[1]) - 0.5 * Gc * (double)G.h);
+    G.oz = (float)(0.5 * (b.mn[2] + b.mx[2]) - 0.5 * Gc * (double)G.h);
+    // support radius of the splat: 2.5 cells, but not below ~2.3 sample spacings of a surface of area ext^2 * 3
+    R = (float)std::max(2.5 * (double)G.h, 4.0 * b.ext / sqrt((double)N));
+    rc = build_cells(w.cells, points, N, b, (double)R, CELLS_MAX, g, s);
+    if (rc) return rc;
+    const long long n3 = (long long)M * M * M;
+    k_sr_sample_weights<<<cdiv(N, TB), TB, 0, s>>>(w.cells.spos, w.cells.cstart, g, N, 1.0f / (R * R), normals, w.snrm);
+    k_sr_rhs<<<cdiv(n3, TB), TB, 0, s>>>(w.cells.spos, w.snrm, w.cells.cstart, g, G, R, w.f);
+    PD_LAUNCH_CHECK();
+    return PDHIP_OK;
+}
+
 }  // namespace
 
 extern "C" size_t pdhip_estimate_normals_ws_bytes(int N, int k, int n_eyes) {
@@ -788,29 +852,17 @@ extern "C" int pdhip_surface_recon(const float* points, const float* normals, co
     hipStream_t s = as_stream(stream);
     ReconWs w;
     carve_recon(w, ws, N, depth);
-    Box b;
-    int rc = cloud_box("pdhip_surface_recon", points, N, w.cells.mom, s, b);
-    if (rc) return rc;
-    // grid: 2^depth cells per axis, the cloud's bounding cube in the middle with 2^depth / 8 cells of margin on every side
-    const int Gc = 1 << depth, M = Gc + 1, margin = Gc / 8;
     Grid G;
-    G.M = M;
-    G.h = (float)(b.ext / (double)(Gc - 2 * margin));
-    G.ox = (float)(0.5 * (b.mn[0] + b.mx[0]) - 0.5 * Gc * (double)G.h);
-    G.oy = (float)(0.5 * (b.mn[1] + b.mx[1]) - 0.5 * Gc * (double)G.h);
-    G.oz = (float)(0.5 * (b.mn[2] + b.mx[2]) - 0.5 * Gc * (double)G.h);
-    // support radius of the splat: 2.5 cells, but not below ~2.3 sample spacings of a surface of area ext^2 * 3
-    const float R = (float)std::max(2.5 * (double)G.h, 4.0 * b.ext / sqrt((double)N));
     CellGrid g;
-    rc = build_cells(w.cells, points, N, b, (double)R, CELLS_MAX, g, s);
+    float R;
+    int rc = recon_rhs("pdhip_surface_recon", points, normals, N, depth, w, G, g, R, s);
     if (rc) return rc;
+    const int Gc = 1 << depth, M = G.M;
     const long long n3 = (long long)M * M * M;
     const int gN3 = cdiv(n3, TB);
     PD_HIP(hipMemsetAsync(w.misc, 0, M_WORDS * sizeof(int), s));
     PD_HIP(hipMemsetAsync(w.p, 0, (size_t)n3 * sizeof(float), s));
     PD_HIP(hipMemsetAsync(w.q, 0, (size_t)n3 * sizeof(float), s));
-    k_sr_sample_weights<<<cdiv(N, TB), TB, 0, s>>>(w.cells.spos, w.cells.cstart, g, N, 1.0f / (R * R), normals, w.snrm);
-    k_sr_rhs<<<gN3, TB, 0, s>>>(w.cells.spos, w.snrm, w.cells.cstart, g, G, R, w.f);
     k_sr_cg_init<<<CG_NB, CG_T, 0, s>>>(w.f, w.chi, w.r, n3, w.part_ff, w.part_rr[0]);
     PD_LAUNCH_CHECK();
     const int cap = 24 * Gc;
@@ -867,5 +919,55 @@ extern "C" int pdhip_surface_recon(const float* points, const float* normals, co
         k_sr_nearest_color<<<cdiv(hm[M_NV], TB), TB, 0, s>>>(vertices, hm[M_NV], w.cells.spos, w.cells.cstart, g, colors, vertex_colors);
         PD_LAUNCH_CHECK();
     }
+    return PDHIP_OK;
+}
+
+// ---- test hooks (include/pdhip.h): where the stages' intermediates lie in the caller's workspace, and the right-hand side, which the solve overwrites.
+// (A Carve on a null base hands out null pointers, so the layouts are carved on an address that is never dereferenced and subtracted again.)
+static char* const LAYOUT_BASE = reinterpret_cast<char*>((uintptr_t)1 << 20);
+static uint64_t layout_offset(const void* p) { return (uint64_t)(static_cast<const char*>(p) - LAYOUT_BASE); }
+
+extern "C" int pdhip_debug_estimate_normals_layout(int N, int k, int n_eyes, uint64_t* off) {
+    PD_REQUIRE(off, "pdhip_debug_estimate_normals_layout: null pointer");
+    PD_REQUIRE(pdhip_estimate_normals_ws_bytes(N, k, n_eyes) > 0, "pdhip_debug_estimate_normals_layout: N=%d k=%d n_eyes=%d: not a size "
+               "pdhip_estimate_normals accepts", N, k, n_eyes);
+    NormWs w;
+    const size_t total = carve_norm(w, LAYOUT_BASE, N, k, n_eyes);
+    const void* at[5] = {w.cells.cstart, w.cells.spos, w.knn, w.eyes, w.vis};
+    for (int i = 0; i < 5; ++i) off[i] = layout_offset(at[i]);
+    off[5] = (uint64_t)total;
+    return PDHIP_OK;
+}
+
+extern "C" int pdhip_debug_surface_recon_layout(int N, int depth, uint64_t* off) {
+    PD_REQUIRE(off, "pdhip_debug_surface_recon_layout: null pointer");
+    PD_REQUIRE(pdhip_surface_recon_ws_bytes(N, depth) > 0, "pdhip_debug_surface_recon_layout: N=%d depth=%d: not a size pdhip_surface_recon "
+               "accepts", N, depth);
+    ReconWs w;
+    const size_t total = carve_recon(w, LAYOUT_BASE, N, depth);
+    const void* at[7] = {w.cells.cstart, w.cells.spos, w.snrm, w.chi, w.eflag, w.misc, w.f};
+    for (int i = 0; i < 7; ++i) off[i] = layout_offset(at[i]);
+    off[7] = (uint64_t)total;
+    return PDHIP_OK;
+}
+
+extern "C" int pdhip_debug_surface_recon_rhs(const float* points, const float* normals, int N, int depth, float* f_out, float* info, void* ws,
+                                             void* stream) {
+    PD_REQUIRE(points && normals && f_out && info && ws, "pdhip_debug_surface_recon_rhs: null pointer");
+    PD_REQUIRE(N >= 16 && N <= (1 << 24), "pdhip_debug_surface_recon_rhs: N=%d points, need 16 .. 2^24", N);
+    PD_REQUIRE(depth >= 6 && depth <= 8, "pdhip_debug_surface_recon_rhs: depth=%d, the dense grid supports 6 .. 8", depth);
+    hipStream_t s = as_stream(stream);
+    ReconWs w;
+    carve_recon(w, ws, N, depth);
+    Grid G;
+    CellGrid g;
+    float R;
+    const int rc = recon_rhs("pdhip_debug_surface_recon_rhs", points, normals, N, depth, w, G, g, R, s);
+    if (rc) return rc;
+    const size_t n3 = (size_t)G.M * G.M * G.M;
+    const float hi[8] = {G.h, G.ox, G.oy, G.oz, g.cs, (float)g.C, R, (float)G.M};
+    PD_HIP(hipMemcpyAsync(f_out, w.f, n3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    PD_HIP(hipMemcpyAsync(info, hi, sizeof(hi), hipMemcpyHostToDevice, s));
+    PD_HIP(hipStreamSynchronize(s));                              // (hi lives on this frame)
     return PDHIP_OK;
 }
