@@ -612,6 +612,13 @@ int pdhip_conv_rr_f16(const void* x, const void* x2, int C, int Ca, int gn_mode,
                       float* ws, long long ws_floats, float* gn_part, int* gn_chunks, void* stream);
 long long pdhip_conv_rr_weight_halfs(int Cin, int taps, int Cs, int Cout);
 int pdhip_conv_rr_pack_f16(const void* w_packed, int Cin, int taps, int Cs, int Cout, void* wf, void* stream);
+/* host-only: the largest number of GroupNorm(32) groups one staged unit of cs channels (128 or 256, by tile variant) of a C-channel source touches -- what
+ * the kernel's in-staging statistics compute per unit; *capacity (may be NULL) = the groups the variant's statistics tables serve.  A source is accepted
+ * with gn_mode != 0 only where the first does not exceed the second; 0 = not a channel count the kernel's group arithmetic serves. */
+int pdhip_conv_rr_gn_groups_max(int cs, int C, int* capacity);
+/* host-only: the plan pdhip_conv_rr_f16 would launch under the debug hooks in force: plan[7] = variant, conv slabs, units per slab, skip slabs, units per
+ * skip slab, pixel bands per image, channel tiles; returns the variant (0: not a layer for the row-resident kernel). */
+int pdhip_conv_rr_plan(int N, int H, int W, int Cin, int Cout, int taps, int Cs, long long ws_floats, int want_gn, int* plan);
 /* test helpers: octet partials of a tensor as a conv epilogue leaves them; the two-pass reference of the fused input transform (k_gn_apply with in-kernel statistics) */
 int pdhip_gn_octet_partials_f16(const void* x, int N, int HW, int C, int chunks, float* part, void* stream);
 int pdhip_gn_apply_parts_f16(const void* x, const void* x2, int Ca, int C, const float* partA, int chunksA, const float* partB, int chunksB, const float* gamma,

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include <hip/hip_fp16.h>
+#include <algorithm>
 
 namespace pdnn {
 
@@ -146,6 +147,23 @@ int conv_rr_pack(const half_t* w_packed, int Cin, int taps, int Cs, int Cout, ha
 int conv_rr(const RrPlan& pl, const RrIn& in, const RrIn* skip, int taps, const half_t* wf, const float* bias, const half_t* residual, int res_up,
             half_t* Y, int N, int H, int W, int Cout, float* ws, size_t ws_floats, float* gn_part /*pl.bands chunks per image*/, hipStream_t s);
 #define PD_RR_MAX_PART_LOADS 8    // octet-partial loads per thread of the in-kernel statistics: chunks / slots of a source must not exceed it
+// The in-staging GroupNorm finishes the statistics of the groups ONE staged unit (cs channels) touches in two LDS tables of RrCfg::GN_ROWS = cs / 8 + 1 rows
+// (8-channel groups at least, + 1 for a group that straddles into the unit), eight statistics threads per group: 256 threads serve at most 32 groups.
+constexpr int rr_gn_groups_cap(int cs) { return cs / 8 + 1 < 32 ? cs / 8 + 1 : 32; }
+// The largest group count of a unit of a C-channel GroupNorm(32) source: the kernel's own `ng` expression (k_conv_rr, issue_stats) over the units
+// c0 = 0, cs, 2 cs, ... < C.  0 = not a source the kernel's magic division serves.  The plan, the launcher and the engine's wish all ask this one function.
+inline int rr_gn_groups_max(int cs, int C) {
+    if (cs <= 0 || C < 32 || C > 4096 || C % 32 != 0) return 0;
+    const int cg = C / 32, mg = ((1 << 20) + cg - 1) / cg;           // (c0 + cs - 1 < 8192, mg <= 2^20: the products need 64 bits only where C % cs != 0)
+    int worst = 0;
+    for (int c0 = 0; c0 < C; c0 += cs) {
+        const int g_first = (int)(((long long)c0 * mg) >> 20), ng = (int)(((long long)(c0 + cs - 1) * mg) >> 20) - g_first + 1;
+        worst = std::max(worst, ng);
+    }
+    return worst;
+}
+// channels per staged unit of the variant conv_rr_plan(..., want_gn) would take for W-wide images under t's hooks (0: no variant with the in-staging GroupNorm)
+int conv_rr_gn_unit(const Tuning& t, int W);
 
 // ---- 3x3 conv on 256-pixel x 64-channel halo tiles, K unsplit (nn_conv_ht.hip): the 64^2 / 128^2 levels at batch 1-2
 bool conv_ht_routes(const Tuning& t, int N, int H, int W, int Cin, int Cout, int Cout_pad, size_t ws_floats);

@@ -114,12 +114,17 @@ struct RrCfg {
     static constexpr int CS_LD = NF * 16 + 8;
     static constexpr int EPI_BYTES = MT * 16 * CS_LD * 2;
     static constexpr int MAIN_BYTES = ACT_BYTES > PARK_BYTES ? (ACT_BYTES > EPI_BYTES ? ACT_BYTES : EPI_BYTES) : (PARK_BYTES > EPI_BYTES ? PARK_BYTES : EPI_BYTES);
-    static constexpr int FIN_OFF = (MAIN_BYTES + 255) & ~255;                // double2 s_fin[17][8]
-    static constexpr int ST_OFF = FIN_OFF + 17 * 8 * 16;                      // float s_st[17][2]
-    static constexpr int FLAG_OFF = ST_OFF + 17 * 8;
+    // statistics tables of the in-staging GroupNorm: one row per group a unit can touch (groups hold 8 channels at least, + 1 for a group that
+    // straddles into the unit); GN_MAX of them can be served, by eight statistics threads each.  The host admits a source by
+    // rr_gn_groups_max(CS, C) <= rr_gn_groups_cap(CS) (nn_common.h) -- the same two numbers
+    static constexpr int GN_ROWS = CS / 8 + 1, GN_MAX = GN_ROWS < 32 ? GN_ROWS : 32;
+    static constexpr int FIN_OFF = (MAIN_BYTES + 255) & ~255;                // double2 s_fin[GN_ROWS][8]
+    static constexpr int ST_OFF = FIN_OFF + GN_ROWS * 8 * 16;                 // float s_st[GN_ROWS][2]
+    static constexpr int FLAG_OFF = ST_OFF + GN_ROWS * 8;
     static constexpr int SMEM = FLAG_OFF + 16;
     static_assert(MT * 16 % W == 0 && (ROWS * W) % PXI == 0 && CS % 128 == 0 && F % 4 == 0, "tile geometry");
     static_assert(W != 8 || MT == 4, "8-wide images: the whole image per workgroup");
+    static_assert(8 * GN_MAX <= 256 && GN_MAX <= GN_ROWS, "eight statistics threads per group, every served group has a table row");
     static_assert(SMEM <= 160 * 1024, "LDS budget");
 };
 
@@ -545,6 +550,7 @@ __global__ __launch_bounds__(256) void k_conv_rr(const RrArgs a) {
 template <int W, int MT, int NF, int CS, bool GNF = true>
 int launch_rr(const RrArgs& a, int grid, hipStream_t s) {
     using G = RrCfg<W, MT, NF, CS>;
+    static_assert(G::GN_MAX == rr_gn_groups_cap(CS), "the host admits GroupNorm sources by the kernel's own table size");
     PD_REQUIRE(GNF || (a.src[0].gn == 0 && a.src[1].gn == 0), "conv_rr: this tile variant has no in-staging GroupNorm");
     auto kern = k_conv_rr<W, MT, NF, CS, GNF>;
     if (G::SMEM > 65536) PD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::SMEM));
@@ -602,21 +608,36 @@ static bool rr_variant(int v, int* w, int* mt, int* nf, int* cs) {
     }
     return false;
 }
+// Candidate tile variants of the image width, smallest channel tile first, 0-terminated (nullptr: not a width of this kernel).  Rule read off
+// tools/bench_rr.py (profiles/r06_rr_bench_standalone.txt): the variant whose tiles come closest to one workgroup per CU with the FEWEST K slabs
+// wins -- every slab beyond the first costs a write-through publish, a ticket round trip and a re-read of the slices by the last arriver
+// (~4 us of a 10 us launch).
+static const int* rr_candidates(int W) {
+    static const int cand8[] = {1, 0}, cand16[] = {7, 2, 0}, cand32[] = {6, 3, 0}, cand64[] = {8, 0};
+    return W == 8 ? cand8 : W == 16 ? cand16 : W == 32 ? cand32 : W == 64 ? cand64 : nullptr;
+}
+static bool rr_variant_has_gn(int v) { return v == 1 || v == 2 || v == 3 || v == 5; }     // (6, 7, 8: compiled without the in-staging GroupNorm)
+// does one staged unit of a C-channel GroupNorm source fit the kernel's statistics tables?
+static bool rr_gn_fits(int cs, int C) { const int ng = rr_gn_groups_max(cs, C); return ng > 0 && ng <= rr_gn_groups_cap(cs); }
+int conv_rr_gn_unit(const Tuning& t, int W) {
+    int w = 0, mt = 0, nf = 0, cs = 0;
+    if (t.rr_variant != 0) return rr_variant(t.rr_variant, &w, &mt, &nf, &cs) && w == W && rr_variant_has_gn(t.rr_variant) ? cs : 0;
+    const int* cand = rr_candidates(W);
+    for (int k = 0; cand != nullptr && cand[k] != 0; ++k)
+        if (rr_variant_has_gn(cand[k]) && rr_variant(cand[k], &w, &mt, &nf, &cs)) return cs;      // (one such candidate per width)
+    return 0;
+}
 RrPlan conv_rr_plan(const Tuning& t, int N, int H, int W, int Cin, int Cout, int taps, int Cs, size_t ws_floats, bool want_gn) {
     RrPlan p{0, 0, 0, 0, 0, 0, 0};
     if (t.rr_mode == 0 || H != W || (taps != 9 && taps != 1)) return p;
-    // Candidate tile variants of the image width, smallest channel tile first.  Rule read off tools/bench_rr.py (profiles/r06_rr_bench_standalone.txt):
-    // the variant whose tiles come closest to one workgroup per CU with the FEWEST K slabs wins -- every slab beyond the first costs a
-    // write-through publish, a ticket round trip and a re-read of the slices by the last arriver (~4 us of a 10 us launch).
-    static const int cand8[] = {1, 0}, cand16[] = {7, 2, 0}, cand32[] = {6, 3, 0}, cand64[] = {8, 0};
-    const int* cand = W == 8 ? cand8 : W == 16 ? cand16 : W == 32 ? cand32 : W == 64 ? cand64 : nullptr;
+    const int* cand = rr_candidates(W);
     if (cand == nullptr) return p;
     int v = t.rr_variant, vw = 0, mt = 0, nf = 0, cs = 0;
     if (v == 0) {
         for (int k = 0; cand[k] != 0; ++k) {
             int w_, mt_, nf_, cs_;
             rr_variant(cand[k], &w_, &mt_, &nf_, &cs_);
-            if (want_gn && (cand[k] == 6 || cand[k] == 7 || cand[k] >= 8)) continue;      // (the variants without the in-staging GroupNorm)
+            if (want_gn && (!rr_variant_has_gn(cand[k]) || !rr_gn_fits(cs_, Cin))) continue;   // (no in-staging GroupNorm, or a unit with more groups than its tables hold)
             if (Cin % cs_ != 0 || Cs % cs_ != 0 || Cout % (nf_ * 16) != 0) continue;
             v = cand[k];
             if ((long long)N * (H * W / (mt_ * 16)) * (Cout / (nf_ * 16)) <= 256) break;        // fits one round of workgroups: take it; else try the next (larger) tile
@@ -624,6 +645,7 @@ RrPlan conv_rr_plan(const Tuning& t, int N, int H, int W, int Cin, int Cout, int
     }
     if (!rr_variant(v, &vw, &mt, &nf, &cs) || vw != W) return p;
     if (Cin % cs != 0 || Cs % cs != 0 || Cout % (nf * 16) != 0) return p;
+    if (want_gn && rr_variant_has_gn(v) && !rr_gn_fits(cs, Cin)) return p;      // (a forced variant included; one without the path at all is refused by its launcher, by name)
     const int bands = H * W / (mt * 16);
     const int ntiles = Cout / (nf * 16);
     const long long tiles = (long long)N * bands * ntiles;
@@ -691,6 +713,10 @@ int conv_rr(const RrPlan& pl, const RrIn& in, const RrIn* skip, int taps, const 
     PD_REQUIRE(S == 1 || (ws != nullptr && (size_t)tiles * S * mt * nf * 256 + PD_SK_TICKET_FLOATS <= ws_floats), "conv_rr: split-K workspace too small");
     PD_REQUIRE(in.C % cs == 0 && (in.x2 == nullptr || in.Ca % cs == 0) && (!skip || (skip->C % cs == 0 && (skip->x2 == nullptr || skip->Ca % cs == 0))),
                "conv_rr: channel counts must be multiples of the unit size");
+    for (const RrIn* i : {&in, skip})
+        if (i != nullptr && i->gn != 0 && rr_variant_has_gn(pl.variant))
+            PD_REQUIRE(rr_gn_fits(cs, i->C), "conv_rr: a %d-channel unit of this %d-channel GroupNorm input touches %d groups, variant %d's statistics tables hold %d",
+                       cs, i->C, rr_gn_groups_max(cs, i->C), pl.variant, rr_gn_groups_cap(cs));
     switch (pl.variant) {
         case 1: return launch_rr<8, 4, 1, 256>(a, grid, s);
         case 2: return launch_rr<16, 8, 2, 128>(a, grid, s);
@@ -732,6 +758,15 @@ __global__ void k_gn_octet_partials(const pdnn::half_t* __restrict__ X, int HW, 
 extern "C" int pdhip_lab_rr_read_stamps(unsigned long long* host, int n) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(pdnn::g_rr_stamps), sizeof(unsigned long long) * n); }
 #endif
 extern "C" long long pdhip_conv_rr_weight_halfs(int Cin, int taps, int Cs, int Cout) { return (long long)pdnn::conv_rr_weight_halfs(Cin, taps, Cs, Cout); }
+extern "C" int pdhip_conv_rr_gn_groups_max(int cs, int C, int* capacity) {
+    if (capacity) *capacity = pdnn::rr_gn_groups_cap(cs);
+    return pdnn::rr_gn_groups_max(cs, C);
+}
+extern "C" int pdhip_conv_rr_plan(int N, int H, int W, int Cin, int Cout, int taps, int Cs, long long ws_floats, int want_gn, int* plan) {
+    const pdnn::RrPlan pl = pdnn::conv_rr_plan(pdnn::tuning(), N, H, W, Cin, Cout, taps, Cs, ws_floats > 0 ? (size_t)ws_floats : 0, want_gn != 0);
+    if (plan) { plan[0] = pl.variant; plan[1] = pl.S0; plan[2] = pl.U0; plan[3] = pl.S1; plan[4] = pl.U1; plan[5] = pl.bands; plan[6] = pl.ntiles; }
+    return pl.variant;
+}
 extern "C" int pdhip_conv_rr_pack_f16(const void* w_packed, int Cin, int taps, int Cs, int Cout, void* wf, void* stream) {
     PD_REQUIRE(w_packed && wf, "pdhip_conv_rr_pack_f16: null argument");
     return pdnn::conv_rr_pack((const pdnn::half_t*)w_packed, Cin, taps, Cs, Cout, (pdnn::half_t*)wf, as_stream(stream));

@@ -324,6 +324,8 @@ struct ResPlan {
 bool wish_in_gn(const Tuning& t, const Act& x, const ConvW& w, int W) {
     if (t.rr_gn <= 0 || W > t.rr_gn || x.p2 != nullptr || x.gn_part == nullptr || x.gn_partB != nullptr || ((x.C / 32) % 8) != 0 || w.cin > 1024 ||
         x.C != w.cin) return false;
+    const int cs = conv_rr_gn_unit(t, W);                // a unit of the variant the plan would take must fit that variant's statistics tables
+    if (cs == 0 || rr_gn_groups_max(cs, x.C) > rr_gn_groups_cap(cs)) return false;
     const int pps = std::max(1, 256 / (x.C >> 3));
     return (x.gn_chunks + pps - 1) / pps <= PD_RR_MAX_PART_LOADS;
 }

@@ -71,6 +71,8 @@ _reg('pdhip_unet_route_table', C.c_int, [i32, i32, i32, C.POINTER(C.c_int), i32,
 _reg('pdhip_conv_ht_f16', C.c_int, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, C.c_longlong, vp, C.POINTER(C.c_int), vp])
 _reg('pdhip_conv_rr_weight_halfs', C.c_longlong, [i32, i32, i32, i32])
 _reg('pdhip_conv_rr_pack_f16', C.c_int, [vp, i32, i32, i32, i32, vp, vp])
+_reg('pdhip_conv_rr_gn_groups_max', C.c_int, [i32, i32, C.POINTER(C.c_int)])
+_reg('pdhip_conv_rr_plan', C.c_int, [i32, i32, i32, i32, i32, i32, i32, C.c_longlong, i32, C.POINTER(C.c_int)])
 _reg('pdhip_gn_octet_partials_f16', C.c_int, [vp, i32, i32, i32, i32, vp, vp])
 _reg('pdhip_gn_apply_parts_f16', C.c_int, [vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, C.c_longlong, i32, i32, i32, i32, vp, vp])
 _reg('pdhip_conv_rr_f16', C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, C.c_longlong, vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp,

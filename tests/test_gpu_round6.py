@@ -89,6 +89,9 @@ CASES = [
     (1, 32, 512, 256, 512, 2, False, None, 0, 16, 4, 0, 0),         # 32^2 decoder conv1 over a 768-channel concat (24 per group), 16 producer chunks
     (1, 32, 512, 0, 512, 2, True, (512, 256), 0, 4, 0, 0, 0),       # 32^2 decoder conv2 + skip
     (3, 32, 128, 0, 64, 0, False, None, 2, 0, 0, 0, 0),             # raw, batch 3, half-resolution residual
+    # (new rows go at the end: pytest numbers the skip tuples of the ids by row)
+    (1, 8, 256, 0, 512, 1, False, None, 0, 1, 0, 0, 0),             # GroupNorm at 8^2 / 256 channels on the automatic selection: variant 1, whose one 256-channel unit holds all 32 groups
+    (1, 8, 256, 0, 512, 2, True, None, 0, 1, 0, 0, 0),              # ... with SiLU and FiLM
 ]
 
 
@@ -149,7 +152,8 @@ def test_conv_rr_vs_torch_fp32_and_two_pass_form(nn, N, HW, Ca, Cb, Cout, gn, fi
     ws = torch.zeros((4096 + 4 * 1024 * 1024,), dtype=torch.float32, device=DEV)
     bdv = b.to(DEV)
     if gn and variant == 0:
-        variant = {8: 1, 16: 2, 32: 3}[HW]                 # (the two-pass comparison below must run the SAME tile variant: the raw-input form would pick the 16-channel tiles)
+        variant = {8: 0, 16: 2, 32: 3}[HW]                 # (the two-pass comparison below must run the SAME tile variant: the raw-input form would pick the 16-channel tiles;
+                                                           # at 8^2 both forms select variant 1 by themselves -- the automatic route stays automatic)
     old = L.pdhip_debug_set_conv_rr(2, variant, slabs)
     try:
         y1, p1, ch = _rr(L, xa, xb, gn, gd, bd, fd, parts, xsa, xsb, 9, wf, bdv, rd, 1 if res == 2 else 0, N, H, W, Cout, ws)
