@@ -388,6 +388,20 @@ int pdhip_texel_visibility(const float* cam_params, int V, const float* gb_pos /
  *      out[K,V,A,A] u8.  ws: 2*V*A*A bytes. */
 int pdhip_nbf_shrink(const uint8_t* mask /*[A,A]*/, const uint8_t* visibility /*[V,A,A]*/, int V, int A,
                      const int32_t* kernels, int K, uint8_t* out, uint8_t* ws, void* stream);
+/* The path pdhip_nbf_shrink / pdhip_nbf_shrink_shapes take for V views in all (S * V for the shapes entry): host only, no device work, and the
+ * very function the launcher routes through.  BYTES: one byte per texel, any A, V, radius and alignment.  BITS_*: 64 texels per word --
+ * A % 64 == 0, A <= 4096, V >= 2, every radius (k - 1) / 2 < 64, (32 + k - 1) * (A / 64) * 16 <= 65536 bytes of LDS, out 16-byte and ws
+ * 8-byte aligned; PACK16 packs with 16-byte loads (mask and visibility 16-byte aligned), BALLOT byte by byte.  COPY: kernels[0] == 0.
+ * align_mask: bits 0-3 = low 4 address bits of (mask | visibility), bits 4-7 = low 4 address bits of out, bits 8-10 = low 3 address bits of ws.
+ * PDHIP_E_ARG: sizes not positive, an even kernel size, or a bit path forced where it is not eligible. */
+#define PDHIP_NBF_BYTES 0
+#define PDHIP_NBF_BITS_PACK16 1
+#define PDHIP_NBF_BITS_BALLOT 2
+#define PDHIP_NBF_COPY 3
+int pdhip_nbf_path(int V, int A, const int32_t* kernels, int K, unsigned align_mask);
+/* test hook: 0 (default) = automatic, 1 = the byte path, 2 = the bit path with the ballot packer; a forced bit path that is not eligible is
+ * refused by the launcher (PDHIP_E_ARG), never launched.  Returns the previous value; thread-local. */
+int pdhip_debug_set_nbf_path(int mode);
 /* Bit-packed transport of boolean texel maps (no reference counterpart: the reference is single-GPU; SURVEY 8(e) prices the view-parallel
  * all-gather record with its visibility maps bit-packed): bit i of out word w = (in[64 w + i] != 0); n % 64 == 0; 16-byte aligned byte side. */
 int pdhip_pack_bits(const uint8_t* in /*[n] 0 / non-0*/, long long n, uint64_t* out /*[n / 64]*/, void* stream);

@@ -288,6 +288,34 @@ __global__ __launch_bounds__(256) void k_nbf_bits(const unsigned long long* __re
     }
 }
 
+// ---- which of its paths the launcher takes (host only; nbf_impl routes through this very function).
+//   bytes         k_nbf_edges / k_nbf_dilate_h / k_nbf_dilate_v_shrink, one byte per texel: any A, V, radius and alignment
+//   bits + pack16 k_pack_bits16 + k_nbf_bits: A % 64 == 0, A <= 4096, V >= 2, every radius < 64, both LDS bitmaps of a 32-row band
+//                 within 64 KiB, out 16-byte aligned (uint4 stores), ws 8-byte aligned (64-bit words), mask and visibility 16-byte aligned
+//   bits + ballot the same with k_pack_bits reading bytes: mask or visibility not 16-byte aligned
+//   copy          kernels[0] == 0: NBF off, out = visibility
+// align_mask: bits 0-3 = low 4 address bits of (mask | visibility), bits 4-7 = low 4 address bits of out, bits 8-10 = low 3 of ws.
+static thread_local int g_nbf_path = 0;                 // test hook: 0 = auto, 1 = bytes, 2 = bits + ballot (refused where not eligible)
+extern "C" int pdhip_debug_set_nbf_path(int mode) { const int old = g_nbf_path; g_nbf_path = mode; return old; }
+static unsigned nbf_align_mask(const void* mask, const void* visibility, const void* out, const void* ws) {
+    return (unsigned)(((uintptr_t)mask | (uintptr_t)visibility) & 15) | (unsigned)((uintptr_t)out & 15) << 4 | (unsigned)((uintptr_t)ws & 7) << 8;
+}
+extern "C" int pdhip_nbf_path(int V, int A, const int32_t* kernels, int K, unsigned align_mask) {
+    PD_REQUIRE(V > 0 && A > 0 && K > 0 && kernels, "pdhip_nbf_shrink: bad sizes");
+    if (kernels[0] == 0) return PDHIP_NBF_COPY;      // NBF off (unproject.py:436-437): single level == raw visibility
+    for (int k = 0; k < K; ++k)
+        PD_REQUIRE(kernels[k] >= 1 && (kernels[k] & 1), "pdhip_nbf_shrink: kernel sizes must be odd and >= 1 (got %d)", kernels[k]);
+    bool bits_ok = (A % 64 == 0) && A <= 4096 && V >= 2;            // bitmaps live in the byte workspace: (V + 1) A^2 / 8 <= 2 V A^2
+    for (int k = 0; k < K; ++k) bits_ok = bits_ok && (kernels[k] - 1) / 2 < 64 && (size_t)(NBF_RB + kernels[k] - 1) * (A / 64) * 16 <= 64 * 1024;
+    bits_ok = bits_ok && (align_mask & 0x7f0u) == 0;                // uint4 stores to out, 64-bit words in ws
+    PD_REQUIRE(g_nbf_path >= 0 && g_nbf_path <= 2, "pdhip_debug_set_nbf_path: unknown mode %d", g_nbf_path);
+    PD_REQUIRE(g_nbf_path != 2 || bits_ok, "pdhip_nbf_shrink: the bit path was forced (pdhip_debug_set_nbf_path) but V=%d A=%d, the kernel sizes or "
+               "the alignment of out / ws do not admit it", V, A);
+    if (!bits_ok || g_nbf_path == 1) return PDHIP_NBF_BYTES;
+    // (A % 64 == 0: an image is A * A / 64 words, a multiple of 16 -- whole 16-byte groups, whole waves in one image)
+    return ((align_mask & 15u) == 0 && g_nbf_path == 0) ? PDHIP_NBF_BITS_PACK16 : PDHIP_NBF_BITS_BALLOT;
+}
+
 static int nbf_impl(const uint8_t* mask, const uint8_t* visibility, int V, int vps, int A, const int32_t* kernels, int K, uint8_t* out,
                     uint8_t* ws, void* stream);
 extern "C" int pdhip_nbf_shrink(const uint8_t* mask, const uint8_t* visibility, int V, int A, const int32_t* kernels,
@@ -308,23 +336,21 @@ static int nbf_impl(const uint8_t* mask, const uint8_t* visibility, int V, int v
     PD_REQUIRE(mask && visibility && out, "pdhip_nbf_shrink: null pointer");
     hipStream_t s = as_stream(stream);
     const size_t n = (size_t)V * A * A;
-    if (kernels[0] == 0) {                      // NBF off (unproject.py:436-437): single level == raw visibility
+    const int path = pdhip_nbf_path(V, A, kernels, K, nbf_align_mask(mask, visibility, out, ws));
+    if (path < 0) return path;
+    if (path == PDHIP_NBF_COPY) {
         PD_HIP(hipMemcpyAsync(out, visibility, n, hipMemcpyDeviceToDevice, s));
         return PDHIP_OK;
     }
     PD_REQUIRE(ws, "pdhip_nbf_shrink: workspace required");
-    for (int k = 0; k < K; ++k)
-        PD_REQUIRE(kernels[k] >= 1 && (kernels[k] & 1), "pdhip_nbf_shrink: kernel sizes must be odd and >= 1 (got %d)", kernels[k]);
     uint8_t* edges = ws;
     uint8_t* tmp = ws + n;
     dim3 g(min(cdiv((long long)A * A, 256), 2048), V);
-    bool bits_ok = (A % 64 == 0) && A <= 4096 && V >= 2;            // bitmaps live in the byte workspace: (V + 1) A^2 / 8 <= 2 V A^2
-    for (int k = 0; k < K; ++k) bits_ok = bits_ok && (kernels[k] - 1) / 2 < 64 && (size_t)(NBF_RB + kernels[k] - 1) * (A / 64) * 16 <= 64 * 1024;
-    if (bits_ok) {
+    if (path != PDHIP_NBF_BYTES) {
         unsigned long long* visb = reinterpret_cast<unsigned long long*>(ws);
         unsigned long long* maskb = visb + (size_t)V * A * (A / 64);
         const long long vw = (long long)V * A * (A / 64), mw = (long long)S * A * (A / 64);
-        if ((((uintptr_t)visibility | (uintptr_t)mask) & 15) == 0 && vw % 16 == 0 && mw % 16 == 0) {
+        if (path == PDHIP_NBF_BITS_PACK16) {
             k_pack_bits16<<<min(cdiv((vw + mw) * 4, 256), 4096), 256, 0, s>>>(visibility, vw * 4, visb, mask, mw * 4, maskb);
         } else {
             k_pack_bits<<<min(cdiv(vw * 64, 256), 4096), 256, 0, s>>>(visibility, vw, visb);

@@ -39,6 +39,12 @@ def test_argument_validation_sets_error_message():
     rc = L.pdhip_nearest_fill(None, None, 1, 3, 8, 8, 0, 0, 0, None, 0, 0, None, None)
     assert L.pdhip_nearest_fill_ws_ints(2, 256, 256) == 2 * 256 * 256 + 2 * 2 * 16 * 256      # near_row + first / last site per 16-row column segment
     assert rc == -1
+    # the NBF path query and its hook are host-only: 0 bytes, 1 bits + pack16, 2 bits + ballot, 3 copy (include/pdhip.h)
+    k = (ctypes.c_int32 * 2)(21, 11)
+    assert [L.pdhip_nbf_path(2, 128, k, 2, m) for m in (0, 0x1, 0x10, 0x100)] == [1, 2, 0, 0] and L.pdhip_nbf_path(2, 100, k, 2, 0) == 0
+    assert L.pdhip_nbf_path(2, 128, (ctypes.c_int32 * 1)(0), 1, 0) == 3
+    assert L.pdhip_nbf_path(2, 128, (ctypes.c_int32 * 1)(20), 1, 0) == -1 and b'odd' in L.pdhip_last_error()
+    assert L.pdhip_debug_set_nbf_path(1) == 0 and L.pdhip_nbf_path(2, 128, k, 2, 0) == 0 and L.pdhip_debug_set_nbf_path(0) == 1
 
 
 def test_product_has_no_cpu_path():
