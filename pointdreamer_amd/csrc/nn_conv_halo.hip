@@ -16,6 +16,7 @@
 // start pixel (the tap shift moves the 16-pixel fragment window by +-1), mirrored on the LDS-DMA source address.
 #include <type_traits>
 #include "nn_common.h"
+#include "nn_conv_tail.h"
 using namespace pdhip;
 namespace pdnn {
 namespace {
@@ -27,8 +28,6 @@ __device__ __forceinline__ void glds16h(const void* gsrc, void* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((gbl_void_h*)gsrc, (lds_void_h*)lds_wave_base, 16, 0, 0);
 #endif
 }
-__device__ __forceinline__ int swz_b(int row) { return (0x78 >> (2 * ((row >> 2) & 3))) & 3; }   // weight tile: aligned 16-row windows
-__device__ __forceinline__ int swz_a(int hp) { return ((hp >> 2) & 1) << 1; }                     // halo: any window start
 
 // WLOG: log2 of the TILE width; ILOG >= WLOG: log2 of the image width.  ILOG > WLOG: the image is cut into column strips of the
 // tile width (a 512-pixel tile = 8 rows x 64 columns instead of 2 rows x 256: 660 halo pixels per chunk instead of 1 032).
@@ -465,7 +464,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_halo(const half_t* __restrict__
             for (int j = 0; j < SUB; ++j) { s1 += red2[(tid * SUB + j) * 2]; q1 += red2[(tid * SUB + j) * 2 + 1]; }
             const int chunks = tpi;
             const int chunk = tin;
-            float* dst = gn_part + (((size_t)img * chunks + chunk) * (Cout >> 3) + (n0 >> 3) + tid) * 2;
+            float* dst = gn_part_slot(gn_part, img, chunks, chunk, Cout, n0, tid);
             dst[0] = s1; dst[1] = q1;
         }
     }

@@ -27,6 +27,7 @@
 // Same operand formats as the other conv kernels: NHWC f16 activations, weights [Cout_pad][9 * Cin] (k = tap * Cin + c), bias f32; output f16
 // NHWC (+ residual, optionally read at half resolution) + GroupNorm octet partials per 256-pixel tile.
 #include "nn_common.h"
+#include "nn_conv_tail.h"
 #include <algorithm>
 #include <type_traits>
 using namespace pdhip;
@@ -39,8 +40,6 @@ typedef const __attribute__((address_space(1))) void ht_gbl_void;
 __device__ __forceinline__ void ht_glds16(const void* gsrc, void* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((ht_gbl_void*)gsrc, (ht_lds_void*)lds_wave_base, 16, 0, 0);
 }
-__device__ __forceinline__ int ht_swz_b(int row) { return (0x78 >> (2 * ((row >> 2) & 3))) & 3; }   // weight slice: aligned 16-row windows
-__device__ __forceinline__ int ht_swz_a(int hp) { return ((hp >> 2) & 1) << 1; }                     // halo: any 16-pixel window
 #if defined(PD_LAB_HT_FILL) && (PD_LAB_HT_FILL == 7 || PD_LAB_HT_FILL == 8)     // (lab: no fragment reads)
 #define HT_DSR128(dst, addr, off) asm volatile("; no read %0 %1" : "=v"(dst) : "v"(addr))
 #else
@@ -51,10 +50,6 @@ __device__ __forceinline__ int ht_swz_a(int hp) { return ((hp >> 2) & 1) << 1; }
 #else
 #define HT_BARRIER() __builtin_amdgcn_s_barrier()
 #endif
-template <int B, int E, typename Fn>
-__device__ __forceinline__ void ht_static_for(Fn&& fn) {
-    if constexpr (B < E) { fn(std::integral_constant<int, B>{}); ht_static_for<B + 1, E>(fn); }
-}
 
 // WLOG: log2 of the image width (5, 6, 7).  grid: total tiles (1-D, XCD-aware), 512 threads: waves 0-3 multiply, waves 4-7 load.
 // (An LDS-DMA issue holds its wave's instruction slot for ~100-180 cycles; 17 of them in front of a wave's own MFMAs left the matrix pipe idle
@@ -111,10 +106,10 @@ __global__ __launch_bounds__(512) void k_conv_ht(const half_t* __restrict__ X, c
                 const int y = ty0 - 1 + hy, x = hx - 1;
                 const bool ok = (hp < HP) & (y >= 0) & (y < H) & (x >= 0) & (x < W);
                 const int spix = ((img * H + y) << WLOG) + x;
-                poff[k] = ok ? (uint32_t)((spix * Cin + ((cq ^ ht_swz_a(hp)) << 3)) * 2) : ~0u;
+                poff[k] = ok ? (uint32_t)((spix * Cin + ((cq ^ swz_a(hp)) << 3)) * 2) : ~0u;
             } else {
                 const int wq = q - NPA, t = wq >> 2, row = (wq & 3) * 16 + lq;         // tap, output channel inside the tile
-                poff[k] = (uint32_t)(((size_t)(n0 + row) * K + (size_t)t * Cin + ((cq ^ ht_swz_b(row)) << 3)) * 2);
+                poff[k] = (uint32_t)(((size_t)(n0 + row) * K + (size_t)t * Cin + ((cq ^ swz_b(row)) << 3)) * 2);
             }
         }
         const char* const Xb = reinterpret_cast<const char*>(X);
@@ -155,11 +150,11 @@ __global__ __launch_bounds__(512) void k_conv_ht(const half_t* __restrict__ X, c
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int p = wave * 64 + i * 16 + r16, hp = (p >> WLOG) * HW2 + (p & (W - 1)) + tx;
-                a0[tx * 4 + i] = (uint32_t)((hp << 6) + ((kg ^ ht_swz_a(hp)) << 4));
+                a0[tx * 4 + i] = (uint32_t)((hp << 6) + ((kg ^ swz_a(hp)) << 4));
             }
         const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) w0[j] = lds0 + (uint32_t)(NPA * 1024 + (j * 16 + r16) * 64 + ((kg ^ ht_swz_b(j * 16 + r16)) << 4));
+        for (int j = 0; j < 4; ++j) w0[j] = lds0 + (uint32_t)(NPA * 1024 + (j * 16 + r16) * 64 + ((kg ^ swz_b(j * 16 + r16)) << 4));
 #pragma unroll
         for (int k = 0; k < 12; ++k) a0[k] += lds0;
         half8 fa[2][4], fw[2][4];                                     // [tap parity][fragment]
@@ -224,7 +219,7 @@ __global__ __launch_bounds__(512) void k_conv_ht(const half_t* __restrict__ X, c
     }
     __syncthreads();                                                  // every fragment read is done: the buffers become the output staging
 
-    // ---- in-launch split-K combine (k_conv_sk's / k_conv_rr's protocol): every slab publishes its f32 accumulators write-through, drains, takes
+    // ---- in-launch split-K combine (splitk_last_arriver, nn_conv_tail.h): every slab publishes its f32 accumulators write-through, drains, takes
     // a ticket; the last arriver sums ALL slices in slab order -- its own included, so the order never depends on who is last -- and goes on
     if (S > 1) {
         constexpr int SLICE_BYTES = 16 * 4096;                        // 16 fragments x 256 lanes x 16 bytes
@@ -235,17 +230,7 @@ __global__ __launch_bounds__(512) void k_conv_ht(const half_t* __restrict__ X, c
             for (int f = 0; f < 16; ++f)
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ht_u4, acc[f >> 2][f & 3]), rs, slab * SLICE_BYTES + (f * 256 + tid) * 16, 0, /*sc1: write-through*/ 16);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        volatile int* flag = reinterpret_cast<volatile int*>(smem + 2 * BUF_BYTES);
-        if (tid == 0) {
-            const unsigned old = __hip_atomic_fetch_add(tickets + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int last = old == (unsigned)(S - 1);
-            if (last) __hip_atomic_store(tickets + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *flag = last;
-        }
-        __syncthreads();
-        if (*flag == 0) return;
+        if (!splitk_last_arriver(tickets, tile, S, tid, smem + 2 * BUF_BYTES)) return;
         if (wave < 4) {
 #pragma unroll
             for (int f = 0; f < 16; ++f) acc[f >> 2][f & 3] = (float4_t){0.f, 0.f, 0.f, 0.f};
@@ -324,7 +309,7 @@ __global__ __launch_bounds__(512) void k_conv_ht(const half_t* __restrict__ X, c
             float s1 = 0.f, q1 = 0.f;
 #pragma unroll
             for (int j = 0; j < SUB; ++j) { s1 += red2[(tid * SUB + j) * 2]; q1 += red2[(tid * SUB + j) * 2 + 1]; }
-            float* dst = gn_part + (((size_t)img * tpi + tin) * (Cout >> 3) + (n0 >> 3) + tid) * 2;
+            float* dst = gn_part_slot(gn_part, img, tpi, tin, Cout, n0, tid);
             dst[0] = s1; dst[1] = q1;
         }
     }
@@ -332,14 +317,14 @@ __global__ __launch_bounds__(512) void k_conv_ht(const half_t* __restrict__ X, c
 
 template <int WLOG>
 int launch_ht(const half_t* X, const half_t* Wt, const float* bias, const half_t* residual, half_t* Y, int N, int H, int Cin, int Cout, int Cout_pad,
-              const half_t* zero_page, float* gn_part, int res_up, int S, float* ws, hipStream_t s) {
+              const half_t* zero_page, float* gn_part, int res_up, int S, const SplitWs& ws, hipStream_t s) {
     constexpr int W = 1 << WLOG, RT = 256 / W, HP = (RT + 2) * ((W + 2 + 7) & ~7), NP = (HP + 15) / 16 + 36;
     constexpr int smem = 2 * NP * 1024 + 64;
     auto kern = k_conv_ht<WLOG>;
     PD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     const int n_tiles = Cout_pad / 64, total = (int)(((long long)N * H * W / 256) * n_tiles);
     kern<<<total * S, 512, smem, s>>>(X, Wt, bias, residual, Y, N, H, Cin, Cout, n_tiles, total, zero_page, gn_part, res_up, S,
-                                      ws ? ws + PD_SK_TICKET_FLOATS : nullptr, reinterpret_cast<unsigned*>(ws));
+                                      ws.payload, ws.tickets);
     PD_LAUNCH_CHECK();
     return PDHIP_OK;
 }
@@ -353,7 +338,7 @@ int launch_ht(const half_t* X, const half_t* Wt, const float* bias, const half_t
 int conv_ht_slabs(const Tuning& t, int N, int H, int W, int Cin, int Cout_pad, size_t ws_floats) {
     const long long tiles = ((long long)N * H * W / 256) * (Cout_pad / 64);
     const int nct = Cin >> 5;
-    auto fits = [&](int S) { return nct % S == 0 && tiles <= 4096 && (size_t)tiles * S * 16384 + PD_SK_TICKET_FLOATS <= ws_floats; };
+    auto fits = [&](int S) { return nct % S == 0 && split_fits(ws_floats, tiles, 16384, S); };
     if (t.ht_slabs > 0) return fits(t.ht_slabs) ? t.ht_slabs : 1;
     int S = 1;
     while (S < 4 && tiles * S * 2 <= 256 && nct / (S * 2) >= 8 && fits(S * 2)) S *= 2;
@@ -383,11 +368,12 @@ int conv_ht(const half_t* X, const half_t* Wt, const float* bias, const half_t* 
     PD_REQUIRE(res_up == 0 || (residual != nullptr && H % 2 == 0), "conv_ht: an up-sampled residual needs even H, W");
     PD_REQUIRE((long long)N * H * W * Cin * 2 <= 0x7ffffff0LL && (long long)Cout_pad * 9 * Cin * 2 <= 0x7ffffff0LL, "conv_ht: operand beyond the 2 GB buffer range");
     const long long tiles = ((long long)N * H * W / 256) * (Cout_pad / 64);
-    PD_REQUIRE(S == 1 || (S > 1 && (Cin >> 5) % S == 0 && tiles <= 4096 && ws != nullptr && (size_t)tiles * S * 16384 + PD_SK_TICKET_FLOATS <= ws_floats),
+    PD_REQUIRE(S == 1 || (S > 1 && (Cin >> 5) % S == 0 && ws != nullptr && split_fits(ws_floats, tiles, 16384, S)),
                "conv_ht: %d K-slabs do not fit the layer / the split-K workspace", S);
-    if (W == 128) return launch_ht<7>(X, Wt, bias, residual, Y, N, H, Cin, Cout, Cout_pad, zero_page, gn_part, res_up, S, ws, s);
-    if (W == 64) return launch_ht<6>(X, Wt, bias, residual, Y, N, H, Cin, Cout, Cout_pad, zero_page, gn_part, res_up, S, ws, s);
-    return launch_ht<5>(X, Wt, bias, residual, Y, N, H, Cin, Cout, Cout_pad, zero_page, gn_part, res_up, S, ws, s);
+    const SplitWs sw = split_ws(ws, ws_floats);
+    if (W == 128) return launch_ht<7>(X, Wt, bias, residual, Y, N, H, Cin, Cout, Cout_pad, zero_page, gn_part, res_up, S, sw, s);
+    if (W == 64) return launch_ht<6>(X, Wt, bias, residual, Y, N, H, Cin, Cout, Cout_pad, zero_page, gn_part, res_up, S, sw, s);
+    return launch_ht<5>(X, Wt, bias, residual, Y, N, H, Cin, Cout, Cout_pad, zero_page, gn_part, res_up, S, sw, s);
 }
 
 }  // namespace pdnn

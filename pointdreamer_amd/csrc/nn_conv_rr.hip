@@ -23,6 +23,7 @@
 //   * a ResBlock's skip 1x1 (unet.py:255) rides along as extra slabs over the block input, like k_conv_sk<10>.
 // Output: bias (+ residual, optionally read at half resolution) -> f16 NHWC + GroupNorm octet partials of the result.
 #include "nn_common.h"
+#include "nn_conv_tail.h"
 #include <algorithm>
 #include <type_traits>
 using namespace pdhip;
@@ -76,10 +77,6 @@ struct RrSrcK {                    // one K source as the kernel sees it
 #ifndef RR_W_AUX
 #define RR_W_AUX 0                 // cache policy of the weight stream (lab: 2 = nt)
 #endif
-template <int B, int E, typename Fn>
-__device__ __forceinline__ void rr_static_for(Fn&& fn) {
-    if constexpr (B < E) { fn(std::integral_constant<int, B>{}); rr_static_for<B + 1, E>(fn); }
-}
 struct RrArgs {
     RrSrcK src[2];                 // [0] the conv's own input (taps0 = 9, or 1 for a 1x1 layer), [1] the appended skip 1x1 source (S1 == 0: none)
     int taps0;
@@ -375,8 +372,8 @@ __global__ __launch_bounds__(256) void k_conv_rr(const RrArgs a) {
                     constexpr int m_off = W == 8 ? i * 2 * RS * PS : (((i * 16) / W) * RS + (i * 16) % W) * PS;
                     xa[r % (PD + 1)] = *reinterpret_cast<const half8*>(frag_base + (tap_off + m_off + jw * 64));
                 };
-                rr_static_for<0, PD>([&](auto r_tag) { rd(r_tag); });
-                rr_static_for<0, R>([&](auto r_tag) {
+                static_for<0, PD>([&](auto r_tag) { rd(r_tag); });
+                static_for<0, R>([&](auto r_tag) {
                     constexpr int r = decltype(r_tag)::value;
                     constexpr int jw = r / (T * MTW), t = (r / MTW) % T, i = r % MTW;
                     if constexpr (r + PD < R) rd(std::integral_constant<int, r + PD>{});
@@ -427,7 +424,7 @@ __global__ __launch_bounds__(256) void k_conv_rr(const RrArgs a) {
     }
 
     RR_STAMP(6);
-    // ---- in-launch split-K combine over the slabs (the protocol of k_conv_sk: write-through slices, drained, one ticket per workgroup; the
+    // ---- in-launch split-K combine over the slabs (splitk_last_arriver, nn_conv_tail.h: write-through slices, drained, one ticket per workgroup; the
     // last arriver sums all slices in slab order -- its own included, so the order never depends on who is last).  Every wave owns FW
     // fragments of the tile: the last arriver's S x FW slice loads are all in flight at once (one wave re-reading 8 x 32 KB slice by
     // slice was 16 us of a 16^2 conv: a handed-off tile arrives at ~65 GB/s per workgroup, microarch guide "handoff-payload")
@@ -438,21 +435,12 @@ __global__ __launch_bounds__(256) void k_conv_rr(const RrArgs a) {
         for (int q = 0; q < FW; ++q)
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(rr_u32x4, sum[q]), rs, slab * SLICE_BYTES + ((wave * FW + q) * 64 + lane) * 16, 0,
                                                    /*sc1: write-through*/ 16);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        volatile int* flag = reinterpret_cast<volatile int*>(smem + G::FLAG_OFF);
-        if (tid == 0) {
-            const unsigned old = __hip_atomic_fetch_add(a.tickets + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int last = old == (unsigned)(S - 1);
-            if (last) __hip_atomic_store(a.tickets + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *flag = last;
-        }
-        __syncthreads();
+        const bool last = splitk_last_arriver(a.tickets, tile, S, tid, smem + G::FLAG_OFF);
         RR_STAMP(7);
 #ifdef PD_LAB_RR_STAMP
-        if (*flag == 0 && tid == 0 && blockIdx.x < 256) { for (int k = 0; k < 16; ++k) g_rr_stamps[blockIdx.x * 16 + k] = lab_t[k]; }
+        if (!last && tid == 0 && blockIdx.x < 256) { for (int k = 0; k < 16; ++k) g_rr_stamps[blockIdx.x * 16 + k] = lab_t[k]; }
 #endif
-        if (*flag == 0) return;
+        if (!last) return;
         constexpr int SB = FW >= 4 ? 4 : 8;                // slices per batch of loads (SB x FW <= 16 x 16-byte loads per lane in flight)
 #pragma unroll
         for (int q = 0; q < FW; ++q) sum[q] = (float4_t){0.f, 0.f, 0.f, 0.f};
@@ -537,7 +525,7 @@ __global__ __launch_bounds__(256) void k_conv_rr(const RrArgs a) {
             float s1 = 0.f, q1 = 0.f;
 #pragma unroll
             for (int j = 0; j < SUB; ++j) { s1 += red2[(tid * SUB + j) * 2]; q1 += red2[(tid * SUB + j) * 2 + 1]; }
-            float* dst = a.gn_part + (((size_t)img * a.bands + band) * (Cout >> 3) + (n0 >> 3) + tid) * 2;
+            float* dst = gn_part_slot(a.gn_part, img, a.bands, band, Cout, n0, tid);
             dst[0] = s1; dst[1] = q1;
         }
     }
@@ -649,7 +637,7 @@ RrPlan conv_rr_plan(const Tuning& t, int N, int H, int W, int Cin, int Cout, int
     const int bands = H * W / (mt * 16);
     const int ntiles = Cout / (nf * 16);
     const long long tiles = (long long)N * bands * ntiles;
-    if (tiles > 4096) return p;
+    if (!split_tiles_fit(tiles)) return p;             // (one ticket word per tile; unsplit layers beyond it were never this kernel's either)
     // automatic routing: the launches a same-box A/B of the DDNM step favours (profiles/r06_rr_ab.txt): batch 1-2 at 8^2 ... 32^2 (batch 4 at
     // 8^2 only: from batch 4 up k_conv_sk's larger tiles win back what the slabs cost).  The 64^2 level at batch 1 (512+-channel layers: 27-30 /
     // 40 / 51 us at 512 / 768 / 1 024 input channels) went to k_conv_ht's two-slab form when that arrived (27 / 34 / 42 us, profiles/r06_ht_bench.txt)
@@ -670,7 +658,7 @@ RrPlan conv_rr_plan(const Tuning& t, int N, int H, int W, int Cin, int Cout, int
         s1 = std::max(1, std::min(u1, (int)((long long)u1 * s0 / ((long long)taps * u0) + 1)));
         while (u1 % s1 != 0) --s1;
     }
-    if ((size_t)tiles * (s0 + s1) * mt * nf * 256 + PD_SK_TICKET_FLOATS > ws_floats && s0 + s1 > 1) return p;
+    if (s0 + s1 > 1 && !split_fits(ws_floats, tiles, (size_t)mt * nf * 256, s0 + s1)) return p;
     p.variant = v; p.S0 = s0; p.U0 = u0 / s0; p.S1 = s1; p.U1 = s1 ? u1 / s1 : 0; p.bands = bands; p.ntiles = ntiles;
     return p;
 }
@@ -703,14 +691,15 @@ int conv_rr(const RrPlan& pl, const RrIn& in, const RrIn* skip, int taps, const 
     a.N = N; a.H = H; a.Cout = Cout; a.ntiles = pl.ntiles; a.bands = pl.bands;
     const int S = pl.S0 + pl.S1;
     const long long tiles = (long long)N * pl.bands * pl.ntiles;
-    PD_REQUIRE(tiles <= 4096, "conv_rr: too many tiles for the ticket table");
-    a.tickets = reinterpret_cast<unsigned*>(ws);
-    a.slabs = ws ? ws + PD_SK_TICKET_FLOATS : nullptr;
+    PD_REQUIRE(split_tiles_fit(tiles), "conv_rr: too many tiles for the ticket table");
+    const SplitWs sw = split_ws(ws, ws_floats);
+    a.tickets = sw.tickets;
+    a.slabs = sw.payload;
     a.gn_part = gn_part;
     const int grid = (int)(tiles * S);
     int vw = 0, cs = 0, mt = 0, nf = 0;
     PD_REQUIRE(rr_variant(pl.variant, &vw, &mt, &nf, &cs) && vw == W, "conv_rr: variant %d does not serve %d-wide images", pl.variant, W);
-    PD_REQUIRE(S == 1 || (ws != nullptr && (size_t)tiles * S * mt * nf * 256 + PD_SK_TICKET_FLOATS <= ws_floats), "conv_rr: split-K workspace too small");
+    PD_REQUIRE(S == 1 || (ws != nullptr && split_fits(ws_floats, tiles, (size_t)mt * nf * 256, S)), "conv_rr: split-K workspace too small");
     PD_REQUIRE(in.C % cs == 0 && (in.x2 == nullptr || in.Ca % cs == 0) && (!skip || (skip->C % cs == 0 && (skip->x2 == nullptr || skip->Ca % cs == 0))),
                "conv_rr: channel counts must be multiples of the unit size");
     for (const RrIn* i : {&in, skip})

@@ -16,6 +16,7 @@
 //     GroupNorm octet partials.  No k_splitk_reduce launch, no f32 round trip through a second kernel (0.97 ms of a 6.6 ms batch-1
 //     forward), and 1x1 convs can be split too.
 #include "nn_common.h"
+#include "nn_conv_tail.h"
 using namespace pdhip;
 namespace pdnn {
 
@@ -406,23 +407,7 @@ __global__ __launch_bounds__(LS ? (4 + NL) * 64 : KG * 256) void k_conv_sk(const
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rs,
                                                            split * SLAB_BYTES + ((i * TN + j) * 256 + t4) * 16, 0, /*sc1: write-through*/ 16);
         }
-        // hand-off form R1 of the cdna guide (section 6, guideline 16; microarch "valid forms"): the payload is stored WRITE-THROUGH (sc1:
-        // it is in memory, not in this XCD's L2, once the store has completed), every storing wave drains with an asm vmcnt(0) the
-        // compiler cannot drop, the workgroup joins, and only then one lane takes the ticket with a relaxed agent-scope atomic; the last
-        // arriver reads the slabs with sc1 loads (L1 bypass).  No release / acquire fence: a buffer_wbl2 / buffer_inv pair per workgroup
-        // measured 3.9x slower in the guide's own table and orders nothing the write-through + drain does not.  Contract (pdhip.h,
-        // pdhip_unet_forward): ONE forward in flight per handle -- tickets and slabs live in the handle's workspace.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave drains ...
-        __syncthreads();                                   // ... before ONE lane takes the ticket
-        volatile int* flag = reinterpret_cast<volatile int*>(smem + FLAG_OFF);
-        if (tid == 0) {
-            const unsigned old = __hip_atomic_fetch_add(tickets + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int last = old == (unsigned)(splits - 1);
-            if (last) __hip_atomic_store(tickets + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch
-            *flag = last;
-        }
-        __syncthreads();
-        if (*flag == 0) return;
+        if (!splitk_last_arriver(tickets, tile, splits, tid, smem + FLAG_OFF)) return;      // (drain, join, ticket: nn_conv_tail.h)
         // the last arriver: sum the slices in slice order (its own included -- the order must not depend on who is last);
         // U slices' loads in flight at a time, clamped index + conditional add (no branch around a load: cdna guide trap 4c)
         if (grp == 0 && consumer) {
@@ -618,8 +603,7 @@ SkPlan conv_sk_plan(const Tuning& t, int N, int H, int W, int Cin, int Cout, int
         if (t.sk_splits >= 1) ps = t.sk_splits;
     }
     ps = std::max(1, std::min(std::min(ps, std::max(KI / 2, 1)), 64));
-    if (ws_floats == 0 || tiles[pick] > 4096) ps = 1;
-    while (ps > 1 && (size_t)tiles[pick] * ps * BMs[pick] * BNs[pick] + PD_SK_TICKET_FLOATS > ws_floats) --ps;
+    while (ps > 1 && !split_fits(ws_floats, tiles[pick], (size_t)BMs[pick] * BNs[pick], ps)) --ps;
     (void)two_source;
     p.bm = BMs[pick]; p.bn = BNs[pick]; p.splits = ps; p.tile_id = pick + 1;
     // ---- the instance (lab hooks: K-groups t.sk_kg, stages t.sk_stages, order t.sk_order; 0 = the tile's default)
@@ -653,11 +637,10 @@ int conv_sk(const SkPlan& pl, const half_t* X, const half_t* Wt, const float* bi
     PD_REQUIRE(X2 == nullptr || (taps == 1 && Cin1 % 64 == 0 && (Cin - Cin1) % 64 == 0 && Cin1 > 0 && Cin1 < Cin), "conv_sk: bad two-source split");
     const long long M = (long long)N * H * W;
     const int m_tiles = (int)((M + pl.bm - 1) / pl.bm), n_tiles = Cout_pad / pl.bn, total = m_tiles * n_tiles;
-    PD_REQUIRE(pl.splits == 1 || (ws != nullptr && (size_t)total * pl.splits * pl.bm * pl.bn + PD_SK_TICKET_FLOATS <= ws_floats && total <= 4096),
-               "conv_sk: split-K workspace too small");
-    // workspace: [0, 4096) ticket words (zeroed at allocation, self-resetting), then the slabs
-    unsigned* tickets = reinterpret_cast<unsigned*>(ws);
-    float* slabs = ws ? ws + PD_SK_TICKET_FLOATS : nullptr;
+    PD_REQUIRE(pl.splits == 1 || (ws != nullptr && split_fits(ws_floats, total, (size_t)pl.bm * pl.bn, pl.splits)), "conv_sk: split-K workspace too small");
+    const SplitWs sw = split_ws(ws, ws_floats);
+    unsigned* tickets = sw.tickets;
+    float* slabs = sw.payload;
     const int grid = total * pl.splits, kg = pl.kg, st = pl.stages;
 #define SK_ARGS grid, s, X, Wt, bias, residual, Y, N, H, W, Cin, Cout, n_tiles, total, zero_page, pl.splits, slabs, tickets, gn_part, X2, Cin1, pl.m_fast, nullptr, nullptr, 0, 0, res_up
 #define SK_L(T, BM_, BN_, NST_, KG_) launch_sk<T, BM_, BN_, NST_, KG_>(SK_ARGS)
@@ -705,10 +688,10 @@ int conv_sk_skip(const SkPlan& pl, const half_t* X, const half_t* Wt, const floa
     PD_REQUIRE(XS2 == nullptr || (Cs1 % 64 == 0 && Cs1 > 0 && Cs1 < Cs), "conv_sk_skip: bad two-source split");
     const long long M = (long long)N * H * W;
     const int m_tiles = (int)((M + pl.bm - 1) / pl.bm), n_tiles = Cout_pad / pl.bn, total = m_tiles * n_tiles;
-    PD_REQUIRE(pl.splits == 1 || (ws != nullptr && (size_t)total * pl.splits * pl.bm * pl.bn + PD_SK_TICKET_FLOATS <= ws_floats && total <= 4096),
-               "conv_sk_skip: split-K workspace too small");
-    unsigned* tickets = reinterpret_cast<unsigned*>(ws);
-    float* slabs = ws ? ws + PD_SK_TICKET_FLOATS : nullptr;
+    PD_REQUIRE(pl.splits == 1 || (ws != nullptr && split_fits(ws_floats, total, (size_t)pl.bm * pl.bn, pl.splits)), "conv_sk_skip: split-K workspace too small");
+    const SplitWs sw = split_ws(ws, ws_floats);
+    unsigned* tickets = sw.tickets;
+    float* slabs = sw.payload;
     const int grid = total * pl.splits, kg = pl.kg;
 #define SKS_ARGS grid, s, X, Wt, bias, nullptr, Y, N, H, W, Cin, Cout, n_tiles, total, zero_page, pl.splits, slabs, tickets, gn_part, nullptr, Cin, 0, XS, XS2, Cs1, Cs
     if (pl.tile_id == 1) return kg == 12 ? launch_sk<10, 128, 128, 3, 1, true, 8>(SKS_ARGS) : kg == 1 ? launch_sk<10, 128, 128, 2, 1>(SKS_ARGS) : launch_sk<10, 128, 128, 2, 2>(SKS_ARGS);

@@ -15,6 +15,7 @@
 // Epilogue: accumulators -> LDS transpose -> 16-byte coalesced NHWC stores with bias and residual fused.
 // Small-M layers: split-K over blockIdx.y with f32 partial tiles + a fixed-order reduce kernel.
 #include "nn_common.h"
+#include "nn_conv_tail.h"
 using namespace pdhip;
 namespace pdnn {
 
@@ -471,7 +472,7 @@ __global__ __launch_bounds__(WM * WN * 64) void k_conv_igemm(const half_t* __res
             for (int r = 0; r < RPP; ++r) { s1 += red[(r * CT + tid) * 2]; q1 += red[(r * CT + tid) * 2 + 1]; }
             const int hw = H * W, chunks = (TAPS == 4 ? 4 : 1) * (hw / BMT);
             const int img = m0 / hw, chunk = (TAPS == 4) ? ((m0 - img * hw) / BMT) * 4 + phase : (m0 - img * hw) / BMT;
-            float* dst = gn_part + (((size_t)img * chunks + chunk) * (Cout >> 3) + (n0 >> 3) + tid) * 2;
+            float* dst = gn_part_slot(gn_part, img, chunks, chunk, Cout, n0, tid);
             dst[0] = s1; dst[1] = q1;
         }
     }
@@ -551,7 +552,7 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const float* __restrict__
         const int chunks = hw / SK_ROWS;
         const long long img = m0 / hw;
         const int chunk = (int)((m0 - img * hw) / SK_ROWS);
-        float* dst = gn_part + (((size_t)img * chunks + chunk) * (Cout >> 3) + oct) * 2;
+        float* dst = gn_part_slot(gn_part, img, chunks, chunk, Cout, 0, oct);
         dst[0] = gs; dst[1] = gq;
     }
 }
@@ -595,9 +596,7 @@ ConvPlan conv_plan(const Tuning& t, int N, int H, int W, int Cin, int Cout, int 
     const bool unsplit = halo && conv3x3_halo_splits(N, H, W, Cin, Cout, Cout_pad, ws_floats) == 1;
     const bool strips = W != 256 || H % 4 == 0;
     const bool single3 = taps == 9 && !nd.two_source;
-    // (the first PD_SK_TICKET_FLOATS words of the workspace are k_conv_sk's self-resetting ticket counters: the f32 partials of the halo
-    // and implicit-GEMM kernels must not land on them, or the next split k_conv_sk launch never sees its last ticket)
-    const size_t part_floats = ws_floats > PD_SK_TICKET_FLOATS ? ws_floats - PD_SK_TICKET_FLOATS : 0;
+    const size_t part_floats = split_payload_floats(ws_floats);      // the f32 partials of the halo and implicit-GEMM kernels live behind the tickets
     auto done = [&](ConvKernel k) {
         p.kernel = k;
         int chunks = 0;
@@ -709,8 +708,9 @@ int splitk_reduce(const float* partial, int splits, long long M, int Cout, const
 int conv_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
     const int N = p.N, H = p.H, W = p.W, Cin = p.Cin, Cout = p.Cout, Cout_pad = p.Cout_pad, taps = p.taps;
     const long long hw = (long long)H * W, M = (long long)N * hw;
-    float* part_ws = a.ws != nullptr && a.ws_floats > PD_SK_TICKET_FLOATS ? a.ws + PD_SK_TICKET_FLOATS : nullptr;   // behind k_conv_sk's tickets
-    const size_t part_floats = part_ws != nullptr ? a.ws_floats - PD_SK_TICKET_FLOATS : 0;
+    const SplitWs sw = split_ws(a.ws, a.ws_floats);
+    float* const part_ws = sw.payload;                     // behind the tickets of the in-launch combines
+    const size_t part_floats = sw.payload_floats;
     float* gn_part = p.gn_chunks > 0 ? a.gn_part : nullptr;
     switch (p.kernel) {
     case CONV_HALO:

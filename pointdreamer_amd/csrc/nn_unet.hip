@@ -7,6 +7,7 @@
 // Activations are NHWC f16 in a bump arena sized at create() for max_batch (288 GB HBM: no reuse games);
 // every forward issues the same launches at the same addresses, asynchronously on the caller's stream.
 #include "nn_common.h"
+#include "nn_conv_tail.h"
 #include <map>
 #include <string>
 #include <vector>
@@ -1119,8 +1120,9 @@ extern "C" int pdhip_gn_silu_conv3x3_nhwc_f16(const void* x, const float* gamma,
     PD_TRY(gn_stats((const half_t*)x, N, H * W, Cin, 1e-5f, stats, ws + (size_t)N * 64, gws, s));
     PD_TRY(gn_table(stats, gamma, beta, film, film_stride, N, Cin, table, s));
     // (the debug split-K workspace is shared with pdhip_conv2d_nhwc_f16, whose k_conv_sk route keeps its tickets in the first words)
-    float* hws = g_dbg_splitk_ws != nullptr && g_dbg_splitk_floats > PD_SK_TICKET_FLOATS ? g_dbg_splitk_ws + PD_SK_TICKET_FLOATS : nullptr;
-    const size_t hws_floats = hws ? g_dbg_splitk_floats - PD_SK_TICKET_FLOATS : 0;
+    const pdnn::SplitWs sw = split_ws(g_dbg_splitk_ws, g_dbg_splitk_floats);
+    float* const hws = sw.payload;
+    const size_t hws_floats = sw.payload_floats;
     PD_REQUIRE(conv3x3_halo_eligible(N, H, W, Cin, Cout_pad) && N > 0 && Cout > 0 && Cout_pad > 0, "conv3x3_halo: unsupported geometry (N=%d H=%d W=%d Cin=%d)", N, H, W, Cin);
     return conv3x3_halo((const half_t*)x, (const half_t*)w_packed, bias, (const half_t*)residual, (half_t*)y, N, H, W, Cin, Cout,
                         Cout_pad, (const half_t*)zero_page, s, nullptr, conv3x3_halo_launch_splits(tuning(), N, H, W, Cin, Cout, Cout_pad, hws_floats),

@@ -133,11 +133,15 @@ def reference_f64(op):
 
 
 # ---- the cases of tests/test_gpu_conv_epilogue.py.  hooks: tile = pdhip_debug_set_conv_tile, sk = (mode, tile, splits) of pdhip_debug_set_conv_sk,
-# splits = forced split-K factor (needs the workspace), strips = pdhip_debug_set_conv_halo_strips.  chunks = the producer's documented chunk count
-# per image; contiguous = each chunk is a contiguous pixel range.
-def _case(name, kernel, N, H, W, Cin, Cout, taps=9, res=True, tile=0, sk=(1, 0, 0), splits=0, ws=False, strips=0, chunks=0, contiguous=True, Cs=0, Cs1=0):
+# splits = forced split-K factor (needs the workspace), strips = pdhip_debug_set_conv_halo_strips, ht = (mode, slabs) of pdhip_debug_set_conv_ht,
+# rr = (variant, slabs) of pdhip_debug_set_conv_rr under mode 2 (None: mode 0).  chunks = the producer's documented chunk count per image;
+# contiguous = each chunk is a contiguous pixel range.  entry: 'launch' = pdhip_debug_conv_launch_nhwc_f16; 'rr' = pdhip_conv_rr_f16 (fragment-major
+# weights, which the debug launch does not carry); 'phase' = pdhip_conv3x3_up2_phase_nhwc_f16 (the engine picks that kernel, not conv_plan).
+def _case(name, kernel, N, H, W, Cin, Cout, taps=9, res=True, tile=0, sk=(1, 0, 0), splits=0, ws=False, strips=0, chunks=0, contiguous=True, Cs=0, Cs1=0,
+          ht=(0, 0), rr=None, entry='launch'):
     return dict(name=name, kernel=kernel, N=N, H=H, W=W, Cin=Cin, Cout=Cout, taps=taps, res=res and not Cs, tile=tile, sk=sk, splits=splits,
-                ws=ws or splits > 0 or sk[2] > 1, strips=strips, chunks=chunks, contiguous=contiguous, Cs=Cs, Cs1=Cs1)
+                ws=ws or splits > 0 or sk[2] > 1 or ht[1] > 1 or (rr is not None and rr[1] > 1), strips=strips, chunks=chunks, contiguous=contiguous,
+                Cs=Cs, Cs1=Cs1, ht=ht, rr=rr, entry=entry)
 
 
 def _cases():
@@ -187,13 +191,39 @@ def _cases():
 CASES = _cases()
 
 
+# ---- the kernels the list above does not reach, at the smallest shapes their planners take (tests/conv_tail_common.py launches them; the float64
+# test and the parent-bytes test of the shared conv tail run CASES + TAIL_CASES).  H, W: the output's.
+def _tail_cases():
+    cs = []
+    # k_conv_ht: 256-pixel x 64-channel tiles of whole rows, chunks = H W / 256; one K-slab (no hand-off) and several (in-launch combine); the three widths
+    cs.append(_case("ht-1x32x32-slab1", 'ht', 1, 32, 32, 64, 136, ht=(2, 1), chunks=4))
+    cs.append(_case("ht-1x32x32-slab2", 'ht', 1, 32, 32, 64, 136, ht=(2, 2), chunks=4))
+    cs.append(_case("ht-2x64x64-slab4-nores", 'ht', 2, 64, 64, 128, 72, res=False, ht=(2, 4), chunks=16))
+    cs.append(_case("ht-1x128x128-slab1", 'ht', 1, 128, 128, 32, 64, ht=(2, 1), chunks=64))
+    # k_conv_rr: chunks = bands per image.  Variant 5 (8 wide, 64 data rows in 128 row slots: fewer data rows than rows per pass), 2 (16 wide, 32-channel
+    # tiles: 128 rows in two passes of 64), 7 (16 wide, 16-channel tiles: 128 rows, one pass), 8 (64 wide: 256 rows in four passes); one slab and several
+    for sl in (1, 2):
+        cs.append(_case(f"rr-v5-2x8x8-slab{sl}", 'rr', 2, 8, 8, 256, 48, rr=(5, sl), chunks=1, entry='rr'))
+        cs.append(_case(f"rr-v2-1x16x16-slab{sl}", 'rr', 1, 16, 16, 256, 96, rr=(2, sl), chunks=2, entry='rr'))
+    cs.append(_case("rr-v7-3x16x16-slab2-nores", 'rr', 3, 16, 16, 256, 48, res=False, rr=(7, 2), chunks=2, entry='rr'))
+    cs.append(_case("rr-v8-1x64x64-slab2", 'rr', 1, 64, 64, 256, 32, rr=(8, 2), chunks=16, entry='rr'))
+    # the four-phase up conv (k_conv_igemm<4>): conv3x3(nearest_x2(x)) over the half-resolution x, 256-row tiles per phase, chunk = 4 tile + phase (the
+    # pixels of one parity: not a contiguous range); 256x256 tiles (padded Cout 256) and 256x128
+    cs.append(_case("phase-2x32x32-geo8", 'phase', 2, 32, 32, 64, 136, res=False, chunks=4, contiguous=False, entry='phase'))
+    cs.append(_case("phase-1x64x64-geo16", 'phase', 1, 64, 64, 64, 72, res=False, chunks=16, contiguous=False, entry='phase'))
+    return cs
+
+
+TAIL_CASES = _tail_cases()
+
+
 def workspace_floats(c):
     """split-K workspace of a case: 4096 ticket words + room for `splits` f32 copies of the padded output (every kernel's need is below that)."""
     if not c['ws']:
         return 0
     pad = (c['Cout'] + 127) // 128 * 128
     M = c['N'] * c['H'] * c['W']
-    return 4096 + max(c['splits'], c['sk'][2], 1) * (M + 128) * pad
+    return 4096 + max(c['splits'], c['sk'][2], c['ht'][1], (c['rr'] or (0, 0))[1], 1) * (M + 128) * pad
 
 
 class Hooks:
@@ -205,7 +235,7 @@ class Hooks:
     def __enter__(self):
         L, c = self.L, self.c
         self.old = (L.pdhip_debug_set_conv_tile(c['tile']), L.pdhip_debug_set_conv_sk(*c['sk']), L.pdhip_debug_set_conv_halo_strips(c['strips']),
-                    L.pdhip_debug_set_conv_ht(0, 0), L.pdhip_debug_set_conv_rr(0, 0, 0))
+                    L.pdhip_debug_set_conv_ht(*c['ht']), L.pdhip_debug_set_conv_rr(*((2,) + tuple(c['rr']) if c['rr'] else (0, 0, 0))))
         # (the forced split factor travels with pdhip_debug_set_conv_splitk; its workspace pointer serves pdhip_conv2d_nhwc_f16 only)
         L.pdhip_debug_set_conv_splitk(None, 0, c['splits'])
         return self

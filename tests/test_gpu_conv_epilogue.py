@@ -14,11 +14,10 @@ import torch
 import torch.nn.functional as F
 
 import conv_epilogue_common as ce
+import conv_tail_common as ct
+from conv_tail_common import DEV, GUARD, TAIL, _nhwc, _pack, _ptr, _stream
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
-GUARD = 0x7F8ABCDE            # bit pattern of the floats behind the partials (a NaN payload no kernel produces)
-TAIL = 4096                   # floats kept behind the partials: all of them carry the guard pattern and are checked
 
 
 @pytest.fixture(scope="module")
@@ -27,28 +26,6 @@ def L():
     from pointdreamer_amd import _lib
     import pointdreamer_amd.ddnm_inpainting  # noqa: F401  (registers the entry points)
     return _lib.lib()
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous().half().to(DEV)
-
-
-def _pack(L, w):
-    Cout, Cin, k = w.shape[0], w.shape[1], w.shape[2]
-    pad = (Cout + 127) // 128 * 128
-    wp = torch.zeros((pad, k * k * Cin), dtype=torch.float16, device=DEV)
-    wd = w.contiguous().float().to(DEV)
-    assert L.pdhip_pack_conv_weight_f16(_ptr(wd), Cout, Cin, k * k, _ptr(wp), _stream()) == 0
-    torch.cuda.synchronize()
-    return wp
 
 
 def launch(L, c, op, x2_split=0, res_up=False, want_gn=True):
@@ -104,6 +81,26 @@ def test_conv_epilogue_partials(L, c):
     if c['chunks'] == 0:
         return                     # (no partials for this geometry: the guard check covered every float of the buffer)
     errs = ce.partials_errors(part, y, chunks, contiguous=c['contiguous'])
+    assert errs == [], errs
+
+
+@pytest.mark.parametrize("c", ce.TAIL_CASES, ids=[c['name'] for c in ce.TAIL_CASES])
+def test_conv_epilogue_partials_of_the_other_entries(L, c):
+    """k_conv_ht, k_conv_rr and the four-phase up conv (tests/conv_tail_common.py launches them): the same checks as above."""
+    op = ct.operands(c)
+    y, part, chunks, kernel = ct.prepare(L, c, op)()
+    assert kernel == ce.KERNELS[c['kernel']], f"routed to kernel {kernel}"
+    assert chunks == c['chunks'], f"{chunks} chunks per image, the kernel documents {c['chunks']}"
+    ref = ct.reference_f64(c, op)
+    err = (y.double().cpu() - ref).abs().max().item()
+    print(f"  y: max err {err:.3e}, bound {2e-3 * ref.abs().max().item() + 1e-3:.3e}")
+    assert err <= 2e-3 * ref.abs().max().item() + 1e-3
+    if c['entry'] == 'phase':      # chunk 4 t + p = the pixels of parity p = (py, px) of the t-th run of 256 half-resolution pixels: gathered, then as everywhere
+        N, H, W, Cc = y.shape
+        yp = y.reshape(N, H // 2, 2, W // 2, 2, Cc).permute(0, 1, 3, 2, 4, 5).reshape(N, chunks // 4, 256, 4, Cc).permute(0, 1, 3, 2, 4)
+        errs = ce.partials_errors(part, yp.reshape(N, H * W, Cc), chunks)
+    else:
+        errs = ce.partials_errors(part, y, chunks, contiguous=c['contiguous'])
     assert errs == [], errs
 
 
