@@ -15,6 +15,13 @@
 // no rounding.  Pixels are a degenerate input for Delaunay (co-circular sites everywhere): where four or more sites share an
 // empty circle several triangulations are valid and qhull's choice is a property of its merge order; this kernel returns a
 // valid one (ties: first maximum in site order), tests check validity there and equality where the triangle is unique.
+//
+// The unit: three row kernels list the sites and queries; k_linear_local answers a tile's queries against the sites of its window (two
+// launches, a small and a large window) and k_linear_tri what they cannot certify, against all sites; k_linear_boundary finishes the queries
+// on the hull's boundary.  The two query kernels differ in where the sites come from and what a result is worth; a query's state
+// (LinQuery), its step on the scan's winner (lin_step: phase 0, phase 1, the lifted plane), the merge of the 64 lanes' candidates with
+// the tie rule (LIN_ARGMAX_MERGE), the site test (lin_site) and the barycentric store (lin_store_bary) exist once.
+// tests/test_gpu_linear_parent.py holds out, tri and the workspace's counters to recorded bytes: the choice among valid triangles is pinned.
 #include "common.h"
 using namespace pdhip;
 
@@ -97,14 +104,142 @@ __global__ void k_linear_copy_sites(const float* __restrict__ img, float* __rest
                                     int mask_is_f32, int64_t mask_bstride, int C, int n, int32_t* __restrict__ tri) {
     const int b = blockIdx.y;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const bool site = mask_is_f32 ? reinterpret_cast<const float*>(mask)[(size_t)b * mask_bstride + i] != 0.0f
-                                      : reinterpret_cast<const uint8_t*>(mask)[(size_t)b * mask_bstride + i] != 0;
-        if (!site) continue;
+        if (!lin_site(mask, mask_is_f32, (size_t)b * mask_bstride + i)) continue;
         for (int c = 0; c < C; ++c) out[((size_t)b * C + c) * n + i] = img[((size_t)b * C + c) * n + i];
         if (tri) { tri[((size_t)b * n + i) * 3] = tri[((size_t)b * n + i) * 3 + 1] = tri[((size_t)b * n + i) * 3 + 2] = -1; }
     }
 }
 
+// ---- what k_linear_tri (all sites of the image, from global memory) and k_linear_local (a window's sites, from LDS) share: a wavefront
+// runs LQ queries at once, ST = 64 / LQ lanes per query, the query's state in the first of them (its slot lane).  A round is one scan of
+// the sites for every query's arg-max of score(p) = A x + B y + Cc (x^2 + y^2) -- the scans are the kernels' own --, one merge of the 64
+// lanes' candidates (LIN_ARGMAX_MERGE), and one step of the query's state on the winner (lin_step).
+constexpr int ST = 64 / LQ;
+
+// what one query carries between rounds (meaningful in the slot lanes).  phase 0: 2-D GJK on {p - q}; phase 1: Delaunay pivots.
+struct LinQuery {
+    i2 q;
+    i2 pa, pb, pc;                     // absolute site coordinates
+    int ia, ib, ic;                    // their places in the scanned site list (kept by lin_step<true> only)
+    int phase, dim;
+    int state;                         // 0 running, 1 done (triangle a, b, c), 2 outside the hull (NaN), 3 idle, 4 on the hull boundary
+    double A, B, Cc, K;                // score(p) = A x + B y + Cc (x^2 + y^2); phase 1 violation <=> score + K > 0
+};
+__device__ __forceinline__ LinQuery lin_query(i2 q, bool owner, int NS) {
+    return {q, {0, 0}, {0, 0}, {0, 0}, -1, -1, -1, 0, 0, owner ? (NS > 0 ? 0 : 2) : 3, 1.0, 0.0, 0.0, 0.0};
+}
+
+// The arg-max of every query over the 64 lanes' candidates: on entry best[k] / bi[k] are this lane's best score and its site index for query
+// k; on return best[0] / bi[0] are those of query lane / ST, in all ST lanes of that query.  THE TIE RULE, here and nowhere else: the larger
+// value wins, then the smaller index -- with scans that visit the sites in ascending order and keep a lane's FIRST maximum this is "first
+// maximum in site order".  Halving exchange: at distance OFF the two partners split the NN queries they both still hold, each sends the half
+// the other keeps (16 -> 8 -> 4 -> 2 -> 1 values per lane over distances 32 .. 4); the ST lanes that then hold the same query finish with a
+// butterfly (NN == 1: nothing left to split, the one value is sent AND kept).
+// Written once, but expanded in the kernel's own body, not called: handed to a function -- by reference or by value, recursive or not -- the
+// arrays reach the vectorizer in another shape, it stops pairing the queries of the scan loop IN FRONT of the merge, and that loop goes from
+// 165 to 180 instructions per 64 sites in k_linear_tri (163 -> 176 in k_linear_local): + 0.7 % on the global pass, + 1.6 % on the 48 x 48 one.
+__device__ __forceinline__ bool lin_better(double ob, int oi, double kb, int ki) { return ob > kb || (ob == kb && oi < ki); }
+#define LIN_EXCHANGE(best, bi, lane, I)                                                                                   \
+    {                                                                                                                     \
+        constexpr int OFF = 32 >> (I), NN = (LQ >> (I)) > 1 ? (LQ >> (I)) : 1, NH = NN > 1 ? NN / 2 : 1, UP = NN > 1 ? NH : 0; \
+        const bool hi = NN > 1 && ((lane) & OFF) != 0;                                                                    \
+        _Pragma("unroll") for (int k = 0; k < NH; ++k) {                                                                  \
+            const double send = hi ? best[k] : best[k + UP], keep = hi ? best[k + UP] : best[k];                          \
+            const int sendi = hi ? bi[k] : bi[k + UP], keepi = hi ? bi[k + UP] : bi[k];                                   \
+            const double ob = __shfl_xor(send, OFF);                                                                      \
+            const int oi = __shfl_xor(sendi, OFF);                                                                        \
+            const bool take = lin_better(ob, oi, keep, keepi);                                                            \
+            best[k] = take ? ob : keep; bi[k] = take ? oi : keepi;                                                        \
+        }                                                                                                                 \
+    }
+#define LIN_ARGMAX_MERGE(best, bi, lane)                                                                                  \
+    static_assert(LQ >= 2 && LQ <= 32 && (LQ & (LQ - 1)) == 0, "distances 32 .. 1: six exchanges");                       \
+    LIN_EXCHANGE(best, bi, lane, 0) LIN_EXCHANGE(best, bi, lane, 1) LIN_EXCHANGE(best, bi, lane, 2)                       \
+    LIN_EXCHANGE(best, bi, lane, 3) LIN_EXCHANGE(best, bi, lane, 4) LIN_EXCHANGE(best, bi, lane, 5)
+
+// One round of one query: `best` is the largest score over the scanned sites, j the index of the site p that has it.  TRACK: keep the site
+// indices ia / ib / ic next to the vertices.  Returns false -- the state untouched -- iff a phase 1 pivot finds no sub-triangle of the fan
+// that keeps q (cannot happen for q inside (a, b, c)): what that means is the caller's.
+template <bool TRACK>
+__device__ __forceinline__ bool lin_step(LinQuery& s, double best, int j, i2 p) {
+    const i2 q = s.q;
+    if (s.phase == 0) {
+        // support point of {p - q} in direction (A, B): value = best - (A qx + B qy)
+        const double sv = best - (s.A * q.x + s.B * q.y);
+        if (sv < 0.0) { s.state = 2; return true; }                                       // q outside the hull of the sites
+        if (sv == 0.0 && !(s.dim == 1 && (s.pa.x - q.x) * s.B == (s.pa.y - q.y) * s.A)) {  // q ON the hull boundary (supporting line of
+            s.state = 4; return true;                                                      // direction (A, B)): k_linear_boundary
+        }
+        if (s.dim == 0) { s.pa = p; if (TRACK) s.ia = j; s.A = -(p.x - q.x); s.B = -(p.y - q.y); s.dim = 1; return true; }
+        if (s.dim == 1) {
+            s.pb = p; if (TRACK) s.ib = j;
+            const double abx = s.pa.x - s.pb.x, aby = s.pa.y - s.pb.y;
+            double px = -aby, py = abx;                                              // perpendicular to ab, turned towards q
+            const double t = px * (q.x - s.pb.x) + py * (q.y - s.pb.y);
+            if (t < 0.0) { px = -px; py = -py; }
+            // t == 0: q lies strictly inside segment ab (sv > 0 put b beyond q), but a and b are far-apart EXTREME sites, not
+            // Delaunay neighbours -- never interpolate along ab.  Keep either perpendicular: a site strictly on that side closes a
+            // triangle with q on its edge ab (the containment tests are inclusive) and phase 1 pivots to the Delaunay triangle;
+            // no site on that side (sv == 0 next round) makes line ab a supporting line of the hull: k_linear_boundary takes the
+            // nearest site on either side of q along it -- which is also the answer when ALL sites are collinear.
+            s.A = px; s.B = py; s.dim = 2; return true;
+        }
+        s.pc = p; if (TRACK) s.ic = j;
+        // triangle (c, b, a): which edge region of the newest vertex holds q?
+        const double cbx = s.pb.x - s.pc.x, cby = s.pb.y - s.pc.y, cax = s.pa.x - s.pc.x, cay = s.pa.y - s.pc.y;
+        const double cox = q.x - s.pc.x, coy = q.y - s.pc.y;
+        double nbx = -cby, nby = cbx;                                                // perpendicular to cb, away from a
+        if (nbx * cax + nby * cay > 0.0) { nbx = -nbx; nby = -nby; }
+        double nax = -cay, nay = cax;                                                // perpendicular to ca, away from b
+        if (nax * cbx + nay * cby > 0.0) { nax = -nax; nay = -nay; }
+        if (nbx * cox + nby * coy > 0.0) { s.pa = s.pb; s.pb = s.pc; if (TRACK) { s.ia = s.ib; s.ib = s.ic; } s.A = nbx; s.B = nby; return true; }
+        if (nax * cox + nay * coy > 0.0) { s.pb = s.pc; if (TRACK) s.ib = s.ic; s.A = nax; s.B = nay; return true; }
+        if (orient(s.pa, s.pb, s.pc) == 0.0) { s.state = 2; return true; }           // (degenerate: collinear sites only)
+        if (orient(s.pa, s.pb, s.pc) < 0.0) {
+            const i2 tp = s.pb; s.pb = s.pc; s.pc = tp;
+            if (TRACK) { const int ti = s.ib; s.ib = s.ic; s.ic = ti; }
+        }
+        s.phase = 1;                                                                 // a proper triangle, counter-clockwise, q inside or on it
+    } else {
+        // deepest site inside the circumcircle of (a, b, c): violation <=> score + K > 0
+        if (best + s.K <= 0.0) { s.state = 1; return true; }
+        // the site replaces the vertex that keeps q inside (fan of the new site over the old triangle)
+        const i2 t0[3] = {p, s.pa, s.pa}, t1[3] = {s.pb, p, s.pb}, t2[3] = {s.pc, s.pc, p};
+        int pick = -1;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (pick >= 0) continue;
+            if (orient(t0[k], t1[k], t2[k]) > 0.0 && orient(t0[k], t1[k], q) >= 0.0 && orient(t1[k], t2[k], q) >= 0.0 &&
+                orient(t2[k], t0[k], q) >= 0.0) pick = k;
+        }
+        if (pick < 0) return false;
+        if (TRACK) {
+            const int n0[3] = {j, s.ia, s.ia}, n1[3] = {s.ib, j, s.ib}, n2[3] = {s.ic, s.ic, j};
+            s.ia = n0[pick]; s.ib = n1[pick]; s.ic = n2[pick];
+        }
+        s.pa = t0[pick]; s.pb = t1[pick]; s.pc = t2[pick];
+    }
+    // lifted plane through a', b', c' (counter-clockwise): N = (b' - a') x (c' - a'); p' below it <=> N . (p' - a') < 0
+    const i2 pa = s.pa, pb = s.pb, pc = s.pc;
+    const double ar = pa.x * pa.x + pa.y * pa.y, br = pb.x * pb.x + pb.y * pb.y, cr = pc.x * pc.x + pc.y * pc.y;
+    const double ux = pb.x - pa.x, uy = pb.y - pa.y, uz = br - ar, vx = pc.x - pa.x, vy = pc.y - pa.y, vz = cr - ar;
+    const double Nx = uy * vz - uz * vy, Ny = uz * vx - ux * vz, Nz = ux * vy - uy * vx;
+    s.A = -Nx; s.B = -Ny; s.Cc = -Nz; s.K = (Nx * pa.x + Ny * pa.y) + Nz * ar;
+    return true;
+}
+
+// barycentric interpolation of q in the counter-clockwise triangle (a, b, c), every channel; the weights are exact integers, the sum is not
+__device__ __forceinline__ void lin_store_bary(const float* __restrict__ im, float* __restrict__ o, int C, int n, int W, const LinQuery& s) {
+    const i2 q = s.q, pa = s.pa, pb = s.pb, pc = s.pc;
+    const int xa = (int)pa.y * W + (int)pa.x, xb = (int)pb.y * W + (int)pb.x, xc = (int)pc.y * W + (int)pc.x;
+    const double wa = orient(q, pb, pc), wb = orient(pa, q, pc), wc = orient(pa, pb, q), Wt = orient(pa, pb, pc);
+    for (int c = 0; c < C; ++c) {
+        const double v = (wa * (double)im[(size_t)c * n + xa] + wb * (double)im[(size_t)c * n + xb]) + wc * (double)im[(size_t)c * n + xc];
+        o[(size_t)c * n] = (float)(v / Wt);
+    }
+}
+
+// the global kernel: the queries of qlist (all of the image's, or what the local passes could not certify) against all sites of the image
 __global__ __launch_bounds__(256, 2) void k_linear_tri(const float* __restrict__ img, float* __restrict__ out, int C, int H, int W,
                                                        const float* __restrict__ sites, const int* __restrict__ qlist,
                                                        const int* __restrict__ counts, int32_t* __restrict__ tri /*[B][H*W][3] or null*/,
@@ -118,27 +253,20 @@ __global__ __launch_bounds__(256, 2) void k_linear_tri(const float* __restrict__
     const float* sx = sites + (size_t)b * 3 * n;
     const float* sy = sx + n;
     const float* sr = sy + n;
-    constexpr int ST = 64 / LQ;
     const int kq = lane / ST;
     const bool slot = (lane % ST) == 0;
     const bool owner = slot && q0 + kq < NQ;
     const int qi = owner ? qlist[(size_t)b * n + q0 + kq] : 0;
-    const i2 q = {(double)(qi % W), (double)(qi / W)};
-    // ---- per-query state (meaningful in the slot lanes).  phase 0: 2-D GJK on {p - q}; phase 1: Delaunay pivots.
-    int phase = 0, dim = 0;
-    int state = owner ? (NS > 0 ? 0 : 2) : 3;        // 0 running, 1 done (triangle ia, ib, ic), 2 outside the hull (NaN), 3 idle
-    i2 pa = {0, 0}, pb = {0, 0}, pc = {0, 0};        // absolute site coordinates
-    int ia = -1, ib = -1, ic = -1;
-    double A = 1.0, B = 0.0, Cc = 0.0, K = 0.0;      // score(p) = A x + B y + Cc (x^2 + y^2); phase 1 violation <=> score + K > 0
+    LinQuery s = lin_query({(double)(qi % W), (double)(qi / W)}, owner, NS);
     for (int round = 0; round < LIN_MAX_ROUNDS; ++round) {
-        if (__ballot(state == 0) == 0ull) break;
-        if (slot) { s_co[wave][kq][0] = A; s_co[wave][kq][1] = B; s_co[wave][kq][2] = Cc; }
+        if (__ballot(s.state == 0) == 0ull) break;
+        if (slot) { s_co[wave][kq][0] = s.A; s_co[wave][kq][1] = s.B; s_co[wave][kq][2] = s.Cc; }
         __builtin_amdgcn_wave_barrier();
         double ca[LQ], cb[LQ], cc[LQ], best[LQ];
         int bi[LQ];
 #pragma unroll
         for (int k = 0; k < LQ; ++k) { ca[k] = s_co[wave][k][0]; cb[k] = s_co[wave][k][1]; cc[k] = s_co[wave][k][2]; best[k] = -1.0e300; bi[k] = 0x7fffffff; }
-        // ---- scan: sites in ascending order, a lane keeps its FIRST maximum, the butterflies prefer the smaller index
+        // ---- scan: sites in ascending order, a lane keeps its FIRST maximum
         float nx = 0.f, ny = 0.f, nr = 0.f;
         if (lane < NS) { nx = sx[lane]; ny = sy[lane]; nr = sr[lane]; }
         for (int j = lane; j < NS; j += 64) {
@@ -151,112 +279,26 @@ __global__ __launch_bounds__(256, 2) void k_linear_tri(const float* __restrict__
                 if (val > best[k]) { best[k] = val; bi[k] = j; }
             }
         }
-#define LIN_HALVE(I)                                                                                                  \
-        if constexpr ((LQ >> (I)) > 1) {                                                                              \
-            constexpr int off = 32 >> (I), nn = LQ >> (I);                                                            \
-            const bool hi = (lane & off) != 0;                                                                        \
-            _Pragma("unroll") for (int k = 0; k < nn / 2; ++k) {                                                      \
-                const double send = hi ? best[k] : best[k + nn / 2], keep = hi ? best[k + nn / 2] : best[k];          \
-                const int sendi = hi ? bi[k] : bi[k + nn / 2], keepi = hi ? bi[k + nn / 2] : bi[k];                   \
-                const double ob = __shfl_xor(send, off);                                                              \
-                const int oi = __shfl_xor(sendi, off);                                                                \
-                const bool take = ob > keep || (ob == keep && oi < keepi);                                            \
-                best[k] = take ? ob : keep; bi[k] = take ? oi : keepi;                                                \
-            }                                                                                                         \
-        }
-        LIN_HALVE(0) LIN_HALVE(1) LIN_HALVE(2) LIN_HALVE(3)
-#undef LIN_HALVE
-#pragma unroll
-        for (int off = ST / 2; off > 0; off >>= 1) {
-            const double ob = __shfl_xor(best[0], off);
-            const int oi = __shfl_xor(bi[0], off);
-            if (ob > best[0] || (ob == best[0] && oi < bi[0])) { best[0] = ob; bi[0] = oi; }
-        }
-        if (state != 0) continue;
+        LIN_ARGMAX_MERGE(best, bi, lane)
+        if (s.state != 0) continue;
         const int j = bi[0];
-        const i2 p = {(double)sx[j], (double)sy[j]};
-        if (phase == 0) {
-            // support point of {p - q} in direction (A, B): value = best - (A qx + B qy)
-            const double sv = best[0] - (A * q.x + B * q.y);
-            if (sv < 0.0) { state = 2; continue; }                                  // q outside the hull of the sites
-            if (sv == 0.0 && !(dim == 1 && (pa.x - q.x) * B == (pa.y - q.y) * A)) {  // q ON the hull boundary (supporting line of
-                state = 4; continue;                                                 // direction (A, B)): k_linear_boundary
-            }
-            if (dim == 0) { pa = p; ia = j; A = -(p.x - q.x); B = -(p.y - q.y); dim = 1; continue; }
-            if (dim == 1) {
-                pb = p; ib = j;
-                const double abx = pa.x - pb.x, aby = pa.y - pb.y;
-                double px = -aby, py = abx;                                          // perpendicular to ab, turned towards q
-                const double t = px * (q.x - pb.x) + py * (q.y - pb.y);
-                if (t < 0.0) { px = -px; py = -py; }
-                // t == 0: q lies strictly inside segment ab (sv > 0 put b beyond q), but a and b are far-apart EXTREME sites, not
-                // Delaunay neighbours -- never interpolate along ab.  Keep either perpendicular: a site strictly on that side closes a
-                // triangle with q on its edge ab (the containment tests are inclusive) and phase 1 pivots to the Delaunay triangle;
-                // no site on that side (sv == 0 next round) makes line ab a supporting line of the hull: k_linear_boundary takes the
-                // nearest site on either side of q along it -- which is also the answer when ALL sites are collinear.
-                A = px; B = py; dim = 2; continue;
-            }
-            pc = p; ic = j;
-            // triangle (c, b, a): which edge region of the newest vertex holds q?
-            const double cbx = pb.x - pc.x, cby = pb.y - pc.y, cax = pa.x - pc.x, cay = pa.y - pc.y;
-            const double cox = q.x - pc.x, coy = q.y - pc.y;
-            double nbx = -cby, nby = cbx;                                            // perpendicular to cb, away from a
-            if (nbx * cax + nby * cay > 0.0) { nbx = -nbx; nby = -nby; }
-            double nax = -cay, nay = cax;                                            // perpendicular to ca, away from b
-            if (nax * cbx + nay * cby > 0.0) { nax = -nax; nay = -nay; }
-            if (nbx * cox + nby * coy > 0.0) { pa = pb; ia = ib; pb = pc; ib = ic; A = nbx; B = nby; continue; }
-            if (nax * cox + nay * coy > 0.0) { pb = pc; ib = ic; A = nax; B = nay; continue; }
-            if (orient(pa, pb, pc) == 0.0) { state = 2; continue; }                  // (degenerate: collinear sites only)
-            if (orient(pa, pb, pc) < 0.0) { const i2 tp = pb; pb = pc; pc = tp; const int ti = ib; ib = ic; ic = ti; }
-            phase = 1;
-        } else {
-            // deepest site inside the circumcircle of (a, b, c): violation <=> score + K > 0
-            if (best[0] + K <= 0.0) { state = 1; continue; }
-            // the site replaces the vertex that keeps q inside (fan of the new site over the old triangle)
-            const i2 t0[3] = {p, pa, pa}, t1[3] = {pb, p, pb}, t2[3] = {pc, pc, p};
-            const int n0[3] = {j, ia, ia}, n1[3] = {ib, j, ib}, n2[3] = {ic, ic, j};
-            int pick = -1;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                if (pick >= 0) continue;
-                if (orient(t0[k], t1[k], t2[k]) > 0.0 && orient(t0[k], t1[k], q) >= 0.0 && orient(t1[k], t2[k], q) >= 0.0 &&
-                    orient(t2[k], t0[k], q) >= 0.0) pick = k;
-            }
-            if (pick < 0) { state = 1; atomicAdd(unresolved, 1); continue; }         // cannot happen for q inside (a, b, c)
-            pa = t0[pick]; pb = t1[pick]; pc = t2[pick]; ia = n0[pick]; ib = n1[pick]; ic = n2[pick];
-        }
-        // lifted plane through a', b', c' (counter-clockwise): N = (b' - a') x (c' - a'); p' below it <=> N . (p' - a') < 0
-        const double ar = pa.x * pa.x + pa.y * pa.y, br = pb.x * pb.x + pb.y * pb.y, cr = pc.x * pc.x + pc.y * pc.y;
-        const double ux = pb.x - pa.x, uy = pb.y - pa.y, uz = br - ar, vx = pc.x - pa.x, vy = pc.y - pa.y, vz = cr - ar;
-        const double Nx = uy * vz - uz * vy, Ny = uz * vx - ux * vz, Nz = ux * vy - uy * vx;
-        A = -Nx; B = -Ny; Cc = -Nz; K = (Nx * pa.x + Ny * pa.y) + Nz * ar;
+        if (!lin_step<true>(s, best[0], j, {(double)sx[j], (double)sy[j]})) { s.state = 1; atomicAdd(unresolved, 1); }   // no pick: keep the triangle, count it
     }
     if (!owner) return;
-    if (state == 0) { atomicAdd(unresolved, 1); state = phase == 1 ? 1 : 2; }   // round cap: phase 1 holds a triangle that contains q (valid, not Delaunay)
-    if (state == 4) {                                     // on the hull boundary: finished by k_linear_boundary
+    if (s.state == 0) { atomicAdd(unresolved, 1); s.state = s.phase == 1 ? 1 : 2; }   // round cap: phase 1 holds a triangle that contains q (valid, not Delaunay)
+    if (s.state == 4) {                                   // on the hull boundary: finished by k_linear_boundary
         const int k = atomicAdd(bcount, 1);
-        blist[3 * k] = b * n + qi; blist[3 * k + 1] = (int)A; blist[3 * k + 2] = (int)B;
+        blist[3 * k] = b * n + qi; blist[3 * k + 1] = (int)s.A; blist[3 * k + 2] = (int)s.B;
         return;
     }
     float* o = out + (size_t)b * C * n + qi;
-    const float* im = img + (size_t)b * C * n;
-    if (tri) { int32_t* t = tri + ((size_t)b * n + qi) * 3; t[0] = state == 1 ? ia : -2; t[1] = state == 1 ? ib : -2; t[2] = state == 1 ? ic : -2; }
-    if (state != 1) {
+    // state 1 is only ever reached from phase 1, which holds a proper triangle (three distinct sites, positive orientation)
+    if (tri) { int32_t* t = tri + ((size_t)b * n + qi) * 3; t[0] = s.state == 1 ? s.ia : -2; t[1] = s.state == 1 ? s.ib : -2; t[2] = s.state == 1 ? s.ic : -2; }
+    if (s.state != 1) {
         for (int c = 0; c < C; ++c) o[(size_t)c * n] = __builtin_nanf("");
         return;
     }
-    const int xa = (int)pa.y * W + (int)pa.x, xb = (int)pb.y * W + (int)pb.x, xc = (int)pc.y * W + (int)pc.x;
-    if (ib == ic) {                                                                  // q on the segment (a, b)
-        const double len = (pb.x - pa.x) * (pb.x - pa.x) + (pb.y - pa.y) * (pb.y - pa.y);
-        const double t = ((q.x - pa.x) * (pb.x - pa.x) + (q.y - pa.y) * (pb.y - pa.y)) / len;
-        for (int c = 0; c < C; ++c) o[(size_t)c * n] = (float)((1.0 - t) * (double)im[(size_t)c * n + xa] + t * (double)im[(size_t)c * n + xb]);
-        return;
-    }
-    const double wa = orient(q, pb, pc), wb = orient(pa, q, pc), wc = orient(pa, pb, q), Wt = orient(pa, pb, pc);
-    for (int c = 0; c < C; ++c) {
-        const double v = (wa * (double)im[(size_t)c * n + xa] + wb * (double)im[(size_t)c * n + xb]) + wc * (double)im[(size_t)c * n + xc];
-        o[(size_t)c * n] = (float)(v / Wt);
-    }
+    lin_store_bary(img + (size_t)b * C * n, o, C, n, W, s);
 }
 
 // ---- local first pass (round 3).  The reference's images are dense in sites (background + splatted points), so the Delaunay triangle
@@ -300,17 +342,14 @@ __global__ __launch_bounds__(256) void k_linear_local(const float* __restrict__ 
     const int tile = blockIdx.x * 4 + wave;
     if (tile >= tiles_x * tiles_y) return;
     const int tx0 = (tile % tiles_x) * LT_, ty0 = (tile / tiles_x) * LT_;
-    auto is_site = [&](int y, int x) -> bool {
-        const size_t i = (size_t)b * mask_bstride + (size_t)y * W + x;
-        return mask_is_f32 ? reinterpret_cast<const float*>(mask)[i] != 0.0f : reinterpret_cast<const uint8_t*>(mask)[i] != 0;
-    };
+    const size_t mb = (size_t)b * mask_bstride;            // the image's mask: pixel (x, y) at mb + y W + x
     // ---- the tile's queries
     int NQ = 0;
     for (int i0 = 0; i0 < LT_ * LT_; i0 += 64) {
         const int i = i0 + lane, ly = i / LT_, lx = i - ly * LT_;
         bool qry = ty0 + ly < H && tx0 + lx < W;
         if (FROM_TODO) qry = qry && todo[(size_t)b * n + (size_t)(ty0 + ly) * W + tx0 + lx] != 0;
-        else qry = qry && !is_site(ty0 + ly, tx0 + lx);
+        else qry = qry && !lin_site(mask, mask_is_f32, mb + (size_t)(ty0 + ly) * W + tx0 + lx);
         const unsigned long long bq = __ballot(qry);
         if (qry) s_q[wave][NQ + __popcll(bq & ((1ull << lane) - 1ull))] = (unsigned short)(lx | (ly << 8));
         NQ += __popcll(bq);
@@ -322,13 +361,12 @@ __global__ __launch_bounds__(256) void k_linear_local(const float* __restrict__ 
     int NS = 0;
     for (int i0 = 0; i0 < ww * wh; i0 += 64) {
         const int i = i0 + lane, ly = i / ww, lx = i - ly * ww;
-        const bool st = i < ww * wh && is_site(wy0 + ly, wx0 + lx);
+        const bool st = i < ww * wh && lin_site(mask, mask_is_f32, mb + (size_t)(wy0 + ly) * W + wx0 + lx);
         const unsigned long long bs = __ballot(st);
         if (st) s_site[wave][NS + __popcll(bs & ((1ull << lane) - 1ull))] = (unsigned)(wx0 + lx) | ((unsigned)(wy0 + ly) << 16);
         NS += __popcll(bs);
     }
     __builtin_amdgcn_wave_barrier();
-    constexpr int ST = 64 / LQ;
     const int kq = lane / ST;
     const bool slot = (lane % ST) == 0;
     for (int q0 = 0; q0 < NQ; q0 += LQ) {
@@ -336,14 +374,10 @@ __global__ __launch_bounds__(256) void k_linear_local(const float* __restrict__ 
         const unsigned qp = owner ? s_q[wave][q0 + kq] : 0;
         const int qxi = tx0 + (int)(qp & 255), qyi = ty0 + (int)(qp >> 8);
         const int qi = qyi * W + qxi;
-        const i2 q = {(double)qxi, (double)qyi};
-        int phase = 0, dim = 0;
-        int state = owner ? (NS > 0 ? 0 : 2) : 3;        // 0 running, 1 done, 2 outside the window's hull, 3 idle, 4 on its boundary
-        i2 pa = {0, 0}, pb = {0, 0}, pc = {0, 0};
-        double A = 1.0, B = 0.0, Cc = 0.0, K = 0.0;
+        LinQuery s = lin_query({(double)qxi, (double)qyi}, owner, NS);   // (state 2 / 4: outside the WINDOW's hull / on its boundary)
         for (int round = 0; round < LIN_MAX_ROUNDS; ++round) {
-            if (__ballot(state == 0) == 0ull) break;
-            if (slot) { s_co[wave][kq][0] = A; s_co[wave][kq][1] = B; s_co[wave][kq][2] = Cc; }
+            if (__ballot(s.state == 0) == 0ull) break;
+            if (slot) { s_co[wave][kq][0] = s.A; s_co[wave][kq][1] = s.B; s_co[wave][kq][2] = s.Cc; }
             __builtin_amdgcn_wave_barrier();
             double ca[LQ], cb[LQ], cc[LQ], best[LQ];
             int bi[LQ];
@@ -358,75 +392,14 @@ __global__ __launch_bounds__(256) void k_linear_local(const float* __restrict__ 
                     if (val > best[k]) { best[k] = val; bi[k] = j; }
                 }
             }
-#define LIN_HALVE(I)                                                                                                  \
-            if constexpr ((LQ >> (I)) > 1) {                                                                          \
-                constexpr int off = 32 >> (I), nn = LQ >> (I);                                                        \
-                const bool hi = (lane & off) != 0;                                                                    \
-                _Pragma("unroll") for (int k = 0; k < nn / 2; ++k) {                                                  \
-                    const double send = hi ? best[k] : best[k + nn / 2], keep = hi ? best[k + nn / 2] : best[k];      \
-                    const int sendi = hi ? bi[k] : bi[k + nn / 2], keepi = hi ? bi[k + nn / 2] : bi[k];               \
-                    const double ob = __shfl_xor(send, off);                                                          \
-                    const int oi = __shfl_xor(sendi, off);                                                            \
-                    const bool take = ob > keep || (ob == keep && oi < keepi);                                        \
-                    best[k] = take ? ob : keep; bi[k] = take ? oi : keepi;                                            \
-                }                                                                                                     \
-            }
-            LIN_HALVE(0) LIN_HALVE(1) LIN_HALVE(2) LIN_HALVE(3)
-#undef LIN_HALVE
-#pragma unroll
-            for (int off = ST / 2; off > 0; off >>= 1) {
-                const double ob = __shfl_xor(best[0], off);
-                const int oi = __shfl_xor(bi[0], off);
-                if (ob > best[0] || (ob == best[0] && oi < bi[0])) { best[0] = ob; bi[0] = oi; }
-            }
-            if (state != 0) continue;
+            LIN_ARGMAX_MERGE(best, bi, lane)
+            if (s.state != 0) continue;
             const unsigned sp = s_site[wave][bi[0]];
-            const i2 p = {(double)(sp & 0xffffu), (double)(sp >> 16)};
-            if (phase == 0) {
-                const double sv = best[0] - (A * q.x + B * q.y);
-                if (sv < 0.0) { state = 2; continue; }
-                if (sv == 0.0 && !(dim == 1 && (pa.x - q.x) * B == (pa.y - q.y) * A)) { state = 4; continue; }
-                if (dim == 0) { pa = p; A = -(p.x - q.x); B = -(p.y - q.y); dim = 1; continue; }
-                if (dim == 1) {
-                    pb = p;
-                    const double abx = pa.x - pb.x, aby = pa.y - pb.y;
-                    double px = -aby, py = abx;
-                    const double t = px * (q.x - pb.x) + py * (q.y - pb.y);
-                    if (t < 0.0) { px = -px; py = -py; }
-                    A = px; B = py; dim = 2; continue;
-                }
-                pc = p;
-                const double cbx = pb.x - pc.x, cby = pb.y - pc.y, cax = pa.x - pc.x, cay = pa.y - pc.y;
-                const double cox = q.x - pc.x, coy = q.y - pc.y;
-                double nbx = -cby, nby = cbx;
-                if (nbx * cax + nby * cay > 0.0) { nbx = -nbx; nby = -nby; }
-                double nax = -cay, nay = cax;
-                if (nax * cbx + nay * cby > 0.0) { nax = -nax; nay = -nay; }
-                if (nbx * cox + nby * coy > 0.0) { pa = pb; pb = pc; A = nbx; B = nby; continue; }
-                if (nax * cox + nay * coy > 0.0) { pb = pc; A = nax; B = nay; continue; }
-                if (orient(pa, pb, pc) == 0.0) { state = 2; continue; }
-                if (orient(pa, pb, pc) < 0.0) { const i2 tp = pb; pb = pc; pc = tp; }
-                phase = 1;
-            } else {
-                if (best[0] + K <= 0.0) { state = 1; continue; }
-                const i2 t0[3] = {p, pa, pa}, t1[3] = {pb, p, pb}, t2[3] = {pc, pc, p};
-                int pick = -1;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    if (pick >= 0) continue;
-                    if (orient(t0[k], t1[k], t2[k]) > 0.0 && orient(t0[k], t1[k], q) >= 0.0 && orient(t1[k], t2[k], q) >= 0.0 &&
-                        orient(t2[k], t0[k], q) >= 0.0) pick = k;
-                }
-                if (pick < 0) { state = 2; continue; }                                   // (cannot happen; the global kernel decides)
-                pa = t0[pick]; pb = t1[pick]; pc = t2[pick];
-            }
-            const double ar = pa.x * pa.x + pa.y * pa.y, br = pb.x * pb.x + pb.y * pb.y, cr = pc.x * pc.x + pc.y * pc.y;
-            const double ux = pb.x - pa.x, uy = pb.y - pa.y, uz = br - ar, vx = pc.x - pa.x, vy = pc.y - pa.y, vz = cr - ar;
-            const double Nx = uy * vz - uz * vy, Ny = uz * vx - ux * vz, Nz = ux * vy - uy * vx;
-            A = -Nx; B = -Ny; Cc = -Nz; K = (Nx * pa.x + Ny * pa.y) + Nz * ar;
+            if (!lin_step<false>(s, best[0], bi[0], {(double)(sp & 0xffffu), (double)(sp >> 16)})) s.state = 2;   // no pick: the global kernel decides
         }
         if (!owner) continue;
-        bool accept = state == 1;
+        const i2 pa = s.pa, pb = s.pb, pc = s.pc;
+        bool accept = s.state == 1;                          // (a query at the round cap is not accepted either: the global kernel counts it)
         if (accept) {
             // circumcircle of (a, b, c) against the window: centre = -(Nx, Ny) / (2 Nz) of the lifted plane, conservative margins
             const double ar = pa.x * pa.x + pa.y * pa.y, br = pb.x * pb.x + pb.y * pb.y, cr = pc.x * pc.x + pc.y * pc.y;
@@ -445,24 +418,18 @@ __global__ __launch_bounds__(256) void k_linear_local(const float* __restrict__ 
             }
             continue;
         }
-        float* o = out + (size_t)b * C * n + qi;
-        const float* im = img + (size_t)b * C * n;
         if (tri) {
-            // site-list index (row-major rank) of a vertex: sites before its row + sites before it in the row (debug / test path)
+            // site-list index (row-major rank) of a vertex: sites before its row + sites before it in the row (debug / test path; the window's
+            // indices are not the image's, so lin_step does not track them here)
             auto rank = [&](i2 v) -> int {
                 int r = rowstart[(size_t)b * (H + 1) + (int)v.y];
-                for (int x = 0; x < (int)v.x; ++x) r += is_site((int)v.y, x) ? 1 : 0;
+                for (int x = 0; x < (int)v.x; ++x) r += lin_site(mask, mask_is_f32, mb + (size_t)(int)v.y * W + x) ? 1 : 0;
                 return r;
             };
             int32_t* t = tri + ((size_t)b * n + qi) * 3;
             t[0] = rank(pa); t[1] = rank(pb); t[2] = rank(pc);
         }
-        const int xa = (int)pa.y * W + (int)pa.x, xb = (int)pb.y * W + (int)pb.x, xc = (int)pc.y * W + (int)pc.x;
-        const double wa = orient(q, pb, pc), wb = orient(pa, q, pc), wc = orient(pa, pb, q), Wt = orient(pa, pb, pc);
-        for (int c = 0; c < C; ++c) {
-            const double v = (wa * (double)im[(size_t)c * n + xa] + wb * (double)im[(size_t)c * n + xb]) + wc * (double)im[(size_t)c * n + xc];
-            o[(size_t)c * n] = (float)(v / Wt);
-        }
+        lin_store_bary(img + (size_t)b * C * n, out + (size_t)b * C * n + qi, C, n, W, s);
     }
 }
 
@@ -567,9 +534,9 @@ extern "C" int pdhip_linear_fill(const float* img, float* out, int B, int C, int
             k_linear_local<LW1, LT1, false, true><<<dim3(cdiv(tiles1, 4), B), 256, 0, s>>>(img, out, C, H, W, mask, mask_is_f32, mask_batch_stride, w.rowstart, tri, w.qlist, w.fbcount, w.todo);
             k_linear_local<LW, LT, true, false><<<dim3(cdiv(tiles, 4), B), 256, 0, s>>>(img, out, C, H, W, mask, mask_is_f32, mask_batch_stride, w.rowstart, tri, w.qlist, w.fbcount, w.todo);
         }
-        k_linear_tri<<<dim3(cdiv(n, 4 * LQ), B), 256, 0, s>>>(img, out, C, H, W, w.sites, w.qlist, w.fbcount, tri, w.unresolved, w.bcount, w.blist);
-    } else
-    k_linear_tri<<<dim3(cdiv(n, 4 * LQ), B), 256, 0, s>>>(img, out, C, H, W, w.sites, w.qlist, w.counts, tri, w.unresolved, w.bcount, w.blist);
+    }
+    // (NS, NQ) per image: behind the local passes the fallback list and its count, else every query of the image
+    k_linear_tri<<<dim3(cdiv(n, 4 * LQ), B), 256, 0, s>>>(img, out, C, H, W, w.sites, w.qlist, local ? w.fbcount : w.counts, tri, w.unresolved, w.bcount, w.blist);
     k_linear_boundary<<<256, 64, 0, s>>>(img, out, C, H, W, w.sites, w.counts, w.bcount, w.blist, tri);
     PD_LAUNCH_CHECK();
     return PDHIP_OK;

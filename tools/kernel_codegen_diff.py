@@ -3,7 +3,8 @@
   python tools/kernel_codegen_diff.py BASE_CSRC HEAD_CSRC [-o table.txt] [unit.hip ...]
 
 BASE_CSRC / HEAD_CSRC: two copies of pointdreamer_amd/csrc (the base usually from `git worktree add <dir> <commit>`).  Every unit (default: the five
-conv units) is compiled to gfx950 assembly with the flags of csrc/Makefile's nn_% rule plus `--cuda-device-only -S`; no GPU is needed.  Per kernel
+conv units) is compiled to gfx950 assembly with the flags of the csrc/Makefile rule that builds it -- the nn_% rule, or the geometry rule (which adds
+`-ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form=1`) for a unit not named nn_* -- plus `--cuda-device-only -S`; no GPU is needed.  Per kernel
 symbol the table holds the register counts, LDS and scratch sizes and spill count of the code object's metadata, the instruction count, and a verdict:
 
   identical   the instruction streams are equal once labels, comments and directive lines are stripped (branch targets compared by position)
@@ -24,13 +25,15 @@ import tempfile
 
 UNITS = ['nn_gemm.hip', 'nn_conv_halo.hip', 'nn_conv_ht.hip', 'nn_conv_sk.hip', 'nn_conv_rr.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function', '--cuda-device-only', '-S']
+GEO_FLAGS = ['-ffp-contract=off', '-mllvm', '-amdgpu-mfma-vgpr-form=1']          # what csrc/Makefile's rule for every unit not named nn_* adds
 META = ('.vgpr_count', '.sgpr_count', '.group_segment_fixed_size', '.private_segment_fixed_size', '.vgpr_spill_count')
 LABEL = re.compile(r'^([.\w$]+):')
 
 
 def assemble(csrc, unit, out):
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    subprocess.run([hipcc] + FLAGS + [unit, '-o', out], cwd=csrc, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
+    geo = [] if os.path.basename(unit).startswith('nn_') else GEO_FLAGS
+    subprocess.run([hipcc] + FLAGS + geo + [unit, '-o', out], cwd=csrc, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
     return out
 
 
@@ -111,7 +114,7 @@ def main():
                     verdict, bad = f"CHANGED d={sum(((cb - ch) + (ch - cb)).values())}", bad + 1
                 cols = ' '.join(f"{b.get(k, '?')}/{h.get(k, '?')}".rjust(13) for k in META)
                 rows.append(f"{u:18s} {verdict:13s} {cols} {len(b['stream']):6d}/{len(h['stream']):<6d} {nice[name]}")
-    head = (f"# base/head per kernel: {' '.join(k[1:] for k in META)} instructions   (flags: {' '.join(FLAGS)})\n"
+    head = (f"# base/head per kernel: {' '.join(k[1:] for k in META)} instructions   (flags: {' '.join(FLAGS)}; units not named nn_*: + {' '.join(GEO_FLAGS)})\n"
             f"# {len(rows)} kernel instances, {bad} changed or unmatched")
     text = head + '\n' + '\n'.join(rows) + '\n'
     if a.out:
