@@ -951,6 +951,54 @@ int pdhip_clean_faces(const int64_t* faces, int F, const int32_t* rep, int Vn, i
                       uint64_t* keys_b, int32_t* vals_a, int32_t* vals_b, size_t sort_len, int32_t* hist, size_t hist_words, int32_t* misc,
                       size_t misc_len, void* stream);
 
+/* ---- coherent orientation of a face list, patch by patch, closed patches outward (csrc/mesh_orient.hip; the reference gets it from its loaders:
+ * trimesh.repair.fix_normals, pymeshlab's "Re-Orient all faces coherently").  The step behind the cleaning in the chain for SUPPLIED meshes:
+ * clean -> orient -> components -> smooth -> decimate -> unwrap -> texture.  EVERY buffer is an argument the caller allocates: there is no workspace and
+ * no size query; the entry is told the length of every temporary and refuses a short one by name.
+ * pdhip_orient_faces: vertices (device [Vn,3] f32) and faces (device [F,3] i64, any indexed triangle list with indices in [0, Vn)).  Definitions:
+ *   - A face with two equal indices is DEGENERATE: it has no edges, is never flipped and gets face_patch = -1.
+ *   - Every other face f has three HALF-EDGES (a, b) = (f[k], f[(k + 1) % 3]), each with the undirected key {lo, hi} and the direction bit d = (a > b).
+ *   - An edge is MANIFOLD when exactly two half-edges carry its key, BOUNDARY with one, NON-MANIFOLD with three or more.
+ *   - Orientation crosses manifold edges only (as in MeshLab and trimesh).  The parity of a manifold edge is e = (d1 == d2): e = 1 means that its two
+ *     faces traverse it in the same direction, so one of them must flip.
+ *   - A PATCH is a connected component of the non-degenerate faces across manifold edges, its root its smallest face index; patches are numbered
+ *     0 .. P - 1 by ascending root.
+ *   - rel[f] is the XOR of the edge parities along any path from the root to f.  A patch is NON-ORIENTABLE when some manifold edge has
+ *     rel[fa] ^ rel[fb] != e (the paths then disagree); none of its faces is flipped, its patch_flipped and patch_vol are 0.
+ *   - A patch is CLOSED when none of its faces has a boundary or a non-manifold edge.
+ *   - Per orientable patch flip[f] = rel[f] ^ c, with c from one of two rules.  The VOLUME rule applies to closed patches, and with open_patches == 1
+ *     to every patch: the patch's box over the vertices its faces name, per axis lo and hi as f64; ext = the longest edge hi - lo of that box;
+ *     s = 4095.0 / ext, one f64 division (s = 0 when ext == 0); q = clamp(floor(((double)x - lo) * s), 0, 4095) per coordinate (one subtraction, one
+ *     product, none fused); the centred integer coordinate is 2 q - 4095; vol = the sum over the patch's faces AS GIVEN of (1 - 2 rel[f]) det(A, B, C)
+ *     in int64 (|det| < 2^39 per face and F <= 2^23, so |vol| < 2^62: an integer sum, whatever its order).  vol < 0 gives c = 1, vol > 0 gives c = 0,
+ *     vol == 0 falls through to the MAJORITY rule: c = 1 when more faces of the patch have rel = 1 than rel = 0 (the fewest flips); a tie gives c = 0,
+ *     so the root keeps its winding.
+ *   - A flipped face (a, b, c) becomes (a, c, b): the first corner stays, so per-face rows such as an OBJ's `ft` flip by the same swap.
+ *   Every output is a function of the mesh alone: not of the order of the faces (except through "smallest index"), the rotation of a face's corners
+ *   (flip, the patches and every count; out_faces keeps each face's own first corner) or the threads' order; two calls give equal bytes.  Nested
+ *   cavities are NOT turned inward: each closed patch is turned outward on its own, as trimesh does for multibody meshes.  Nothing crosses a
+ *   non-manifold edge, and no hole is filled.
+ * Outputs (device): out_faces [F,3] i64 (every face, flipped or as given); flip [F] u8; face_patch [F] i32; per patch, entries [0, P) of arrays of F
+ * elements each (the rest is not touched): patch_root, patch_faces, patch_flipped (faces of the patch that were flipped) i32, patch_flags i32 (1 closed,
+ * 2 non-orientable, 4 decided by volume: the rule applied and vol != 0, 8 complemented: c = 1), patch_vol i64 (vol where the volume rule applied to an
+ * orientable patch, else 0); counts [8] i32: patches, faces flipped, non-orientable patches, incoherent manifold edges as given (e = 1), boundary edges,
+ * non-manifold edges, degenerate faces, 0.  open_patches: 0 = 'majority' (open patches by the majority rule), 1 = 'volume'.
+ * Temporaries (device; their contents before and after mean nothing): keys_a, keys_b [sort_len] u64 and vals_a, vals_b [sort_len] i32,
+ * sort_len >= 3 F (the half-edge table and its stable radix sort);  hist [hist_words] i32, hist_words >= 512 * ceil(3 F / 2048);  face_tmp
+ * [face_tmp_len] i32, face_tmp_len >= 5 F (the parity union-find's words, root, root flag, patch id, the face bits);  box [box_len] i32,
+ * box_len >= 6 F (the patch boxes in ordered bits);  tiles [tiles_len] i32, tiles_len >= 2 * (F / 2048 + 1) (the tiled scan's sums);  misc [misc_len]
+ * i32, misc_len >= 64.  Integer atomics only, zero scratch.  1 <= Vn <= 2^26, 1 <= F <= 2^23.
+ * PDHIP_E_ARG with the cause, every output untouched: a null pointer (named), sizes out of range, open_patches other than 0 and 1, a short temporary
+ * (named, with both lengths); and from the device (the temporaries are written, no output is): a face index outside [0, Vn), a referenced vertex (of a
+ * degenerate face too) that is not finite.  SYNCHRONISES the stream once, after the last launch (8 bytes).  Patches are found by the parity variant of
+ * csrc/union_find.h: one word parent << 1 | parity per face, hooks by compare-and-swap, path halving by one 32-bit store; non-orientability is decided
+ * by a later launch that re-checks every manifold edge.  A walk is bounded by 2 F + 64 steps; should one use them up, PDHIP_E_STATE. */
+int pdhip_orient_faces(const float* vertices, int Vn, const int64_t* faces, int F, int open_patches, int64_t* out_faces, uint8_t* flip,
+                       int32_t* face_patch, int32_t* patch_root, int32_t* patch_faces, int32_t* patch_flipped, int32_t* patch_flags, int64_t* patch_vol,
+                       int32_t* counts, uint64_t* keys_a, uint64_t* keys_b, int32_t* vals_a, int32_t* vals_b, size_t sort_len, int32_t* hist,
+                       size_t hist_words, int32_t* face_tmp, size_t face_tmp_len, int32_t* box, size_t box_len, int32_t* tiles, size_t tiles_len,
+                       int32_t* misc, size_t misc_len, void* stream);
+
 /* ---- test-only entries onto the shared device primitives (csrc/prims_debug.hip): the radix sort and the scans of csrc/radix_sort.h and the sort
  * half of csrc/cell_list.h, which every geometry unit that sorts or scans includes.  The kernels have internal linkage, so these entries run
  * prims_debug.hip's copy: the same source and the same flags as every consumer's.  Nothing the product calls (tests/test_gpu_prims.py).
@@ -975,12 +1023,22 @@ int pdhip_clean_faces(const int64_t* faces, int F, const int32_t* rep, int Vn, i
  * 2 = a walk used up its budget of steps; root then holds -1 where a walk ended).  Three steps: k_uf_identity; one thread per pair,
  * unite(find_root, find_root) with a budget of 2 n + 64 steps; one thread per vertex, walk_root with n steps.  1 <= n <= 2^26,
  * 0 <= n_pairs <= 2^26; no workspace.  With n_pairs > 0 it SYNCHRONISES once before the unions (4 bytes: the pairs with an index outside
- * [0, n) are counted on the device, and any is PDHIP_E_ARG before parent is touched). */
+ * [0, n) are counted on the device, and any is PDHIP_E_ARG before parent is touched).
+ * pdhip_debug_parity_union: the parity variant of that union-find, which mesh_orient.hip uses.  pairs (device [n_pairs, 2] i32) and parity (device
+ * [n_pairs] u8, 0 or 1: pair p says rel[a] ^ rel[b] == parity[p]; both may be NULL with n_pairs == 0) -> word (device [n] i32, the caller's: the
+ * forest, parent << 1 | parity, left as the unions made it), root (device [n] i32: the smallest index of every node's class), rel (device [n] u8: the
+ * parity of the node relative to its root along the forest; a function of the pairs alone in a class without conflict), conflict (device [n] u8: 1 for
+ * every node of a class in which some pair contradicts the forest's relations, i.e. which has no 2-colouring; decided by a launch that re-checks every
+ * pair after the unions, so it does not depend on the threads' order), status as above.  Five steps: k_ufp_identity; one thread per pair,
+ * unite_parity(find_root_parity, find_root_parity) with a budget of 2 n + 64 steps; one thread per node, walk_root_parity with n steps; the re-check;
+ * the spread of the flag from the roots.  Limits, the synchronisation and the refusals as pdhip_debug_union_pairs; a parity above 1 is refused too. */
 size_t pdhip_debug_prims_workspace_bytes(int n, int nc);
 int pdhip_debug_radix_sort(const uint64_t* keys, const int32_t* vals, int n, int bits, uint64_t* keys_out, int32_t* vals_out, void* ws, void* stream);
 int pdhip_debug_sort_by_cell(const uint64_t* keys, int n, int nc, uint64_t* keys_out, int32_t* idx_out, int32_t* cstart_out, void* ws, void* stream);
 int pdhip_debug_scan(const void* in, void* out, int n, int elem_bytes, int mode, int inclusive, int nc, void* ws, void* stream);
 int pdhip_debug_union_pairs(const int32_t* pairs, int n_pairs, int n, int32_t* parent, int32_t* root, int32_t* status, void* stream);
+int pdhip_debug_parity_union(const int32_t* pairs, const uint8_t* parity, int n_pairs, int n, int32_t* word, int32_t* root, uint8_t* rel,
+                             uint8_t* conflict, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

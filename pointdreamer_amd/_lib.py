@@ -88,6 +88,9 @@ _SIGS = {
     'pdhip_weld_cells_axis': (C.c_int, [i32]),
     'pdhip_weld_vertices': (C.c_int, [vp, i32, f64, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp]),
     'pdhip_clean_faces': (C.c_int, [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, sz, vp]),
+    'pdhip_orient_faces': (C.c_int, [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz,
+                                     vp, sz, vp]),
+    'pdhip_debug_parity_union': (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
     'pdhip_debug_prims_workspace_bytes': (sz, [i32, i32]),
     'pdhip_debug_radix_sort': (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp]),
     'pdhip_debug_sort_by_cell': (C.c_int, [vp, i32, i32, vp, vp, vp, vp, vp]),

@@ -1,7 +1,8 @@
 // Test-only entries onto the shared device primitives: the radix sort, the one-workgroup scan and the tiled scans of radix_sort.h, the sort
 // half of cell_list.h (k_cell_keys, k_cell_starts, sort_by_cell), and the union-find of union_find.h.  include/pdhip.h has the contracts;
 // tests/test_gpu_prims.py holds each of them to an exact numpy reference at the tile edges, tests/test_prims_cpu.py the references, the size
-// query and the refusals.  Nothing the product calls.
+// query and the refusals; tests/test_gpu_parity_union.py holds the union-find's parity variant (pdhip_debug_parity_union) to a sequential one.
+// Nothing the product calls.
 //
 // Every kernel of the headers has internal linkage, so each including unit carries a copy of its own, and no test can run the copy inside
 // uv_atlas.hip or knn.hip.  What the tests run is THIS unit's copy: compiled from the same source with the same flags (GEO_SRC of the Makefile)
@@ -39,6 +40,53 @@ __global__ void k_ufd_roots(const int* __restrict__ parent, int n, int32_t* __re
     const int r = walk_root(parent, v, steps);
     if (r < 0) atomicOr(status, UF_WALK);
     root[v] = r;
+}
+
+// ---- the parity variant: the pairs' check, the unions, the flatten, the re-check of every pair and the spread of the flag over the classes
+__global__ void k_ufp_check(const int32_t* __restrict__ pairs, const uint8_t* __restrict__ parity, int n_pairs, int n, int32_t* __restrict__ bad) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n_pairs && !(index_ok(pairs[2 * (size_t)p], n) && index_ok(pairs[2 * (size_t)p + 1], n) && parity[p] <= 1)) atomicAdd(bad, 1);
+}
+
+// one thread per pair, the budget mesh_orient.hip gives an edge
+__global__ __launch_bounds__(UF_T) void k_ufp_unite(const int32_t* __restrict__ pairs, const uint8_t* __restrict__ parity, int n_pairs, int n, int* word,
+                                                    int32_t* __restrict__ status) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs) return;
+    long long budget = 2ll * n + 64;
+    const int a = pairs[2 * (size_t)p], b = pairs[2 * (size_t)p + 1];
+    int pa, pb;
+    const int ra = find_root_parity(word, a, pa, budget), rb = find_root_parity(word, b, pb, budget);
+    if (unite_parity(word, ra, rb, pa ^ pb ^ (int)parity[p], budget) < 0) atomicOr(status, UF_UNITE);
+}
+
+__global__ void k_ufp_roots(const int* __restrict__ word, int n, int32_t* __restrict__ root, uint8_t* __restrict__ rel, uint8_t* __restrict__ conflict,
+                            int32_t* __restrict__ status) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    int steps = n, par;
+    const int r = walk_root_parity(word, v, par, steps);
+    if (r < 0) atomicOr(status, UF_WALK);
+    root[v] = r;
+    rel[v] = (uint8_t)par;
+    conflict[v] = 0;
+}
+
+// a pair that the relations of the forest contradict flags its class, at the root
+__global__ void k_ufp_recheck(const int32_t* __restrict__ pairs, const uint8_t* __restrict__ parity, int n_pairs, const int32_t* __restrict__ root,
+                              const uint8_t* __restrict__ rel, uint8_t* __restrict__ conflict, const int32_t* __restrict__ status) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs || *status) return;
+    const int a = pairs[2 * (size_t)p], b = pairs[2 * (size_t)p + 1];
+    if ((rel[a] ^ rel[b]) != parity[p]) conflict[root[a]] = 1;
+}
+
+// (a root keeps its own flag; every other node writes a byte that nobody reads in this launch)
+__global__ void k_ufp_spread(const int32_t* __restrict__ root, int n, uint8_t* conflict, const int32_t* __restrict__ status) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n || *status) return;
+    const int r = root[v];
+    if (r != v && conflict[r]) conflict[v] = 1;
 }
 
 // KeyFn of sort_by_cell: the key of point i, read from an array
@@ -156,6 +204,36 @@ extern "C" int pdhip_debug_union_pairs(const int32_t* pairs, int n_pairs, int n,
     k_uf_identity<<<gn, UF_T, 0, s>>>(parent, n);
     if (n_pairs > 0) k_ufd_unite<<<gp, UF_T, 0, s>>>(pairs, n_pairs, n, parent, status);
     k_ufd_roots<<<gn, UF_T, 0, s>>>(parent, n, root, status);
+    PD_LAUNCH_CHECK();
+    return PDHIP_OK;
+}
+
+extern "C" int pdhip_debug_parity_union(const int32_t* pairs, const uint8_t* parity, int n_pairs, int n, int32_t* word, int32_t* root, uint8_t* rel,
+                                        uint8_t* conflict, int32_t* status, void* stream) {
+#define PR_PTR(p) PD_REQUIRE(p, "pdhip_debug_parity_union: null pointer (" #p ")")
+    PR_PTR(word); PR_PTR(root); PR_PTR(rel); PR_PTR(conflict); PR_PTR(status);
+#undef PR_PTR
+    PD_REQUIRE(n >= 1 && n <= MAX_N, "pdhip_debug_parity_union: n=%d outside [1, 2^26]", n);
+    PD_REQUIRE(n_pairs >= 0 && n_pairs <= MAX_N, "pdhip_debug_parity_union: n_pairs=%d outside [0, 2^26]", n_pairs);
+    PD_REQUIRE((pairs && parity) || n_pairs == 0, "pdhip_debug_parity_union: null pointer (%s) with n_pairs=%d", pairs ? "parity" : "pairs", n_pairs);
+    hipStream_t s = as_stream(stream);
+    const int gp = cdiv(n_pairs, UF_T), gn = cdiv(n, UF_T);
+    PD_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    if (n_pairs > 0) {                                              // no index outside [0, n) reaches word[]: counted before the unions start
+        k_ufp_check<<<gp, UF_T, 0, s>>>(pairs, parity, n_pairs, n, status);
+        PD_LAUNCH_CHECK();
+        int bad = 0;
+        const int rc = read_words(status, &bad, 1, s);
+        if (rc) return rc;
+        PD_REQUIRE(bad == 0, "pdhip_debug_parity_union: %d pair(s) with an index outside [0, n=%d) or a parity other than 0 and 1", bad, n);
+    }
+    k_ufp_identity<<<gn, UF_T, 0, s>>>(word, n);
+    if (n_pairs > 0) k_ufp_unite<<<gp, UF_T, 0, s>>>(pairs, parity, n_pairs, n, word, status);
+    k_ufp_roots<<<gn, UF_T, 0, s>>>(word, n, root, rel, conflict, status);
+    if (n_pairs > 0) {
+        k_ufp_recheck<<<gp, UF_T, 0, s>>>(pairs, parity, n_pairs, root, rel, conflict, status);
+        k_ufp_spread<<<gn, UF_T, 0, s>>>(root, n, conflict, status);
+    }
     PD_LAUNCH_CHECK();
     return PDHIP_OK;
 }

@@ -74,6 +74,11 @@ SMOOTH_KEYS = ('spr_smooth', 'spr_smooth_lambda', 'spr_smooth_mu')
 # the normalisation; mesh_weld_tolerance (default 0: exactly equal coordinates) is the welding distance as a share of the mesh's box diagonal, in
 # [0, 0.1], as MeshLab's percentage is.  The atlas cache of such a run is xatlas_<res>_weld.pth: it never shares one with a run without the key
 CLEAN_KEYS = ('mesh_clean', 'mesh_weld_tolerance')
+# opt-in stage behind that one, on a SUPPLIED mesh too (after the cleaning if that ran, before the normalisation): mesh_orient: 'coherent' makes the
+# faces of every patch agree and turns closed patches outward (mesh_orient.py); mesh_orient_open: 'majority' (default: an open patch keeps the winding of
+# most of its faces) or 'volume' (open patches follow the closed patches' rule).  The `ft` rows of flipped faces get the same (1, 2) swap, and the atlas
+# cache name gains _orient
+ORIENT_KEYS = ('mesh_orient', 'mesh_orient_open')
 
 
 class Cfg(dict):
@@ -114,7 +119,8 @@ def load_config(cfg_file, overrides=None):
     cfg = Cfg(yaml.safe_load(open(cfg_file)))
     cfg.update(overrides or {})
     unknown = [k for k in cfg if k not in SUPPORTED_KEYS and k not in UPSTREAM_KEYS and k not in GEOMETRY_KEYS and k not in RENDER_KEYS
-               and k not in SUBSAMPLE_KEYS and k not in OUTLIER_KEYS and k not in COMPONENT_KEYS and k not in SMOOTH_KEYS and k not in CLEAN_KEYS]
+               and k not in SUBSAMPLE_KEYS and k not in OUTLIER_KEYS and k not in COMPONENT_KEYS and k not in SMOOTH_KEYS and k not in CLEAN_KEYS
+               and k not in ORIENT_KEYS]
     if unknown:
         raise KeyError(f"{cfg_file}: unknown config keys {unknown}")
     if 'texture_gen_method' not in cfg:
@@ -176,6 +182,14 @@ def load_config(cfg_file, overrides=None):
         t = cfg.mesh_weld_tolerance
         if isinstance(t, bool) or not isinstance(t, (int, float)) or not 0.0 <= t <= 0.1:
             raise ValueError(f"mesh_weld_tolerance={t!r}: the welding distance is a share of the mesh's box diagonal in [0, 0.1]")
+    if 'mesh_orient' in cfg and cfg.mesh_orient not in ('coherent',):
+        raise ValueError(f"mesh_orient={cfg.mesh_orient!r}: the orientation of a supplied mesh is 'coherent' (the faces of every patch agree, closed "
+                         "patches face outward)")
+    if 'mesh_orient_open' in cfg:
+        if 'mesh_orient' not in cfg:
+            raise ValueError("mesh_orient_open steers the orientation that mesh_orient: coherent asks for: mesh_orient is missing")
+        if cfg.mesh_orient_open not in ('majority', 'volume'):
+            raise ValueError(f"mesh_orient_open={cfg.mesh_orient_open!r}: open patches are oriented by 'majority' or by 'volume'")
     if cfg.optimize_from == 'None':                      # YAML `None` is the string 'None' (demo.py:213 treats both alike)
         cfg['optimize_from'] = None
     return cfg
@@ -311,6 +325,20 @@ def _clean_supplied(cfg, vertices, faces, ft, logger):
     return v, f, ft
 
 
+def _orient_supplied(cfg, vertices, faces, ft, logger):
+    """The opt-in ORIENT_KEYS on a supplied mesh: faces coherently oriented; the `ft` rows (numpy, or None) of flipped faces get the same swap."""
+    from . import mesh_orient
+    rule = cfg.get('mesh_orient_open', 'majority')
+    f, flip, c = mesh_orient.orient_faces(vertices, faces, open_patches=rule, return_flip=True, return_counts=True)
+    logger.info(f'mesh_orient: coherent (open patches by {rule}): {c["patches"]} patches, {c["flipped"]} of {len(f)} faces flipped, '
+                f'{c["nonorientable_patches"]} non-orientable patches, {c["incoherent_edges"]} incoherent edges before')
+    if ft is not None:
+        m = flip.cpu().numpy().astype(bool)
+        ft = np.ascontiguousarray(ft).copy()
+        ft[m] = ft[m][:, [0, 2, 1]]
+    return f, ft
+
+
 def _load_shape(cfg, pc_file, name, device, logger):
     """demo.py:359-452: cloud, mesh and atlas of one shape, normalised as the reference does."""
     out = os.path.join(cfg.output_path, name)
@@ -341,7 +369,8 @@ def _load_shape(cfg, pc_file, name, device, logger):
     io_utils.save_colored_pc_ply(xyz.cpu().numpy(), rgb.cpu().numpy(), os.path.join(out, 'input_pc.ply'))
     geo_path = pc_file.replace('.ply', '_untextured_mesh.obj')
     weld = 'mesh_clean' in cfg and os.path.exists(geo_path)       # (the key touches a supplied mesh only)
-    xatlas_file = os.path.join(out, 'geo', f'xatlas_{cfg.xatlas_texture_res}{"_weld" if weld else ""}.pth')
+    orient = 'mesh_orient' in cfg and os.path.exists(geo_path)   # (likewise)
+    xatlas_file = os.path.join(out, 'geo', f'xatlas_{cfg.xatlas_texture_res}{"_weld" if weld else ""}{"_orient" if orient else ""}.pth')
     cached_geo = os.path.join(out, 'geo', f'{name}_untextured', 'models', 'model_normalized.obj')
     if not os.path.exists(geo_path) and not os.path.exists(cached_geo) and cfg.get('geo_from') == 'SPR':
         # baselines/spr.py:recon_one_shape_SPR on the normalised cloud (demo.py:411-416), on the device; the mesh goes to the
@@ -370,6 +399,8 @@ def _load_shape(cfg, pc_file, name, device, logger):
         faces = torch.from_numpy(f).to(device)
         if weld:
             vertices, faces, ft = _clean_supplied(cfg, vertices, faces, ft if vt is not None else None, logger)
+        if orient:
+            faces, ft = _orient_supplied(cfg, vertices, faces, ft if vt is not None else None, logger)
         if supplied:                                     # (the cached mesh was made from the normalised cloud: demo.py:401-406)
             vertices -= (vmax + vmin) / 2.
             vertices /= (vmax - vmin).max()
